@@ -2,12 +2,16 @@
 """Benchmark of the MRFP+ training hot path (one step = forward + backward + fused SGD on one synthetic
 batch, inputs resident in HBM).  Contract: prints ONE JSON line on rank 0.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload (config.workload): BASELINE.json's metric is quoted on ResNet-101 DeepLabV3+ + MRFP+ at 768x768,
 16 images per GPU, bf16 activations (configs[2]; configs[3] = the same per rank on 8 GPUs, weak scaling).
 All three perturbation toggles are forced ON (worst case).
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the line.
+--full adds what the headline does not need: the roofline of one extra per-launch-timed step (`roofline`, --dump-convs,
+--dump-launches) and the CPU-oracle baseline (`cpu_baseline`; off again with --no-cpu-baseline).
 """
 import argparse
 import ctypes
@@ -33,25 +37,35 @@ PEAK_F32_TFLOPS = 157.3
 PEAK_HBM_GBS = 8000.0
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--trunk", default="resnet-101", choices=["resnet-50", "resnet-101", "wider_resnet38_a2"])
     ap.add_argument("--size", type=int, default=768)
     ap.add_argument("--width", type=int, default=0, help="input width when not square (configs[4]: --size 1024 --width 2048)")
     ap.add_argument("--batch", type=int, default=16, help="images per GPU")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure the roofline (one extra per-launch-timed step) and the "
+                    "CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy "
+                    "(loss.npy; state_sample.npy: a fixed sample of the updated model state)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
     ap.add_argument("--graph", action="store_true", help="replay zero_grad + forward + backward as a hipGraph (single GPU)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--dump-convs", default=None, help="write per-launch conv shapes/timings (JSON) here")
-    ap.add_argument("--dump-launches", default=None, help="diagnostic: time EVERY C-ABI launch of one step on its own, write JSON here")
+    ap.add_argument("--dump-convs", default=None, help="with --full: write per-launch conv shapes/timings (JSON) here")
+    ap.add_argument("--dump-launches", default=None, help="with --full, diagnostic: time EVERY C-ABI launch of one step on its own, "
+                    "write JSON here")
     ap.add_argument("--fourier", action="store_true", help="variant: also attach the build-defined multi-resolution Fourier "
                     "amplitude perturbation (perturb.MultiResolutionFourier, every step) -- NOT the reference path, "
                     "reported as its own workload")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if (args.dump_convs or args.dump_launches) and not args.full:
+        ap.error("--dump-convs / --dump-launches come from the roofline step: add --full")
+    return args
 
 
 class HipTimer:
@@ -194,6 +208,10 @@ def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
+    # the same inputs in every run with the same arguments: weights and batch come from seeded generators (synth.py), the
+    # perturbation draws (HRFP re-draw, NP+ noise) from torch's global generators, seeded below with MRFP_SEED + rank -- the
+    # per-rank seeds harness.sync_replicas() sets in a multi-rank run, which would otherwise come from the OS
+    os.environ.setdefault("MRFP_SEED", "0")
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -231,6 +249,7 @@ def main():
     else:
         torch.cuda.set_device(0)
     dev = torch.device("cuda", local if world > 1 else 0)
+    torch.manual_seed(int(os.environ["MRFP_SEED"]) + rank)
 
     from mrfp_amd import synth, deepv3
     from mrfp_amd.config import cfg
@@ -295,11 +314,14 @@ def main():
         dist.all_reduce(ones)
         ranks_seen = int(ones.item())
 
-    # roofline of the dominant kernel family (the MFMA implicit-GEMM convolutions): algorithmic FLOPs of all conv
+    # what the last timed step computed, read before --full's extra step changes the model state
+    outputs = output_arrays(model, loss) if args.dump_outputs and rank == 0 else None
+
+    # --full: roofline of the dominant kernel family (the MFMA implicit-GEMM convolutions): algorithmic FLOPs of all conv
     # launches of one step / their summed device time, measured with hipEvents around each launch of ONE EXTRA step.
     # That step runs on EVERY rank (it issues the gradient all-reduces like any other step: rank 0 alone would leave the
     # other ranks' collectives unmatched); only rank 0 reports its timings.
-    roof = step_roofline(model, trainer, x, y, args)
+    roof = step_roofline(model, trainer, x, y, args) if args.full else None
     out = None
     if rank == 0:
         ms = 1e3 * elapsed / args.steps
@@ -319,11 +341,47 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         else:
             out["cpu_baseline"] = None
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
         print(json.dumps(out))
+
+
+DUMP_SAMPLE = 4096            # --dump-outputs: values kept per state tensor (all of a smaller one)
+DUMP_LIMIT = 64 << 20         # bytes, all files together
+
+
+def output_arrays(model, loss):
+    """What a caller of the timed path holds after its last step, as float32 numpy arrays: `loss`, the value the step returned,
+    and `state_sample`, the model state the step updated -- every floating tensor of model.state_dict() in state_dict order
+    (parameters, BatchNorm running statistics, the re-drawn HRFP weights), all of a tensor up to DUMP_SAMPLE values, else
+    DUMP_SAMPLE positions drawn by a generator seeded from its key: the same positions in every run and every build."""
+    import zlib
+    parts = []
+    with torch.no_grad():
+        for k, t in model.state_dict().items():
+            if not t.is_floating_point():
+                continue
+            flat = t.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                g = torch.Generator().manual_seed(zlib.crc32(k.encode()))
+                idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.float())
+        return {"loss": loss.detach().float().cpu().numpy(), "state_sample": torch.cat(parts).cpu().numpy()}
+
+
+def write_outputs(d, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("[bench] --dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def _eager_step(trainer, x, y):

@@ -190,8 +190,8 @@ def test_sync_switch_whiten_two_ranks_vs_reference(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# bench.py end to end at world size 2 (the roofline leg used to run on rank 0 only and would have left the
-# other ranks' collectives unmatched).  Both ranks share the one GPU, gloo transport.
+# bench.py --full end to end at world size 2 (the roofline leg used to run on rank 0 only and would have left
+# the other ranks' collectives unmatched).  Both ranks share the one GPU, gloo transport.
 # ---------------------------------------------------------------------------------------------------------------------
 def test_bench_two_ranks_end_to_end():
     import json
@@ -199,7 +199,7 @@ def test_bench_two_ranks_end_to_end():
     env = dict(os.environ, MRFP_BENCH_SHARE_GPU="1", MRFP_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29753", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--trunk", "resnet-50", "--size", "128", "--batch", "2", "--dtype", "bf16"]
+           "--trunk", "resnet-50", "--size", "128", "--batch", "2", "--dtype", "bf16", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

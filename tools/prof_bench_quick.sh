@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp MRFP_WGRAD_STREAM=0
 O=$R/gpurun_out/pbq; rm -rf $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o b -- python3 $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline > $O.log 2>&1 || { tail -5 $O.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o b -- python3 $R/bench.py --steps 3 --warmup 2 --full --no-cpu-baseline > $O.log 2>&1 || { tail -5 $O.log; exit 1; }
 cd $R && python3 - "$1" <<'PY'
 import csv, glob, re, sys
 pat = re.compile(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1] else None

@@ -1,9 +1,9 @@
-"""Reads gpurun_out/sweep_*.json (tools/tile_sweep.sh) and prints, per distinct convolution launch shape of the bench step, the time under
+"""Reads $MRFP_OUT/sweep_*.json (default out/, written by tools/tile_sweep.sh) and prints, per distinct convolution launch shape of the bench step, the time under
 every tile override next to the default choice -- where a fixed override beats the built-in heuristics by more than the run-to-run noise
 (two default runs are in the set), the heuristics have something to learn."""
 import glob, json, os, collections
 runs = {}
-for f in sorted(glob.glob("gpurun_out/sweep_*.json")):
+for f in sorted(glob.glob(os.path.join(os.environ.get("MRFP_OUT", "out"), "sweep_*.json"))):
     tag = os.path.basename(f)[6:-5]
     g = collections.OrderedDict()
     for r in json.load(open(f)):

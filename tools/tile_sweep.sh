@@ -1,6 +1,7 @@
 # per-shape convolution times under every tile override (one box): gpurun -- bash tools/tile_sweep.sh ; then python tools/tile_sweep.py
 cd ${GRAFT_REPO_ROOT:-/root/repo}
-run() { tag=$1; shift; env "$@" python bench.py --steps 3 --warmup 2 --no-cpu-baseline --dump-convs gpurun_out/sweep_$tag.json > /dev/null 2>&1; echo "$tag done"; }
+O=${MRFP_OUT:-out}; mkdir -p $O            # results directory, relative to the repository root
+run() { tag=$1; shift; env "$@" python bench.py --steps 3 --warmup 2 --full --no-cpu-baseline --dump-convs $O/sweep_$tag.json > /dev/null 2>&1; echo "$tag done"; }
 run default MRFP_X=0
 run default2 MRFP_X=0
 run t96_0 MRFP_CONV_T96=0
