@@ -402,6 +402,23 @@ int mrfp_u8hwc_to_f32chw(const void* src, float* dst, int64_t H, int64_t W, void
 int mrfp_jitter_u8(const void* src, void* dst, int64_t npix, int op, float factor, int shift, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Frequency filters of the input pipeline (reference dataloaders.py:24-45 HPF, 59-79 LPF, 47-57 PHOT: np.fft.fftn over the
+ * (H,W,3) image), on the ToTensor layout: x, y float32 [B,3,H,W] (y may be x).  Signed frequencies as the reference's fftshift
+ * gives them: f = i - n//2, f in [-(n//2), n-1-n//2].  twH / twW: float2 tables exp(-2 pi i t/N), t < N, N = H and N = W
+ * (built in double on the host).  ws: mrfp_band_filter_ws_bytes / mrfp_phot_ws_bytes bytes (-1: arguments not supported).
+ *   mrfp_band_filter: per channel plane low = Re(IDFT2(F * band)); high != 0 (HPF): band = fy^2 + fx^2 <= radius^2, y = x - low;
+ *     high == 0 (LPF): band = fy^2 + fx^2 < radius^2, y = low.  A band-limited DFT (no full transform), any H, W < 65536,
+ *     0 <= radius < 33; no atomics: bitwise reproducible.
+ *   mrfp_phot: y = Re(ifftn(F / |F|)) * 5 * 255 over the 3-D spectrum (channel axis included); a zero bin gives NaN as numpy
+ *     does (a grey image: all NaN).  H and W of the form 2^a 3^b 5^c, each <= 4096; other lengths fail naming the length.
+ * ------------------------------------------------------------------------------------------- */
+int64_t mrfp_band_filter_ws_bytes(int64_t B, int64_t H, int64_t W, float radius);
+int mrfp_band_filter(const float* x, float* y, void* ws, const void* twH, const void* twW, int64_t B, int64_t H, int64_t W,
+                     float radius, int high, void* stream);
+int64_t mrfp_phot_ws_bytes(int64_t B, int64_t H, int64_t W);
+int mrfp_phot(const float* x, float* y, void* ws, const void* twH, const void* twW, int64_t B, int64_t H, int64_t W, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Whitening-loss setup (host-side, no kernel; csrc/hostmath.hip).
  *   mrfp_kmeans1d: globally optimal k-means of n doubles into k clusters -- what `kmeans1d.cluster(var_flatten,
  *     self.clusters)` does at reference network/cov_settings.py:57 (kmeans1d is an un-vendored PyPI dependency; its published

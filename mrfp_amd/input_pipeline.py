@@ -1,4 +1,9 @@
-"""The reference's training transform (main.py:409-419 transform_tr) on the GPU, bit-exact with its PIL calls.
+"""The reference's training transforms (main.py:409-419 transform_tr and the Resize / Crop compositions of its other training
+sets) on the GPU, bit-exact with their PIL calls, and its frequency filters HPF / LPF / PHOT (dataloaders.py:24-79).
+
+ResizeTransform (main.py:319-330, 499-507, 592-603) and CropTransform (main.py:764-773) reuse the kernels below: Pillow's BILINEAR
+tables for the resampler, the assemble kernel with no padding, and the same flip, jitter and blur steps as TrainTransform.
+hpf / lpf / phot (csrc/freq.hip) take the ToTensor layout float32 [3,H,W] or [B,3,H,W].
 
 Reference: main.py:409-419 `transform_tr` = RandomHorizontalFlip -> ColorJitter -> RandomSizeAndCrop(crop_size,
 crop_nopad=False, ignore_index=255) -> Resize(crop_size) -> RandomGaussianBlur -> ToTensor (dataloaders.py).  This module
@@ -39,16 +44,36 @@ def _bicubic_vec(x: np.ndarray) -> np.ndarray:
     return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
 
 
+def _bilinear_vec(x: np.ndarray) -> np.ndarray:
+    x = np.abs(x)
+    return np.where(x < 1.0, 1.0 - x, 0.0)
+
+
+_FILTERS = {"bicubic": (_bicubic_vec, 2.0), "bilinear": (_bilinear_vec, 1.0)}
+
+
 @lru_cache(maxsize=256)
 def _bicubic_tables(in_size: int, out_size: int):
-    """Pillow precompute_coeffs(BICUBIC) + normalize_coeffs_8bpc -> (bounds int32 [out,2], coefs int32 [out,ksize]).
+    """Pillow precompute_coeffs(BICUBIC) + normalize_coeffs_8bpc -> (bounds int32 [out,2], coefs int32 [out,ksize])."""
+    return _resample_tables(in_size, out_size, "bicubic")
+
+
+@lru_cache(maxsize=256)
+def _bilinear_tables(in_size: int, out_size: int):
+    """Pillow precompute_coeffs(BILINEAR) + normalize_coeffs_8bpc: the image half of dataloaders.py:467-482 Resize."""
+    return _resample_tables(in_size, out_size, "bilinear")
+
+
+def _resample_tables(in_size: int, out_size: int, filt: str):
+    """Pillow precompute_coeffs + normalize_coeffs_8bpc for `filt` -> (bounds int32 [out,2], coefs int32 [out,ksize]).
     Vectorised over the destination index with the same IEEE double operations in the same order as Pillow's scalar loop
     (the weight sum is a sequential cumsum, not numpy's pairwise sum); checked entry by entry against the scalar
-    restatement in oracle/input_oracle.py (tests/test_input_cpu.py)."""
+    restatement in oracle/input_oracle.py::resample_tables (tests/test_input_cpu.py, tests/test_input_resize_cpu.py)."""
+    fn, sup = _FILTERS[filt]
     scale = filterscale = float(in_size) / out_size
     if filterscale < 1.0:
         filterscale = 1.0
-    support = 2.0 * filterscale
+    support = sup * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     ss = 1.0 / filterscale
     xx = np.arange(out_size, dtype=np.float64)
@@ -57,7 +82,7 @@ def _bicubic_tables(in_size: int, out_size: int):
     xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
     t = np.arange(ksize, dtype=np.float64)[None, :]
     live = np.arange(ksize)[None, :] < xmax[:, None]
-    w = np.where(live, _bicubic_vec((t + xmin[:, None] - center[:, None] + 0.5) * ss), 0.0)
+    w = np.where(live, fn((t + xmin[:, None] - center[:, None] + 0.5) * ss), 0.0)
     ww = np.cumsum(w, axis=1)[:, -1:]                                           # sequential adds, trailing zeros change nothing
     w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
     one = float(1 << PRECISION_BITS)
@@ -109,6 +134,109 @@ class Draw:
     blur: Optional[float]              # GaussianBlur radius when its gate fired
 
 
+def _draw_jitter(rng, np_rng, j) -> Optional[list]:
+    """ColorJitter's draws (dataloaders.py:655 gate; when it fires, get_params :622-643: four uniform factors from numpy's global
+    stream, then np.random.shuffle of the four transforms) -> [(op, factor), ...] in application order, or None."""
+    if rng.random() < 0.5:
+        ops = [("brightness", float(np_rng.uniform(max(0, 1 - j["brightness"]), 1 + j["brightness"]))),
+               ("contrast", float(np_rng.uniform(max(0, 1 - j["contrast"]), 1 + j["contrast"]))),
+               ("saturation", float(np_rng.uniform(max(0, 1 - j["saturation"]), 1 + j["saturation"]))),
+               ("hue", float(np_rng.uniform(-j["hue"], j["hue"])))]
+        np_rng.shuffle(ops)                                # consumes the stream as shuffling the four Lambdas does
+        return ops
+    return None
+
+
+def _draw_blur(rng) -> Optional[float]:
+    """RandomGaussianBlur (dataloaders.py:172-174): gate, then the radius."""
+    return rng.random() if rng.random() < 0.5 else None
+
+
+def _check_pair(name: str, img_u8: torch.Tensor, lab_u8: torch.Tensor):
+    if not (img_u8.is_cuda and lab_u8.is_cuda and img_u8.dtype == torch.uint8 and lab_u8.dtype == torch.uint8):
+        raise _lib.MrfpHipError("%s: uint8 CUDA tensors expected (there is no CPU path)" % name)
+    H, W, C = img_u8.shape
+    if C != 3 or tuple(lab_u8.shape) != (H, W):
+        raise _lib.MrfpHipError("%s: image [H,W,3] and label [H,W] expected" % name)
+    return H, W, img_u8.contiguous(), lab_u8.contiguous()
+
+
+def _jitter(cur: torch.Tensor, jitter) -> torch.Tensor:
+    """ColorJitter on the original-size image (per-pixel: commutes with the flip)."""
+    if not jitter:
+        return cur
+    npix = cur.shape[0] * cur.shape[1]
+    ws = torch.empty(16, dtype=torch.uint8, device=cur.device)
+    for op, factor in jitter:
+        nxt = torch.empty_like(cur)
+        shift = int(factor * 255) & 255 if op == "hue" else 0
+        call("mrfp_jitter_u8", ptr(cur), ptr(nxt), npix, _JITTER_OPS[op], float(factor), shift, ptr(ws), stream())
+        cur = nxt
+    return cur
+
+
+def _resample(cur: torch.Tensor, H: int, W: int, sh: int, sw: int, xtab, ytab, flip: bool) -> torch.Tensor:
+    """img.resize((sw, sh)) of the (unflipped) uint8 [H,W,3] image, mirrored when `flip`: xtab / ytab = (bounds, coefs, ksize)."""
+    dev = cur.device
+    if sw != W or flip:         # horizontal pass first (Pillow ImagingResample), reading the source mirrored when flipped
+        # (at sw == W the coefficients are exactly (0, 1, 0): the pass is then a plain mirrored copy)
+        bx, kx, ksx = xtab
+        tmp = torch.empty((H, sw, 3), dtype=torch.uint8, device=dev)
+        call("mrfp_resample_u8", ptr(cur), ptr(tmp), H, W, H, sw, 3, ptr(bx), ptr(kx), ksx, 0, int(flip), stream())
+        cur = tmp
+    if sh != H:
+        by, ky, ksy = ytab
+        tmp = torch.empty((sh, sw, 3), dtype=torch.uint8, device=dev)
+        call("mrfp_resample_u8", ptr(cur), ptr(tmp), H, sw, sh, sw, 3, ptr(by), ptr(ky), ksy, 1, 0, stream())
+        cur = tmp
+    return cur
+
+
+def _out_slot(t: Optional[torch.Tensor], shape, dtype, dev, what: str) -> torch.Tensor:
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if not (t.is_cuda and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
+        raise _lib.MrfpHipError("%s: contiguous %s CUDA tensor of shape %s expected, got %s %s" % (what, dtype, tuple(shape), t.dtype,
+                                                                                                tuple(t.shape)))
+    return t
+
+
+def _assemble(cur: torch.Tensor, lab_u8: torch.Tensor, ty, tx, sh: int, sw: int, d: "Draw", Hc: int, Wc: int, ignore: int,
+              out_img: Optional[torch.Tensor], out_lab: Optional[torch.Tensor]):
+    """Pad + crop + (RandomGaussianBlur) + ToTensor of the scaled image `cur` [sh,sw,3]; the label is read from the ORIGINAL map
+    through Pillow's nearest-neighbour tables ty [sh], tx [sw] (mirrored when d.flip) -> (float32 [3,Hc,Wc], int64 [Hc,Wc])."""
+    H, W = lab_u8.shape
+    dev = cur.device
+    out_img = _out_slot(out_img, (3, Hc, Wc), torch.float32, dev, "out_img")
+    out_lab = _out_slot(out_lab, (Hc, Wc), torch.int64, dev, "out_lab")
+    blur = d.blur is not None and d.blur != 0.0          # PIL returns a copy for radius 0
+    crop_u8 = torch.empty((Hc, Wc, 3), dtype=torch.uint8, device=dev) if blur else None
+    call("mrfp_input_assemble", ptr(cur), ptr(lab_u8), ptr(ty), ptr(tx), sh, sw, H, W, int(d.flip), d.pad[0], d.pad[1],
+         d.crop[0], d.crop[1], Hc, Wc, int(ignore), ptr(out_img), ptr(crop_u8), ptr(out_lab), stream())
+    if blur:                                              # RandomGaussianBlur (dataloaders.py:168-177), then ToTensor
+        ww, fw = _blur_weights(d.blur)
+        a, b = crop_u8, torch.empty_like(crop_u8)
+        for vertical in (0, 0, 0, 1, 1, 1):               # ImagingBoxBlur: three passes along x, then three along y
+            call("mrfp_box_blur3_u8", ptr(a), ptr(b), Hc, Wc, 3, ww, fw, vertical, stream())
+            a, b = b, a
+        call("mrfp_u8hwc_to_f32chw", ptr(a), ptr(out_img), Hc, Wc, stream())
+    return out_img, out_lab
+
+
+def _cached(cache: dict, key, build):
+    t = cache.get(key)
+    if t is None:
+        t = build()
+        if len(cache) > 64:
+            cache.clear()
+        cache[key] = t
+    return t
+
+
+def _dev(dev, *arrays):
+    return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrays)
+
+
 class TrainTransform:
     """transform_tr of the reference (main.py:409-419) on the device."""
 
@@ -123,15 +251,7 @@ class TrainTransform:
         when the ColorJitter gate fires, numpy's global stream as get_params does (:622-643: four uniform factors, then
         np.random.shuffle of the four transforms)."""
         flip = rng.random() < 0.5
-        jitter = None
-        if rng.random() < 0.5:
-            j = self.JITTER
-            ops = [("brightness", float(np_rng.uniform(max(0, 1 - j["brightness"]), 1 + j["brightness"]))),
-                   ("contrast", float(np_rng.uniform(max(0, 1 - j["contrast"]), 1 + j["contrast"]))),
-                   ("saturation", float(np_rng.uniform(max(0, 1 - j["saturation"]), 1 + j["saturation"]))),
-                   ("hue", float(np_rng.uniform(-j["hue"], j["hue"])))]
-            np_rng.shuffle(ops)                            # consumes the stream as shuffling the four Lambdas does
-            jitter = ops
+        jitter = _draw_jitter(rng, np_rng, self.JITTER)
         scale_amt = 1.0 * rng.uniform(self.scale_min, self.scale_max)
         sw, sh = int(w * scale_amt), int(h * scale_amt)
         t = self.crop_size
@@ -143,7 +263,7 @@ class TrainTransform:
             W2, H2 = sw + 2 * pad_w, sh + 2 * pad_h
             x1 = 0 if W2 == t else rng.randint(0, W2 - t)
             y1 = 0 if H2 == t else rng.randint(0, H2 - t)
-        blur = rng.random() if rng.random() < 0.5 else None
+        blur = _draw_blur(rng)
         return Draw(flip, jitter, (sw, sh), (pad_w, pad_h), (x1, y1), blur)
 
     def _tables(self, dev, H, W, sh, sw):
@@ -162,45 +282,141 @@ class TrainTransform:
     def __call__(self, img_u8: torch.Tensor, lab_u8: torch.Tensor, d: Draw, out_img: Optional[torch.Tensor] = None,
                  out_lab: Optional[torch.Tensor] = None):
         """img_u8: uint8 [H,W,3], lab_u8: uint8 [H,W], both on the GPU -> (float32 [3,T,T], int64 [T,T])."""
-        if not (img_u8.is_cuda and lab_u8.is_cuda and img_u8.dtype == torch.uint8 and lab_u8.dtype == torch.uint8):
-            raise _lib.MrfpHipError("TrainTransform: uint8 CUDA tensors expected (there is no CPU path)")
-        H, W, C = img_u8.shape
-        if C != 3 or tuple(lab_u8.shape) != (H, W):
-            raise _lib.MrfpHipError("TrainTransform: image [H,W,3] and label [H,W] expected")
-        img_u8, lab_u8 = img_u8.contiguous(), lab_u8.contiguous()
-        dev, T = img_u8.device, self.crop_size
+        H, W, img_u8, lab_u8 = _check_pair("TrainTransform", img_u8, lab_u8)
         sw, sh = d.scaled
-        bx, kx, by, ky, tx, ty, ksx, ksy = self._tables(dev, H, W, sh, sw)
-        cur = img_u8
-        if d.jitter:                                       # ColorJitter on the original-size image (per-pixel: commutes with the flip)
-            ws = torch.empty(16, dtype=torch.uint8, device=dev)
-            for op, factor in d.jitter:
-                nxt = torch.empty_like(cur)
-                shift = int(factor * 255) & 255 if op == "hue" else 0
-                call("mrfp_jitter_u8", ptr(cur), ptr(nxt), H * W, _JITTER_OPS[op], float(factor), shift, ptr(ws), stream())
-                cur = nxt
-        if sw != W or d.flip:       # horizontal pass first (Pillow ImagingResample), reading the source mirrored when flipped
-            # (at sw == W the coefficients are exactly (0, 1, 0): the pass is then a plain mirrored copy)
-            tmp = torch.empty((H, sw, 3), dtype=torch.uint8, device=dev)
-            call("mrfp_resample_u8", ptr(cur), ptr(tmp), H, W, H, sw, 3, ptr(bx), ptr(kx), ksx, 0, int(d.flip), stream())
-            cur = tmp
-        if sh != H:
-            tmp = torch.empty((sh, sw, 3), dtype=torch.uint8, device=dev)
-            call("mrfp_resample_u8", ptr(cur), ptr(tmp), H, sw, sh, sw, 3, ptr(by), ptr(ky), ksy, 1, 0, stream())
-            cur = tmp
-        if out_img is None:
-            out_img = torch.empty((3, T, T), dtype=torch.float32, device=dev)
-        if out_lab is None:
-            out_lab = torch.empty((T, T), dtype=torch.int64, device=dev)
-        blur = d.blur is not None and d.blur != 0.0          # PIL returns a copy for radius 0
-        crop_u8 = torch.empty((T, T, 3), dtype=torch.uint8, device=dev) if blur else None
-        call("mrfp_input_assemble", ptr(cur), ptr(lab_u8), ptr(ty), ptr(tx), sh, sw, H, W, int(d.flip), d.pad[0], d.pad[1],
-             d.crop[0], d.crop[1], T, T, int(self.ignore_index), ptr(out_img), ptr(crop_u8), ptr(out_lab), stream())
-        if blur:                                              # RandomGaussianBlur (dataloaders.py:168-177), then ToTensor
-            ww, fw = _blur_weights(d.blur)
-            a, b = crop_u8, torch.empty_like(crop_u8)
-            for vertical in (0, 0, 0, 1, 1, 1):               # ImagingBoxBlur: three passes along x, then three along y
-                call("mrfp_box_blur3_u8", ptr(a), ptr(b), T, T, 3, ww, fw, vertical, stream())
-                a, b = b, a
-            call("mrfp_u8hwc_to_f32chw", ptr(a), ptr(out_img), T, T, stream())
-        return out_img, out_lab
+        bx, kx, by, ky, tx, ty, ksx, ksy = self._tables(img_u8.device, H, W, sh, sw)
+        cur = _jitter(img_u8, d.jitter)
+        cur = _resample(cur, H, W, sh, sw, (bx, kx, ksx), (by, ky, ksy), d.flip)
+        return _assemble(cur, lab_u8, ty, tx, sh, sw, d, self.crop_size, self.crop_size, self.ignore_index, out_img, out_lab)
+
+
+class ResizeTransform:
+    """The Resize composition of the reference (Foggy Cityscapes main.py:319-330, BDD100k :499-507, Synthia :592-603):
+    RandomHorizontalFlip -> ColorJitter -> Resize(size1, size2) -> RandomGaussianBlur -> ToTensor, on the device.
+    Resize (dataloaders.py:467-482) hands (size1, size2) to PIL as (width, height) (the `# (h, w)` comment there is wrong):
+    BILINEAR for the image, NEAREST for the label.  Output: float32 [3,size2,size1] (0..255) and int64 [size2,size1]."""
+
+    JITTER = TrainTransform.JITTER
+
+    def __init__(self, size1: int, size2: int):
+        self.size1, self.size2 = int(size1), int(size2)
+        self._dev_tables = {}
+
+    def draw(self, w: int, h: int, rng=_random, np_rng=np.random) -> Draw:
+        """python's `random`: flip, jitter gate, blur gate (+ radius); numpy's stream as ColorJitter.get_params when its gate
+        fires.  (w, h), the source size, draws nothing here: it is taken for the same signature as TrainTransform.draw."""
+        flip = rng.random() < 0.5
+        jitter = _draw_jitter(rng, np_rng, self.JITTER)
+        blur = _draw_blur(rng)
+        return Draw(flip, jitter, (self.size1, self.size2), (0, 0), (0, 0), blur)
+
+    def __call__(self, img_u8: torch.Tensor, lab_u8: torch.Tensor, d: Draw, out_img: Optional[torch.Tensor] = None,
+                 out_lab: Optional[torch.Tensor] = None):
+        """img_u8: uint8 [H,W,3], lab_u8: uint8 [H,W], both on the GPU -> (float32 [3,size2,size1], int64 [size2,size1]);
+        out_img / out_lab: slots to write into (e.g. one sample of a batch)."""
+        H, W, img_u8, lab_u8 = _check_pair("ResizeTransform", img_u8, lab_u8)
+        sw, sh = self.size1, self.size2
+        dev = img_u8.device
+        bx, kx, by, ky, tx, ty = _cached(self._dev_tables, (str(dev), H, W), lambda: _dev(
+            dev, *_bilinear_tables(W, sw), *_bilinear_tables(H, sh), _nearest_table(W, sw), _nearest_table(H, sh)))
+        cur = _jitter(img_u8, d.jitter)
+        cur = _resample(cur, H, W, sh, sw, (bx, kx, kx.shape[1]), (by, ky, ky.shape[1]), d.flip)
+        return _assemble(cur, lab_u8, ty, tx, sh, sw, Draw(d.flip, d.jitter, (sw, sh), (0, 0), (0, 0), d.blur), sh, sw, 255,
+                         out_img, out_lab)
+
+
+class CropTransform:
+    """The Crop composition of the reference (Mapillary, main.py:764-773): RandomHorizontalFlip -> ColorJitter ->
+    RandomCrop_p(base_size, crop_size) -> RandomGaussianBlur -> ToTensor, on the device.  RandomCrop_p (dataloaders.py:216-234)
+    crops `crop_size` wide and `base_size` tall at x0 = randint(0, w - crop_size), y0 = randint(0, h - base_size), drawn
+    unconditionally (an image smaller than the crop raises ValueError in draw(), as it does there).
+    Output: float32 [3,base_size,crop_size] (0..255) and int64 [base_size,crop_size]."""
+
+    JITTER = TrainTransform.JITTER
+
+    def __init__(self, base_size: int, crop_size: int):
+        self.base_size, self.crop_size = int(base_size), int(crop_size)
+        self._dev_tables = {}
+
+    def draw(self, w: int, h: int, rng=_random, np_rng=np.random) -> Draw:
+        """python's `random`: flip, jitter gate, randint x0, randint y0, blur gate (+ radius); numpy's stream as
+        ColorJitter.get_params when its gate fires."""
+        flip = rng.random() < 0.5
+        jitter = _draw_jitter(rng, np_rng, self.JITTER)
+        x0 = rng.randint(0, w - self.crop_size)
+        y0 = rng.randint(0, h - self.base_size)
+        blur = _draw_blur(rng)
+        return Draw(flip, jitter, (w, h), (0, 0), (x0, y0), blur)
+
+    def __call__(self, img_u8: torch.Tensor, lab_u8: torch.Tensor, d: Draw, out_img: Optional[torch.Tensor] = None,
+                 out_lab: Optional[torch.Tensor] = None):
+        """img_u8: uint8 [H,W,3], lab_u8: uint8 [H,W], both on the GPU -> (float32 [3,base_size,crop_size],
+        int64 [base_size,crop_size]); out_img / out_lab: slots to write into."""
+        H, W, img_u8, lab_u8 = _check_pair("CropTransform", img_u8, lab_u8)
+        x0, y0 = d.crop
+        if not (0 <= x0 <= W - self.crop_size and 0 <= y0 <= H - self.base_size):
+            raise _lib.MrfpHipError("CropTransform: a %dx%d crop at (%d, %d) leaves the %dx%d image" % (
+                self.crop_size, self.base_size, x0, y0, W, H))
+        dev = img_u8.device
+        # identity tables: the flip is a mirrored copy through the resampler (coefficients exactly (0, 1, 0)), the label is read
+        # through the identity nearest-neighbour tables, mirrored by the assemble kernel
+        bx, kx, tx, ty = _cached(self._dev_tables, (str(dev), H, W), lambda: _dev(
+            dev, *_bilinear_tables(W, W), _nearest_table(W, W), _nearest_table(H, H)))
+        cur = _jitter(img_u8, d.jitter)
+        cur = _resample(cur, H, W, H, W, (bx, kx, kx.shape[1]), None, d.flip)
+        return _assemble(cur, lab_u8, ty, tx, H, W, Draw(d.flip, d.jitter, (W, H), (0, 0), (x0, y0), d.blur), self.base_size,
+                         self.crop_size, 255, out_img, out_lab)
+
+
+# ---- frequency filters (dataloaders.py:24-79; csrc/freq.hip) --------------------------------------------------------------
+@lru_cache(maxsize=32)
+def _twiddles(n: int, device_str: str) -> torch.Tensor:
+    """exp(-2 pi i t/n), t < n, built in double, stored as float32 (re, im) pairs."""
+    t = np.arange(n, dtype=np.float64)
+    tab = np.stack([np.cos(2 * np.pi * t / n), -np.sin(2 * np.pi * t / n)], 1).astype(np.float32)
+    return torch.from_numpy(tab).to(device_str)
+
+
+def _freq_args(name: str, x, out):
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() in (3, 4) and x.shape[-3] == 3
+            and x.numel() > 0):
+        raise _lib.MrfpHipError("%s: a float32 CUDA tensor [3,H,W] or [B,3,H,W] expected, got %s" % (
+            name, "%s %s %s" % (x.dtype, tuple(x.shape), x.device) if isinstance(x, torch.Tensor) else type(x).__name__))
+    x = x.contiguous()
+    B = 1 if x.dim() == 3 else x.shape[0]
+    H, W = x.shape[-2], x.shape[-1]
+    out = _out_slot(out, tuple(x.shape), torch.float32, x.device, name + ": out")
+    dev = str(x.device)
+    return x, out, B, H, W, _twiddles(H, dev), _twiddles(W, dev)
+
+
+def _band(name: str, x, radius: float, out, high: bool):
+    x, out, B, H, W, twH, twW = _freq_args(name, x, out)
+    nb = int(_lib.lib().mrfp_band_filter_ws_bytes(B, H, W, float(radius)))
+    if nb < 0:
+        raise _lib.MrfpHipError("%s: radius %r on %dx%d images is not supported (0 <= radius < 33, H, W < 65536)" % (name, radius, H, W))
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    call("mrfp_band_filter", ptr(x), ptr(out), ptr(ws), ptr(twH), ptr(twW), B, H, W, float(radius), int(high), stream())
+    return out
+
+
+def hpf(x: torch.Tensor, radius: float = 16.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """HPF (dataloaders.py:24-45) on the ToTensor layout: x - Re(IDFT2(F * [fy^2 + fx^2 <= radius^2])) per channel plane.
+    x: float32 CUDA [3,H,W] or [B,3,H,W] (any H, W) -> the same shape."""
+    return _band("hpf", x, radius, out, True)
+
+
+def lpf(x: torch.Tensor, radius: float = 16.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LPF (dataloaders.py:59-79): Re(IDFT2(F * [fy^2 + fx^2 < radius^2])) per channel plane (strict: the bins at distance
+    exactly `radius` are removed by both filters, so hpf + lpf != x)."""
+    return _band("lpf", x, radius, out, False)
+
+
+def phot(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PHOT (dataloaders.py:47-57): Re(ifftn(F / |F|)) * 5 * 255 over the 3-D (H,W,3) spectrum.  H and W of the form
+    2^a 3^b 5^c, <= 4096.  A zero bin gives NaN everywhere, as numpy does: a grey image (R = G = B) returns all NaN."""
+    x, out, B, H, W, twH, twW = _freq_args("phot", x, out)
+    nb = int(_lib.lib().mrfp_phot_ws_bytes(B, H, W))
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    call("mrfp_phot", ptr(x), ptr(out), ptr(ws), ptr(twH), ptr(twW), B, H, W, stream())
+    return out
