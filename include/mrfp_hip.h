@@ -255,28 +255,30 @@ int mrfp_conv_fwd(const void* x, const void* wpack, const float* bias, void* y, 
                   int64_t Ho, int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil,
                   int64_t sstride, const void* addend, float* colstats, void* stream);
 /* colstats (optional): the epilogue also writes per-channel partial sums of the STORED output,
- * float [nblk][2][ldy] (sum, sum of squares per row block), nblk = mrfp_conv_stats_blocks(...): the
- * BatchNorm statistics pass over the conv output disappears (feed it to mrfp_bn_finalize with B = 1,
- * nslab = nblk, count = B*Ho*Wo). */
-int64_t mrfp_conv_stats_blocks(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t R, int64_t S, int64_t Ho,
-                               int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t sstride);
-/* rows of the [M][N] output one of those row blocks covers (block r = rows [r * rb, (r + 1) * rb)): when rb divides Ho*Wo no block
- * straddles an image and the blocks of image b are the per-image partial sums nn.InstanceNorm2d needs (reference Resnet.py:176-178,
- * 534-536: InstanceNorm after the stem convolutions) -- feed them to mrfp_in_finalize with nslab = Ho*Wo / rb. */
+ * float [nblk][2][ldy] (sum, sum of squares per row block): the BatchNorm statistics pass over the conv output
+ * disappears.  mrfp_conv_stats_layout describes that buffer for the launch with the same arguments (a statistics buffer, no
+ * bias, no addend; wstats = 1: mrfp_conv_fwd_wstats, sstride = 1) -- the kernel the launch runs on (tile shape, the pointwise
+ * kernels, the row-reuse and 64/128-channel 3x3 kernels), and with it the row blocks, depends on all of them.  It writes
+ *   out[0] row_blocks   nblk, the row blocks the epilogue writes
+ *   out[1] block_rows   rows of the [M][N] output one of them covers (block r = rows [r * rb, (r + 1) * rb)): when rb divides
+ *                       Ho*Wo no block straddles an image and the blocks of image b are the per-image partial sums
+ *                       nn.InstanceNorm2d needs (reference Resnet.py:176-178, 534-536: InstanceNorm after the stem convolutions) --
+ *                       feed them to mrfp_in_finalize with nslab = Ho*Wo / rb.  NEGATIVE for the weight-stationary 3x3 kernel:
+ *                       its rows are per image, -rb of them each.
+ *   out[2] alloc_rows   rows of 2*ldy floats colstats must hold: large launches fold their row blocks into 64 groups appended
+ *                       behind them
+ *   out[3] final_first, out[4] final_count: the rows to hand to mrfp_bn_finalize (B = 1, nslab = final_count, count = B*Ho*Wo). */
+int mrfp_conv_stats_layout(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S,
+                           int64_t Ho, int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t sstride, int wstats,
+                           int64_t* out);
+/* out[1] of mrfp_conv_stats_layout for mrfp_conv_fwd with ldy = N and wstats = 0 (0 on bad geometry). */
 int64_t mrfp_conv_stats_block_rows(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t R, int64_t S, int64_t Ho,
                                    int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t sstride);
-/* takes the geometry arguments of the mrfp_conv_fwd call it describes: the kernel the launch runs on (tile shape, the pointwise
- * kernels, the row-reuse 3x3 kernels) -- and with it the number of row blocks -- depends on all of them. */
 /* The K-loop gathers through 32-bit buffer-descriptor offsets, so one launch reads at most 3.75 GB of input; a larger
  * activation (BASELINE.json configs[4] at 16 images per GPU: 16 x 256 x 512 x 1024 bf16 = 4.3 GB) is walked in batch ranges
  * by mrfp_conv_fwd / mrfp_conv_wgrad themselves (one image must stay below the limit).  Returns 1 when B images of
  * image_bytes = H*W*C*sizeof(dtype) run as ONE launch -- only then are the fused per-row-block statistics available. */
 int mrfp_conv_single_launch(int64_t B, int64_t image_bytes);
-/* colstats must hold mrfp_conv_stats_rows(nblk) rows of 2*ldy floats; large launches fold their row blocks into
- * 64 groups appended behind them: hand rows [final_first, final_first + final_count) to mrfp_bn_finalize. */
-int64_t mrfp_conv_stats_rows(int64_t nblk);
-int64_t mrfp_conv_stats_final_first(int64_t nblk);
-int64_t mrfp_conv_stats_final_count(int64_t nblk);
 /* mrfp_conv_fwd whose fused statistics count output row m (pixel b, oh, ow) `rowweight[m]` times: the statistics of the
  * nearest-neighbour RESIZED output (rowweight = the pixel's multiplicity in the resize, 0..255) -- the HRFP stages
  * conv -> F.interpolate(nearest) -> BatchNorm(train) (reference deepv3.py:320-327) without a statistics pass over the

@@ -7,8 +7,9 @@ step, HRFP re-initialisation, load_state_dict).
 """
 from __future__ import annotations
 
+import ctypes
 import weakref
-from typing import Optional
+from typing import Any, NamedTuple, Optional
 
 import torch
 
@@ -19,6 +20,19 @@ from .ops import CL, GRAD_DEFERRED, _chk, empty_cl, grad_sink, notify_grad, zero
 _PACKS = {}      # id(weight Parameter) -> {key: _Pack}; entry dropped when the Parameter dies
 import os as _os
 FUSE_STATS = [_os.environ.get("MRFP_FUSE_STATS", "1") != "0"]   # conv epilogues emit BatchNorm partial statistics for bias-free convolutions
+
+
+class ConvStats(NamedTuple):
+    """The statistics a convolution's epilogue wrote (y._mrfp_colstats; layout: mrfp_conv_stats_layout)."""
+    final: torch.Tensor        # the rows to hand to a BatchNorm finalize (compacted for large launches)
+    final_count: int           # ... their count
+    elements: int              # the element count per channel they sum over
+    rows: torch.Tensor         # the RAW per-row-block rows (an InstanceNorm consumer needs them per image: ops._in_plane_sums)
+    row_blocks: int            # ... their count
+    block_rows: int            # output rows of one row block; < 0: -(rows per image); 0: resize-weighted, no per-image use
+    resize_plan: Any           # the ops.NearestPlan the statistics are weighted for (STAT_RESIZE: its one consumer), or None
+
+
 _LAST_STATS = [None]  # handed from _Conv2d.forward to conv2d() (autograd re-wraps the output tensor object)
 # set by a caller right before a convolution whose output goes through a nearest-neighbour resize into a training-mode BatchNorm
 # (deepv3.MRFPPlus._hrfp): the ops.NearestPlan of that resize.  The epilogue statistics then count every output pixel as often as
@@ -460,8 +474,13 @@ class _Conv2d(torch.autograd.Function):
             wtab = plan.multiplicity(B)          # statistics of the nearest-resized output (see STAT_RESIZE)
         if wtab is not None or (bias is None and FUSE_STATS[0] and single):
             # no bias = a convolution that feeds a normalisation layer: let the epilogue produce its statistics
-            nblk = int(L.mrfp_conv_stats_blocks(dt(x), B, H, W, Cphys, Nphys, R, S, Ho, Wo, stride, pad_h, pad_w, dil, 1))
-            stats = torch.empty(int(L.mrfp_conv_stats_rows(nblk)) * 2 * Nphys, dtype=torch.float32, device=x.device)
+            lay = (ctypes.c_int64 * 5)()
+            rc = L.mrfp_conv_stats_layout(dt(x), B, H, W, Cphys, Nphys, Nphys, R, S, Ho, Wo, stride, pad_h, pad_w, dil, 1,
+                                          int(wtab is not None), lay)
+            if rc != 0:
+                raise _lib.MrfpHipError("mrfp_conv_stats_layout failed (%d): %s" % (rc, L.mrfp_last_error().decode()))
+            nblk, rb, rows, first, cnt = lay
+            stats = torch.empty(rows * 2 * Nphys, dtype=torch.float32, device=x.device)
         _lib.NOTE[0] = (C, N)
         if wtab is not None:
             call("mrfp_conv_fwd_wstats", ptr(x), ptr(pk.wf), ptr(pk.bias), ptr(y), dt(x), B, H, W, Cphys, Nphys, Nphys, R, S,
@@ -471,16 +490,12 @@ class _Conv2d(torch.autograd.Function):
             call("mrfp_conv_fwd", ptr(x), ptr(pk.wf), ptr(pk.bias), ptr(y), dt(x), B, H, W, Cphys, Nphys, Nphys, R, S,
                  Ho, Wo, stride, pad_h, pad_w, dil, 1, None, ptr(stats), stream())
         if stats is not None:      # the rows the BatchNorm finalize should read (compacted for large launches)
-            first, cnt = int(L.mrfp_conv_stats_final_first(nblk)), int(L.mrfp_conv_stats_final_count(nblk))
             final = stats[first * 2 * Nphys:(first + cnt) * 2 * Nphys]
             if wtab is not None:
                 # (element count = that of the RESIZED tensor; no per-image use; the plan identifies the one consumer they serve)
-                _LAST_STATS[0] = (final, cnt, B * plan.Ho * plan.Wo, stats, nblk, 0, plan)
+                _LAST_STATS[0] = ConvStats(final, cnt, B * plan.Ho * plan.Wo, stats, nblk, 0, plan)
             else:
-                # (rows to hand to a BatchNorm finalize, their count, the element count; + the RAW per-row-block rows and their count:
-                #  an InstanceNorm consumer needs them per image -- ops._InstanceNormAct)
-                rb = int(L.mrfp_conv_stats_block_rows(dt(x), B, H, W, Cphys, Nphys, R, S, Ho, Wo, stride, pad_h, pad_w, dil, 1))
-                _LAST_STATS[0] = (final, cnt, B * Ho * Wo, stats, nblk, rb)
+                _LAST_STATS[0] = ConvStats(final, cnt, B * Ho * Wo, stats, nblk, rb, None)
         else:
             _LAST_STATS[0] = None
         ctx.save_for_backward(x, weight, bias)

@@ -135,6 +135,14 @@ __host__ __device__ inline Lanes make_lanes(int C, int VEC) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// A run-time switch (MRFP_*: A/B runs, tests): the integer value of the environment variable `name`, `dflt` where it is unset.
+// Callers keep it in a function-local `static const`, so every switch is read once per process (the tests that flip one run a
+// child process).
+inline int env_switch(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
 // choose the vector width for a channel count: full 16-byte vectors when C allows it
 template <typename T> inline int pick_vec(int64_t C) {
     const int full = FullVec<T>::value;
@@ -145,12 +153,8 @@ inline int lines_per_image(int64_t B, int64_t Ho) {
     // ~1024 workgroups over the chip (4 per CU, 16 waves/CU, 4 independent 16-byte loads per lane in the
     // statistics kernels): enough bytes in flight to cover HBM latency, few enough partial sums that the
     // finalize kernels stay in the microseconds.
-    static int total = 0;
-    if (total == 0) {
-        const char* e = getenv("MRFP_ROW_BLOCKS");
-        total = e ? atoi(e) : 2048;
-        if (total < 64) total = 2048;
-    }
+    static const int set = env_switch("MRFP_ROW_BLOCKS", 2048);
+    const int total = set < 64 ? 2048 : set;
     int64_t cap = total / (B > 0 ? B : 1);
     if (cap < 1) cap = 1;
     if (Ho <= cap) return (int)Ho;

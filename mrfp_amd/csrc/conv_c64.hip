@@ -286,20 +286,15 @@ __global__ __launch_bounds__(256, (CB == 1 ? 2 : 1)) void conv3x3_c64_kernel(C64
     }
 }
 
-static int g_c64 = -1;
-bool c64_applicable(const ConvP& p, int esz) {
-    if (g_c64 < 0) {
-        const char* e = getenv("MRFP_CONV_C64");
-        g_c64 = e ? atoi(e) : 1;
-    }
-    if (!g_c64 || esz != 2) return false;
+static bool c64_applicable(const ConvP& p, int esz) {
+    static const int on = env_switch("MRFP_CONV_C64", 1);
+    if (!on || esz != 2) return false;
     if (p.R != 3 || p.S != 3 || p.stride != 1 || p.sstride != 1 || p.Ho != p.H || p.Wo != p.W) return false;
     if (p.dil < 1 || p.dil > 2 || p.pad_h != p.dil || p.pad_w != p.dil) return false;
     if ((p.ldy & 7) != 0) return false;
     if (p.C == 64) { if (p.N != 64 && p.N != 128) return false; }
     else if (p.C == 128) {        // MRFP_CONV_C128=0: the 128-channel layers stay on the implicit-GEMM tiles (A/B runs)
-        static int c128 = -1;
-        if (c128 < 0) { const char* e = getenv("MRFP_CONV_C128"); c128 = e ? atoi(e) : 1; }
+        static const int c128 = env_switch("MRFP_CONV_C128", 1);
         if (!c128 || (p.N != 64 && p.N != 128 && p.N != 256)) return false;
         // one workgroup per CU that first loads 288 registers of weights per wave: it pays from ~32 output row strips per workgroup on
         // (measured in the step: 128 -> 64 @256^2 188 -> 133 us, @192^2 105 -> 130 us; 128 -> 128 @96^2 52 -> 64 us).  MRFP_CONV_C128=2: always (tests)
@@ -310,21 +305,22 @@ bool c64_applicable(const ConvP& p, int esz) {
     if ((int64_t)p.M * p.ldy * esz >= (int64_t)kOOB || p.H < 2 * p.dil) return false;
     return true;
 }
-static int c64_grid(const ConvP& p) {
+bool c64_plan(const ConvP& p, int esz, ConvPlan& plan) {
+    if (!c64_applicable(p, esz)) return false;
     const int SW = p.N == 64 ? 128 : 64;
-    const int64_t units = (int64_t)p.B * ((p.W + SW - 1) / SW) * p.H;
+    const int64_t upi = (int64_t)((p.W + SW - 1) / SW) * p.H, units = upi * p.B;      // row strips per image, in all
     const int64_t cap = p.C == 64 ? kGrid2PerCU : kGrid1PerCU;     // two workgroups per CU (64 channels) / one (128: 512 registers per wave)
-    return (int)(units < cap ? units : cap);       // every workgroup owns at least one row strip
+    plan.kind = ConvKernel::c64;
+    plan.tile_rows = 0;
+    plan.grid = (int)(units < cap ? units : cap);   // every workgroup owns at least one row strip
+    // statistics row slots per image and pixel sub-strip: an upper bound of the workgroups whose span touches one image (spans are
+    // units / grid strips or one more long)
+    plan.spi = (int)(upi / (units / plan.grid) + 2);
+    const int64_t rows_per_image = (int64_t)(p.N == 64 ? 2 : 1) * plan.spi;
+    plan.stats_blocks = p.B * rows_per_image;
+    plan.stats_block_rows = -rows_per_image;
+    return true;
 }
-// statistics row slots per image and pixel sub-strip: an upper bound of the workgroups whose span touches one image
-static int c64_spi(const ConvP& p) {
-    const int SW = p.N == 64 ? 128 : 64;
-    const int64_t upi = (int64_t)((p.W + SW - 1) / SW) * p.H, units = upi * p.B;
-    const int64_t lmin = units / c64_grid(p);      // shortest span (>= 1)
-    return (int)(upi / lmin + 2);
-}
-int64_t c64_stats_blocks(const ConvP& p) { return (int64_t)p.B * (p.N == 64 ? 2 : 1) * c64_spi(p); }
-int64_t c64_stats_block_rows(const ConvP& p) { return -(int64_t)(p.N == 64 ? 2 : 1) * c64_spi(p); }   // < 0: -(rows per image)
 
 template <typename T, int CB, int NCG, bool STATS, bool ADD>
 static int c64_launch(const C64P& q, int grid, hipStream_t st) {
@@ -348,24 +344,21 @@ static int c64_pick(const ConvP& p, const C64P& q, int grid, hipStream_t st) {
 }
 
 template <typename T>
-static int c64_run_t(const ConvP& p, hipStream_t st) {
+static int c64_run_t(const ConvP& p, const ConvPlan& plan, hipStream_t st) {
     C64P q;
     q.x = p.x; q.w = p.w; q.y = p.y; q.bias = p.bias; q.addend = p.addend; q.colstats = p.colstats; q.rowweight = p.rowweight;
     q.B = p.B; q.H = p.H; q.W = p.W; q.N = p.N; q.ldy = p.ldy; q.dil = p.dil;
     const int SW = p.N == 64 ? 128 : 64;
     q.strips = (p.W + SW - 1) / SW;
     q.units = p.B * q.strips * p.H;
-    q.spi = c64_spi(p);
+    q.spi = plan.spi;          // (the statistics rows the caller sized from the same plan: mrfp_conv_stats_layout)
     q.xbytes = p.xbytes; q.wbytes = p.wbytes; q.ybytes = (unsigned)((int64_t)p.M * p.ldy * 2);
-    const int grid = c64_grid(p);
-    // the statistics rows the caller sized through c64_stats_blocks() hold spi slots per image and sub-strip: the longest run of
-    // workgroups whose spans touch one image must fit (spans are units / grid or one more long)
-    const int64_t upi = (int64_t)q.strips * p.H, lmin = q.units / grid;
-    MRFP_CHECK(grid >= 1 && lmin >= 1 && upi / lmin + 2 <= q.spi && (int64_t)p.B * (p.N == 64 ? 2 : 1) * q.spi == c64_stats_blocks(p),
-               "conv_c64: grid %d / %d statistics slots per image do not match the workspace rule", grid, q.spi);
+    const int grid = plan.grid;
     if (p.C == 64) return p.N == 64 ? c64_pick<T, 1, 2>(p, q, grid, st) : c64_pick<T, 1, 4>(p, q, grid, st);
     return p.N == 64 ? c64_pick<T, 2, 2>(p, q, grid, st) : c64_pick<T, 2, 4>(p, q, grid, st);
 }
-int c64_run(const ConvP& p, bool is_f16, hipStream_t st) { return is_f16 ? c64_run_t<f16>(p, st) : c64_run_t<bf16>(p, st); }
+int c64_run(const ConvP& p, const ConvPlan& plan, bool is_f16, hipStream_t st) {
+    return is_f16 ? c64_run_t<f16>(p, plan, st) : c64_run_t<bf16>(p, plan, st);
+}
 
 }  // namespace mrfp

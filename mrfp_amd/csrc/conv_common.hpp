@@ -23,9 +23,11 @@
 namespace mrfp {
 
 // Launch geometry of the PERSISTENT kernels (conv_c64.hip, conv_wg3.hip, conv_wg1.hip): their grids are "one round" of resident
-// workgroups, and the statistics / slab buffers their callers allocate (c64_spi, wg3_splits_bound, wg1_splits_bound,
-// mrfp_conv_wgrad*_ws_bytes) are sized FROM these grids -- every such rule derives from the two constants below, and each *_run checks
-// its chosen split / span count against the bound function before it launches (an error, never a write past a buffer sized elsewhere).
+// workgroups, and the statistics / slab buffers their callers allocate (the ConvPlan of conv_c64, wg3_splits_bound, wg1_splits_bound,
+// mrfp_conv_wgrad*_ws_bytes) are sized FROM these grids -- every such rule derives from the two constants below.  conv_c64 launches
+// the grid and statistics slots of the same plan its caller's workspace was sized from (conv_plan); the weight-gradient kernels plan
+// their splits separately from their bound functions, so wg3_run / wg1_run check the split they chose against the bound before they
+// launch (an error, never a write past a buffer sized elsewhere).
 //   (kCUs: common.hpp)
 constexpr int kGrid1PerCU = kCUs;               // one resident workgroup per CU (512-register waves: conv_c64 at 128 channels, conv_wg1)
 constexpr int kGrid2PerCU = 2 * kCUs;           // two per CU (conv_c64 at 64 channels, conv_wg3)
@@ -301,16 +303,25 @@ __device__ __forceinline__ uint4 gate_chunk16(const uint4& v, unsigned bits) {
 #define MRFP_EARLY_FULL 1      // bit 0: the 96x128 tile holds BOTH k steps of a K tile across the next fill, bit 1: the 128x128 tile too
 #endif
 
+// ---- launch plan of a forward / dgrad convolution (conv_igemm.hip: conv_plan) ------------------------------------------------
+// Host only: ConvP is the kernel argument, and its layout stays as it is.  The kernels in conv_plan's priority order: the pointwise
+// short-K kernels, the long-K pointwise kernel, the 64/128-channel 3x3 kernel, the row-reuse kernels (384 x 64, 192 x 128), then the
+// generic tiles (256 x 64 for N <= 64, 192 x 128, 96 x 128, 128 x 128).
+enum class ConvKernel { pw, pwk, c64, rr384, rr192, t256x64, t192x128, t96x128, t128x128 };
+struct ConvPlan {
+    ConvKernel kind;
+    int tile_rows;              // output rows of one tile (0: conv_c64, which walks row strips)
+    int64_t stats_blocks;       // statistics row blocks the epilogue writes
+    int64_t stats_block_rows;   // output rows one of them covers; NEGATIVE for conv_c64: -(statistics rows per image)
+    int grid, spi;              // conv_c64: persistent grid, statistics slots per image and pixel sub-strip
+};
+
 // ---- pointwise (1x1, stride 1) short-K kernels, conv_pw.hip ----------------------------------------------------------------
-bool pw_applicable(const ConvP& p, int esz);          // does run_igemm hand this launch to conv_pw.hip?
-int64_t pw_stats_blocks(const ConvP& p);              // statistics row blocks such a launch writes
-int64_t pw_stats_block_rows(const ConvP& p);          // output rows one of them covers
+bool pw_plan(const ConvP& p, int esz, ConvPlan& plan);        // false: not a launch for this kernel (plan untouched)
 int pw_run(const ConvP& p, bool is_f16, hipStream_t st);
 
 // ---- weight-stationary kernel for the long-K pointwise layers (K = 512 / 1024 / 1280), conv_pwk.hip -------------------------------
-bool pwk_applicable(const ConvP& p, int esz);
-int64_t pwk_stats_blocks(const ConvP& p);
-int64_t pwk_stats_block_rows(const ConvP& p);
+bool pwk_plan(const ConvP& p, int esz, ConvPlan& plan);
 int pwk_run(const ConvP& p, bool is_f16, hipStream_t st);
 
 // ---- weight-stationary 3x3 kernel for the 64-input-channel layers (HRFP ends, stem / layer-1 3x3), conv_c64.hip ---------------
@@ -329,9 +340,7 @@ bool wg1_applicable(int dtype_size, int64_t B, int64_t H, int64_t W, int64_t C, 
 int wg1_run(const void* const* xs, const void* const* dys, int64_t count, float* slab, bool is_f16, int64_t M, int64_t C, int64_t N, int64_t ldn,
             unsigned xbytes, unsigned dybytes, int* splits, hipStream_t st);
 
-bool c64_applicable(const ConvP& p, int esz);
-int64_t c64_stats_blocks(const ConvP& p);             // statistics rows such a launch writes: [image][sub-strip][slot]
-int64_t c64_stats_block_rows(const ConvP& p);         // NEGATIVE: -(rows per image) -- the rows are per image, not per fixed row count
-int c64_run(const ConvP& p, bool is_f16, hipStream_t st);
+bool c64_plan(const ConvP& p, int esz, ConvPlan& plan);      // statistics rows: [image][sub-strip][slot], per image (not per row count)
+int c64_run(const ConvP& p, const ConvPlan& plan, bool is_f16, hipStream_t st);
 
 }  // namespace mrfp

@@ -25,22 +25,13 @@
 #include "conv_common.hpp"
 #include <type_traits>
 
-// MRFP_WREG (build switch, default 0; round 6 experiment, profiles/r06_experiments.md): the WEIGHT fragments of the 16-bit ALIGNED
-// kernels go global -> registers (one buffer_load_dwordx4 per 16x32 fragment, issued where the K tile's LDS-DMA is issued) instead of
-// global -> LDS -> registers: the activation tile alone passes through LDS, so the LDS-DMA landing traffic and the ds_read_b128 count
-// of a K tile both drop by BN / (BM + BN) (tools/fill_micro.hip: fragment reads beside the DMA halve the DMA's rate).
-// bit 0: the plain single-buffer loop, bit 1: the row-reuse loop.
-#ifndef MRFP_WREG
-#define MRFP_WREG 0
-#endif
-
 namespace mrfp {
 
 MRFP_STAMP_DECL(g_stamps_igemm)
 int stamps_igemm(unsigned long long* out, int n) { return MRFP_STAMP_READ(g_stamps_igemm, out, n); }
 
 template <typename T, int WM, int WN, bool ALIGNED, bool STRIDED, int TM, int TN, bool RR = false>
-__global__ __launch_bounds__(64 * WM * WN, (((RR || ((MRFP_WREG & 1) && ALIGNED && sizeof(T) == 2)) && TM * TN >= 6) ? 2 : 3)) void conv_igemm_kernel(ConvP p) {   // 2nd = waves per SIMD
+__global__ __launch_bounds__(64 * WM * WN, ((RR && TM * TN >= 6) ? 2 : 3)) void conv_igemm_kernel(ConvP p) {   // 2nd = waves per SIMD
     constexpr int NT = 64 * WM * WN, BM = 32 * TM * WM, BN = 32 * TN * WN;
     constexpr int SA = BM * 8 / NT, SB = BN * 8 / NT, RSTEP = NT / 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -130,18 +121,7 @@ __global__ __launch_bounds__(64 * WM * WN, (((RR || ((MRFP_WREG & 1) && ALIGNED 
 
     typedef __attribute__((address_space(3))) void lds_void;
     constexpr bool M16 = kM16 && sizeof(T) == 2;
-    constexpr bool WREG = (MRFP_WREG & 1) && M16 && ALIGNED && !RR;      // weight fragments through registers (plain loop)
     const int l15 = lane & 15, lq = lane >> 4;
-    // WREG: byte offset of weight row n = (this wave's column block j) * 16 + l15 in the pack, + this lane quarter's chunk
-    unsigned wq_base[2 * TN];
-    uint4 fbn[2][2 * TN];          // the NEXT K tile's weight fragments [k step][column block], in flight beside its LDS-DMA
-    if constexpr (WREG) {
-#pragma unroll
-        for (int j = 0; j < 2 * TN; ++j) {
-            const int n = n0 + wn * 32 * TN + j * 16 + l15;
-            wq_base[j] = n < p.N ? (unsigned)n * (unsigned)p.kchunks * 16u + (unsigned)lq * 16u : kOOB;
-        }
-    }
     auto load_tile = [&](int kt) {
         const int dh = tr * p.dil, dw = ts * p.dil;
         const int cc = ALIGNED ? tc * 8 + chunk : tc;
@@ -167,20 +147,10 @@ __global__ __launch_bounds__(64 * WM * WN, (((RR || ((MRFP_WREG & 1) && ALIGNED 
         const unsigned qoff = !qok ? kOOB
                               : ALIGNED ? (unsigned)((tr * p.S + ts) * p.cpr + tc * 8 + chunk) * 16u
                                         : (unsigned)(kt * 8 + chunk) * 16u;
-        if constexpr (WREG) {
-            // (ALIGNED) the K tile's 8 chunks of weight row n start at chunk (tap * cpr + tc * 8); lane quarter lq takes chunk 4 kk + lq
-            const unsigned t0 = (unsigned)((tr * p.S + ts) * p.cpr + tc * 8) * 16u;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int j = 0; j < 2 * TN; ++j)
-                    fbn[kk][j] = bload(wr, wq_base[j] >= kOOB ? kOOB : wq_base[j] + t0 + (unsigned)(kk * 64));
-        } else {
 #pragma unroll
         for (int i = 0; i < SB; ++i) {
             const unsigned voff = (b_base[i] >= kOOB || !qok) ? kOOB : b_base[i] + qoff;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_void*)(sB0 + (wrow + i * RSTEP) * 128), 16, (int)voff, 0, 0, 0);
-        }
         }
         // advance to the next K tile.  ALIGNED: channel chunk OUTER, filter tap INNER -- the R*S taps of one 64-channel
         // slab re-read (shifted) the same input pixels back to back, so 8 of 9 reads of a 3x3 convolution are served
@@ -219,7 +189,6 @@ __global__ __launch_bounds__(64 * WM * WN, (((RR || ((MRFP_WREG & 1) && ALIGNED 
 
     const int nkt = classed ? ((p.R - tr0 + 1) >> 1) * ((p.S - ts0 + 1) >> 1) * (p.cpr >> 3) : (p.kchunks + 7) >> 3;
     const int lr = lane & 31, lh = lane >> 5;
-    uint4 fbc[2][2 * TN];          // WREG: the CURRENT K tile's weight fragments
     auto compute = [&](int kk0 = 0, int kk1 = 2) {
         const char* a = sA0;
         const char* b = sB0;
@@ -231,10 +200,7 @@ __global__ __launch_bounds__(64 * WM * WN, (((RR || ((MRFP_WREG & 1) && ALIGNED 
 #pragma unroll
                 for (int i = 0; i < 2 * TM; ++i) fa[i] = *reinterpret_cast<const uint4*>(a + lds_off(wm * 32 * TM + i * 16 + l15, ch));
 #pragma unroll
-                for (int j = 0; j < 2 * TN; ++j) {
-                    if constexpr (WREG) fb[j] = fbc[kk][j];
-                    else fb[j] = *reinterpret_cast<const uint4*>(b + lds_off(wn * 32 * TN + j * 16 + l15, ch));
-                }
+                for (int j = 0; j < 2 * TN; ++j) fb[j] = *reinterpret_cast<const uint4*>(b + lds_off(wn * 32 * TN + j * 16 + l15, ch));
 #pragma unroll
                 for (int i = 0; i < 2 * TM; ++i)
 #pragma unroll
@@ -379,13 +345,6 @@ __global__ __launch_bounds__(64 * WM * WN, (((RR || ((MRFP_WREG & 1) && ALIGNED 
                 // the barrier (`s_waitcnt vmcnt(5); s_barrier; s_waitcnt vmcnt(0); ds_read` in the ISA) -- a wave would pass the
                 // barrier with its pieces still in flight and the others would read stale LDS
                 dma_wait<0>();
-                if constexpr (WREG) {
-                    // (vmcnt(0) above covers the register loads too) next -> current: the loads of tile kt + 1 below get fresh registers
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                        for (int j = 0; j < 2 * TN; ++j) { fbc[kk][j] = fbn[kk][j]; settle(fbc[kk][j]); }
-                }
                 __syncthreads();      // barrier: tile kt has landed everywhere
                 if constexpr (HOLD == 1) compute(0, 1);
 #pragma unroll
@@ -394,10 +353,7 @@ __global__ __launch_bounds__(64 * WM * WN, (((RR || ((MRFP_WREG & 1) && ALIGNED 
 #pragma unroll
                     for (int i = 0; i < 2 * TM; ++i) fa[h][i] = *reinterpret_cast<const uint4*>(sA0 + lds_off(wm * 32 * TM + i * 16 + l15, ch));
 #pragma unroll
-                    for (int j = 0; j < 2 * TN; ++j) {
-                        if constexpr (WREG) fb[h][j] = fbc[2 - HOLD + h][j];
-                        else fb[h][j] = *reinterpret_cast<const uint4*>(sB0 + lds_off(wn * 32 * TN + j * 16 + l15, ch));
-                    }
+                    for (int j = 0; j < 2 * TN; ++j) fb[h][j] = *reinterpret_cast<const uint4*>(sB0 + lds_off(wn * 32 * TN + j * 16 + l15, ch));
                 }
                 __syncthreads();      // lgkmcnt(0) + barrier: every wave holds its last fragments, the buffer is free
                 if (kt + 1 < nkt) load_tile(kt + 1);
@@ -691,14 +647,10 @@ static int pick_igemm(const ConvP& p, hipStream_t st) {
 // 96x128 tile (4 waves x 96x32): same K loop, 3/4 of the rows.  Chosen when the 128-row tiling leaves the last
 // round of workgroups (3 per CU x 256 CUs) mostly empty: M = 36 864 (16 x 48 x 48), N = 256 is 576 tiles = 0.75 rounds
 // at 128 rows but exactly one full round (768) at 96 rows.
-static int g_t96 = -1;
 static bool use_tile96(const ConvP& p, int esz) {
-    if (g_t96 < 0) {
-        const char* e = getenv("MRFP_CONV_T96");
-        g_t96 = e ? atoi(e) : 1;
-    }
-    if (!g_t96 || p.N <= 64) return false;
-    if (g_t96 == 2) return true;      // A/B measurements: 96-row tile wherever it is legal
+    static const int mode = env_switch("MRFP_CONV_T96", 1);
+    if (!mode || p.N <= 64) return false;
+    if (mode == 2) return true;       // A/B measurements: 96-row tile wherever it is legal
     // strided dgrads (a stride-2 forward's input gradient): the 128x128 tile won all three layers of the bench step by 8-13 %
     // (tools/tile_sweep.sh, round 3)
     if (p.sstride > 1) return false;
@@ -716,14 +668,10 @@ static bool use_tile96(const ConvP& p, int esz) {
 }
 // 192x128 tile (4 waves x 96x64): 77 FLOP per LDS-fill byte instead of 64 and 0.83 KiB of fragment reads per MFMA instead
 // of 1; for long-K layers with many rounds of tiles
-static int g_t192 = -1;
 static bool use_tile192(const ConvP& p, int esz) {
-    if (g_t192 < 0) {
-        const char* e = getenv("MRFP_CONV_T192");      // =0: A/B measurements (measured +4..5 % on the long-K layers)
-        g_t192 = e ? atoi(e) : 1;
-    }
-    if (!g_t192 || esz != 2 || p.N <= 64) return false;
-    if (g_t192 == 2) return true;        // A/B measurements: 192-row tile wherever it is legal
+    static const int mode = env_switch("MRFP_CONV_T192", 1);      // =0: A/B measurements (measured +4..5 % on the long-K layers)
+    if (!mode || esz != 2 || p.N <= 64) return false;
+    if (mode == 2) return true;          // A/B measurements: 192-row tile wherever it is legal
     if (p.sstride > 1) return false;     // strided dgrads: the 128x128 tile wins (-12 %: the strided 192x128 instance spills 48 bytes per lane)
     // Whole rounds: three workgroups of this tile fit a CU (768 slots), and a launch of exactly 1, 2 or 4 rounds keeps every CU
     // equally busy to the end -- measured (tools/tile_sweep.sh, round 3) on every such layer of the bench step against the tile
@@ -745,13 +693,9 @@ static bool use_tile192(const ConvP& p, int esz) {
 // Row-reuse kernels: the tile (192 rows; 0 = not applicable) a launch runs on.  MRFP_CONV_RR=0: off; 1: where the plain
 // kernel would run the 192x128 tile; 2 (default): also instead of the 128x128 / 96x128 tiles; 3: wherever 192 rows fit the image
 // geometry (tests).  (A 96-row and a 192x64 variant for the N <= 64 layers were measured slower in round 2 and removed.)
-static int g_rr = -1;
 static int rr_tile(const ConvP& p, int esz) {
-    if (g_rr < 0) {
-        const char* e = getenv("MRFP_CONV_RR");
-        g_rr = e ? atoi(e) : 2;
-    }
-    if (!g_rr || esz != 2) return 0;
+    static const int mode = env_switch("MRFP_CONV_RR", 2);
+    if (!mode || esz != 2) return 0;
     if (p.R != 3 || p.S != 3 || p.stride != 1 || p.sstride != 1 || p.Ho != p.H || p.Wo != p.W) return 0;
     if (p.dil < 1 || p.dil > 2 || p.pad_h != p.dil || p.pad_w != p.dil) return 0;
     if ((p.cpr & 7) != 0 || (p.W & 15) != 0) return 0;
@@ -768,11 +712,10 @@ static int rr_tile(const ConvP& p, int esz) {
         // rows and three 64 x 64 weight tiles per filter row: 77 KB for 3 x 144 MFMAs per wave, 122 FLOP per fill byte.  (Round 2's
         // 192 x 64 variant -- 53 KB per fill, 82 FLOP per byte, three workgroups per CU -- had measured slower than the plain tile.)
         // MRFP_CONV_RR64=0 switches it off (A/B runs).
-        static int rr64 = -1;
-        if (rr64 < 0) { const char* e = getenv("MRFP_CONV_RR64"); rr64 = e ? atoi(e) : 1; }
+        static const int rr64 = env_switch("MRFP_CONV_RR64", 1);
         if (!rr64 || !fits(384)) return 0;
         const int64_t t384 = (int64_t)(p.M / 384);
-        return (g_rr >= 3 || t384 >= 512) ? 384 : 0;      // at least one full round at two workgroups per CU
+        return (mode >= 3 || t384 >= 512) ? 384 : 0;      // at least one full round at two workgroups per CU
     }
     // Where it pays (bench.py --dump-convs with the switch off / on, several boxes): long K (C >= 256: at least 12 patch fills
     // per tile to amortise the 76 KB prologue), at least one full round of tiles at two workgroups per CU, and an N that does not
@@ -782,63 +725,80 @@ static int rr_tile(const ConvP& p, int esz) {
     // (two of these workgroups fit a CU: a launch that is not whole rounds of 512 and short -- 512 -> 512 @48^2 d2, 768 tiles -- runs
     //  better on the plain 192x128 tile, three per CU: 887 vs 930 us for the six launches of the bench step)
     const bool pays = p.C >= 256 && t192 >= 512 && (t192 >= 2048 || t192 % 512 == 0) && ((p.N + 127) / 128) * 128 - p.N <= 64;
-    if (fits(192) && (g_rr >= 3 || (pays && (g_rr >= 2 || use_tile192(p, esz))))) return 192;
+    if (fits(192) && (mode >= 3 || (pays && (mode >= 2 || use_tile192(p, esz))))) return 192;
     return 0;
 }
 
-// number of statistics row blocks (= m-tiles x wave rows) the epilogue of a forward launch writes
-static int64_t stats_row_blocks(const ConvP& p, int esz) {
-    if (pw_applicable(p, esz)) return pw_stats_blocks(p);            // pointwise kernels (conv_pw.hip): one per workgroup range
-    if (pwk_applicable(p, esz)) return pwk_stats_blocks(p);          // long-K pointwise kernel (conv_pwk.hip): likewise
-    if (c64_applicable(p, esz)) return c64_stats_blocks(p);          // weight-stationary 3x3 kernel (conv_c64.hip): one per workgroup and sub-strip
-    if (rr_tile(p, esz) == 384) return (int64_t)(p.M / 384) * 4;      // row-reuse kernel for N <= 64: 384-row tiles, 4 wave rows
-    if (rr_tile(p, esz)) return (int64_t)(p.M / 192) * 2;             // row-reuse kernels: 192-row tiles, 2 wave rows
-    if (p.N > 64 && use_tile192(p, esz)) return (int64_t)((p.M + 191) / 192) * 2;      // <2,2,3,2>: 192-row tile, 2 wave rows
-    if (p.N <= 64) return (int64_t)((p.M + 255) / 256) * 4;          // <4,1,2,2>: 256-row tile, 4 wave rows
-    if (use_tile96(p, esz)) return (int64_t)((p.M + 95) / 96);          // <1,4,3,1>: 96-row tile, 1 wave row
-    return (int64_t)((p.M + 127) / 128) * 2;                          // <2,2,2,2>: 128-row tile, 2 wave rows
-}
-
-// output rows one statistics row block covers (block r = rows [r * rb, (r + 1) * rb) of the [M][N] output)
-static int64_t stats_block_rows(const ConvP& p, int esz) {
-    if (pw_applicable(p, esz)) return pw_stats_block_rows(p);
-    if (pwk_applicable(p, esz)) return pwk_stats_block_rows(p);
-    if (c64_applicable(p, esz)) return c64_stats_block_rows(p);     // negative: -(statistics rows per image)
-    if (rr_tile(p, esz)) return 96;
-    if (p.N > 64 && use_tile192(p, esz)) return 96;
-    if (p.N <= 64) return 64;
-    if (use_tile96(p, esz)) return 96;
-    return 64;
-}
-
-// tile height (output rows) run_igemm picks for the dgrad of a strided convolution (sstride > 1: neither the pointwise nor the
-// row-reuse kernels take those).  The class-major row order (ConvP::classed) needs every parity class to be WHOLE tiles of it --
-// with MRFP_CONV_T96 / T192 = 2 (A/B runs, tests) the 96- and 192-row tiles reach strided launches too.
-static int strided_tile_rows(const ConvP& p, int esz) {
-    if (p.N <= 64) return 256;
-    if (esz == 2 && use_tile192(p, esz)) return 192;
-    if (use_tile96(p, esz)) return 96;
-    return 128;
+// The kernel a forward / dgrad launch runs on and the statistics rows its epilogue writes -- the one rule read by the launch
+// (run_igemm), the class-major row order and the compaction (conv_fwd_impl) and the caller's workspace (mrfp_conv_stats_layout).
+// The specialised kernels first (each decides in its own file), then the row-reuse kernels, then the generic tiles.  A tile of
+// WM x WN waves with TM 32-row blocks per wave writes one statistics row block per wave row: 32 * TM output rows each.
+// (The 16-bit-only kernels refuse esz == 4 themselves: pw / pwk / c64 / rr_tile / use_tile192.)
+static ConvPlan conv_plan(const ConvP& p, int esz) {
+    ConvPlan plan{};
+    if (pw_plan(p, esz, plan) || pwk_plan(p, esz, plan) || c64_plan(p, esz, plan)) return plan;
+    auto tile = [&](ConvKernel kind, int WM, int TM) {
+        plan.kind = kind;
+        plan.tile_rows = 32 * TM * WM;
+        plan.stats_blocks = (int64_t)((p.M + plan.tile_rows - 1) / plan.tile_rows) * WM;
+        plan.stats_block_rows = 32 * TM;
+        return plan;
+    };
+    const int rr = rr_tile(p, esz);
+    if (rr == 384) return tile(ConvKernel::rr384, 4, 3);              // <4,1,3,2>, N <= 64
+    if (rr) return tile(ConvKernel::rr192, 2, 3);                     // <2,2,3,2>
+    if (p.N <= 64) return tile(ConvKernel::t256x64, 4, 2);            // <4,1,2,2>
+    // (measured and dropped: the 256x256 8-wave tile, a two-wave 96x128 variant, a 256x128 tile, a 160x128 tile:
+    //  profiles/r02_experiments.md)
+    if (use_tile192(p, esz)) return tile(ConvKernel::t192x128, 2, 3);  // <2,2,3,2>
+    if (use_tile96(p, esz)) return tile(ConvKernel::t96x128, 1, 3);    // <1,4,3,1>
+    return tile(ConvKernel::t128x128, 2, 2);                          // <2,2,2,2>
 }
 
 template <typename T>
-static int run_igemm(const ConvP& p, hipStream_t st) {
-    if constexpr (sizeof(T) == 2) {
-        if (pw_applicable(p, 2)) return pw_run(p, std::is_same<T, f16>::value, st);
-        if (pwk_applicable(p, 2)) return pwk_run(p, std::is_same<T, f16>::value, st);
-        if (c64_applicable(p, 2)) return c64_run(p, std::is_same<T, f16>::value, st);
-        const int rr = rr_tile(p, 2);
-        if (rr == 384) return launch_igemm_rr<T, 4, 1, 3, 2>(p, st);
-        if (rr) return launch_igemm_rr<T, 2, 2, 3, 2>(p, st);
+static int run_igemm(const ConvP& p, const ConvPlan& plan, hipStream_t st) {
+    if constexpr (sizeof(T) == 2) {      // (kernels with 16-bit instances only: conv_plan never picks them for fp32)
+        const bool is_f16 = std::is_same<T, f16>::value;
+        switch (plan.kind) {
+        case ConvKernel::pw: return pw_run(p, is_f16, st);
+        case ConvKernel::pwk: return pwk_run(p, is_f16, st);
+        case ConvKernel::c64: return c64_run(p, plan, is_f16, st);
+        case ConvKernel::rr384: return launch_igemm_rr<T, 4, 1, 3, 2>(p, st);
+        case ConvKernel::rr192: return launch_igemm_rr<T, 2, 2, 3, 2>(p, st);
+        case ConvKernel::t192x128: return pick_igemm<T, 2, 2, 3, 2>(p, st);
+        default: break;
+        }
     }
-    if (p.N <= 64) return pick_igemm<T, 4, 1, 2, 2>(p, st);
-    // (measured and dropped: the 256x256 8-wave tile, a two-wave 96x128 variant, a 256x128 tile, a 160x128 tile:
-    //  profiles/r02_experiments.md)
-    if constexpr (sizeof(T) == 2) {
-        if (use_tile192(p, (int)sizeof(T))) return pick_igemm<T, 2, 2, 3, 2>(p, st);
+    switch (plan.kind) {
+    case ConvKernel::t256x64: return pick_igemm<T, 4, 1, 2, 2>(p, st);
+    case ConvKernel::t96x128: return pick_igemm<T, 1, 4, 3, 1>(p, st);
+    case ConvKernel::t128x128: return pick_igemm<T, 2, 2, 2, 2>(p, st);
+    default: break;
     }
-    if (use_tile96(p, (int)sizeof(T))) return pick_igemm<T, 1, 4, 3, 1>(p, st);
-    return pick_igemm<T, 2, 2, 2, 2>(p, st);
+    set_error("conv_fwd: kernel %d has no fp32 instance", (int)plan.kind);
+    return -1;
+}
+
+// The kernel argument of a forward / dgrad launch from the mrfp_conv_fwd* arguments: geometry, M, cpr, kchunks, and the optional
+// operands -- which of them are present is part of what conv_plan reads.  The tensor pointers, the buffer sizes and the class-major
+// row order are per launch (conv_fwd_impl).
+static int conv_params(ConvP& p, int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S,
+                       int64_t Ho, int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t sstride,
+                       const float* bias, const void* addend, const void* addend_mask, float* colstats, const unsigned char* rowweight) {
+    MRFP_CHECK(B > 0 && H > 0 && W > 0 && C > 0 && N > 0 && R > 0 && S > 0 && Ho > 0 && Wo > 0, "conv_fwd: bad arguments");
+    MRFP_CHECK(stride >= 1 && dil >= 1 && sstride >= 1 && ldy >= N, "conv_fwd: bad stride/dilation/pitch");
+    MRFP_CHECK(dtype == MRFP_F32 || dtype == MRFP_BF16 || dtype == MRFP_F16, "conv_fwd: unknown dtype %d", dtype);
+    const int esz = dtype == MRFP_F32 ? 4 : 2;
+    MRFP_CHECK((C * esz) % 16 == 0, "conv_fwd: C=%lld must make 16-byte chunks (pad the channels)", (long long)C);
+    MRFP_CHECK(B * Ho * Wo < (1LL << 31), "conv_fwd: tensor too large for 32-bit tile indices");
+    p = ConvP{};
+    p.bias = bias; p.addend = (const char*)addend; p.addend_mask = (const unsigned char*)addend_mask;
+    p.colstats = colstats; p.rowweight = rowweight;
+    p.B = (int)B; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.N = (int)N; p.ldy = (int)ldy;
+    p.R = (int)R; p.S = (int)S; p.Ho = (int)Ho; p.Wo = (int)Wo;
+    p.stride = (int)stride; p.pad_h = (int)pad_h; p.pad_w = (int)pad_w; p.dil = (int)dil; p.sstride = (int)sstride;
+    p.M = (int)(B * Ho * Wo); p.cpr = (int)(C * esz / 16); p.kchunks = (int)(R * S * p.cpr);
+    return 0;
 }
 
 }  // namespace mrfp
@@ -855,30 +815,27 @@ static int conv_fwd_impl(const void* x, const void* wpack, const float* bias, vo
     MRFP_CHECK(!rowweight || (colstats && ((uintptr_t)rowweight & 3) == 0), "conv_fwd_wstats: the row weights need statistics and 4-byte alignment");
     MRFP_CHECK(!addend_mask || (addend && dtype != MRFP_F32 && (N & 7) == 0 && ldy == N),
                "conv_fwd_gated: a gate mask needs an addend, 16-bit activations, N %% 8 == 0 and a dense output");
-    MRFP_CHECK(x && wpack && y && B > 0 && H > 0 && W > 0 && C > 0 && N > 0 && R > 0 && S > 0 && Ho > 0 && Wo > 0,
-               "conv_fwd: bad arguments");
-    MRFP_CHECK(stride >= 1 && dil >= 1 && sstride >= 1 && ldy >= N, "conv_fwd: bad stride/dilation/pitch");
-    const int esz = dtype == MRFP_F32 ? 4 : 2;
-    MRFP_CHECK(dtype == MRFP_F32 || dtype == MRFP_BF16 || dtype == MRFP_F16, "conv_fwd: unknown dtype %d", dtype);
-    MRFP_CHECK((C * esz) % 16 == 0, "conv_fwd: C=%lld must make 16-byte chunks (pad the channels)", (long long)C);
-    MRFP_CHECK(aligned16(x) && aligned16(wpack), "conv_fwd: x / wpack must be 16-byte aligned");
-    MRFP_CHECK(B * Ho * Wo < (1LL << 31), "conv_fwd: tensor too large for 32-bit tile indices");
+    MRFP_CHECK(x && wpack && y, "conv_fwd: bad arguments");
     ConvP p;
-    p.x = (const char*)x; p.w = (const char*)wpack; p.y = (char*)y; p.bias = bias; p.addend = (const char*)addend; p.colstats = colstats;
-    p.addend_mask = (const unsigned char*)addend_mask;
-    p.rowweight = rowweight;
-    p.B = (int)B; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.N = (int)N; p.ldy = (int)ldy;
-    p.R = (int)R; p.S = (int)S; p.Ho = (int)Ho; p.Wo = (int)Wo;
-    p.stride = (int)stride; p.pad_h = (int)pad_h; p.pad_w = (int)pad_w; p.dil = (int)dil; p.sstride = (int)sstride;
-    p.M = (int)(B * Ho * Wo); p.cpr = (int)(C * esz / 16); p.kchunks = (int)(R * S * p.cpr);
+    const int bad = conv_params(p, dtype, B, H, W, C, N, ldy, R, S, Ho, Wo, stride, pad_h, pad_w, dil, sstride, bias, addend, addend_mask,
+                                colstats, rowweight);
+    if (bad) return bad;
+    MRFP_CHECK(aligned16(x) && aligned16(wpack), "conv_fwd: x / wpack must be 16-byte aligned");
+    const int esz = dtype == MRFP_F32 ? 4 : 2;
+    p.w = (const char*)wpack;
+    // The plan is made from the whole batch BEFORE the class-major row order below changes M: that decision needs the tile height,
+    // and M cannot change it -- class-major launches are strided dgrads, which only the generic tiles take, and the tile rules for
+    // those never look at M (use_tile192 / use_tile96 decide on the switches and sstride alone).  Class-major launches carry no
+    // statistics, so the row blocks of the whole-batch M size nothing.  (Batch ranges get a plan each, in the loop.)
+    ConvPlan plan = conv_plan(p, esz);
     {   // dgrad of a stride-2 convolution: parity-class-major rows (see the kernel) where the geometry allows it -- even output size,
         // whole 64-channel K tiles, classes of whole (<= 256-row) tiles, one launch.  MRFP_DGRAD_CLASSED=0: the per-pixel form (A/B runs)
-        static int on = -1;
-        if (on < 0) { const char* e = getenv("MRFP_DGRAD_CLASSED"); on = e ? atoi(e) : 1; }
+        static const int on = env_switch("MRFP_DGRAD_CLASSED", 1);
         p.classed = on && sstride == 2 && stride == 1 && dil == 1 && (Ho & 1) == 0 && (Wo & 1) == 0 && (p.cpr & 7) == 0 &&
                     ((B * (Ho / 2) * (Wo / 2)) % 256) == 0 && !colstats;
-        // ... and whole tiles of the height this launch will actually run (a tile straddling two classes would index past dx)
-        if (p.classed && ((B * (Ho / 2) * (Wo / 2)) % strided_tile_rows(p, esz)) != 0) p.classed = 0;
+        // ... and whole tiles of the height this launch will actually run (a tile straddling two classes would index past dx; with
+        // MRFP_CONV_T96 / T192 = 2 -- A/B runs, tests -- the 96- and 192-row tiles reach strided launches too)
+        if (p.classed && ((B * (Ho / 2) * (Wo / 2)) % plan.tile_rows) != 0) p.classed = 0;
         // pointwise: rows = the even-even pixels only, the epilogue stores 2 x 2 blocks (measured: three classes of store-only tiles
         // made the class-major form 20 % SLOWER than the per-pixel one on the 1x1 stride-2 downsample dgrads)
         if (p.classed && R == 1 && S == 1 && pad_h == 0 && pad_w == 0) p.classed = 2;
@@ -894,14 +851,10 @@ static int conv_fwd_impl(const void* x, const void* wpack, const float* bias, vo
     const int64_t bmax = (int64_t)(kOOB - 1) / img;          // images per launch
     const bool chunked = B > bmax;
     MRFP_CHECK(!chunked || !colstats, "conv_fwd: fused statistics are not available for inputs above 3.75 GB (see mrfp_conv_single_launch)");
-    MRFP_CHECK(!rowweight || !pw_applicable(p, esz), "conv_fwd_wstats: not available on the pointwise kernels");
+    MRFP_CHECK(!rowweight || plan.kind != ConvKernel::pw, "conv_fwd_wstats: not available on the pointwise kernels");
     if (chunked) p.classed = 0;          // (batch ranges: the class size would change per range)
-    int dbg_drop = 0;
-    {   // timing-only diagnostics: zero-record descriptors drop that operand's traffic, instruction stream unchanged
-        static int dbg = -1;
-        if (dbg < 0) { const char* e = getenv("MRFP_DEBUG_DROP"); dbg = e ? atoi(e) : 0; }
-        dbg_drop = dbg;
-    }
+    // timing-only diagnostics: zero-record descriptors drop that operand's traffic, instruction stream unchanged
+    static const int dbg_drop = env_switch("MRFP_DEBUG_DROP", 0);
     int rc = 0;
     for (int64_t b0 = 0; b0 < B && !rc; b0 += bmax) {
         const int64_t bc = B - b0 < bmax ? B - b0 : bmax;
@@ -914,15 +867,15 @@ static int conv_fwd_impl(const void* x, const void* wpack, const float* bias, vo
         p.addend_mask = addend_mask ? (const unsigned char*)addend_mask + ((m0 * ldy) >> 3) : nullptr;
         p.xbytes = (dbg_drop & 1) ? 0u : (unsigned)(bc * img);
         p.wbytes = (dbg_drop & 2) ? 0u : (unsigned)wb;
-        rc = dtype == MRFP_F32 ? run_igemm<float>(p, (hipStream_t)stream)
-             : dtype == MRFP_F16 ? run_igemm<f16>(p, (hipStream_t)stream) : run_igemm<bf16>(p, (hipStream_t)stream);
+        if (chunked) plan = conv_plan(p, esz);       // a batch range is a launch of its own: a smaller M may take another kernel
+        rc = dtype == MRFP_F32 ? run_igemm<float>(p, plan, (hipStream_t)stream)
+             : dtype == MRFP_F16 ? run_igemm<f16>(p, plan, (hipStream_t)stream) : run_igemm<bf16>(p, plan, (hipStream_t)stream);
     }
     if (rc || !colstats) return rc;
-    const int64_t nblk = stats_row_blocks(p, esz);
-    if (nblk > kCompactAbove) {
+    if (plan.stats_blocks > kCompactAbove) {
         const int C2 = 2 * (int)ldy;
         hipLaunchKernelGGL(compact_stats_kernel, dim3((unsigned)((C2 + 63) / 64), kStatGroups), dim3(256), 0,
-                           (hipStream_t)stream, colstats, (int)nblk, C2);
+                           (hipStream_t)stream, colstats, (int)plan.stats_blocks, C2);
         MRFP_LAUNCH_CHECK();
     }
     return 0;
@@ -973,37 +926,36 @@ int mrfp_conv_fwd_gated(const void* x, const void* wpack, const float* bias, voi
                          nullptr, stream, addend_mask);
 }
 
-int64_t mrfp_conv_stats_blocks(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t R, int64_t S, int64_t Ho,
-                               int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t sstride) {
-    // the SAME geometry the launch will see (conv_fwd_impl): the kernel choice -- and with it the number of row blocks -- looks at
-    // the filter, stride, padding, dilation and image size, not only at M, N, C
+int mrfp_conv_stats_layout(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S,
+                           int64_t Ho, int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t sstride, int wstats,
+                           int64_t* out) {
+    MRFP_CHECK(out, "conv_stats_layout: no output array");
+    // the operands the launch will carry (mrfp_conv_fwd with a statistics buffer and no bias or addend, or mrfp_conv_fwd_wstats):
+    // the plan reads only whether they are present, so stand-ins do
+    float stats_present;
+    unsigned char rows_present;
     ConvP p;
-    const int esz = dtype == MRFP_F32 ? 4 : 2;
-    p.B = (int)B; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.N = (int)N; p.ldy = (int)N;
-    p.R = (int)R; p.S = (int)S; p.Ho = (int)Ho; p.Wo = (int)Wo;
-    p.stride = (int)stride; p.pad_h = (int)pad_h; p.pad_w = (int)pad_w; p.dil = (int)dil; p.sstride = (int)sstride;
-    p.M = (int)(B * Ho * Wo); p.cpr = (int)(C * esz / 16); p.kchunks = (int)(R * S * p.cpr);
-    p.classed = 0;
-    p.bias = nullptr; p.colstats = nullptr; p.rowweight = nullptr; p.addend = nullptr; p.addend_mask = nullptr;
-    return stats_row_blocks(p, esz);
+    const int bad = conv_params(p, dtype, B, H, W, C, N, ldy, R, S, Ho, Wo, stride, pad_h, pad_w, dil, sstride, nullptr, nullptr,
+                                nullptr, &stats_present, wstats ? &rows_present : nullptr);
+    if (bad) return bad;
+    const ConvPlan plan = conv_plan(p, dtype == MRFP_F32 ? 4 : 2);
+    const int64_t nblk = plan.stats_blocks;
+    const bool compact = nblk > kCompactAbove;      // (conv_fwd_impl: the groups are appended behind the row blocks)
+    out[0] = nblk;
+    out[1] = plan.stats_block_rows;
+    out[2] = compact ? nblk + kStatGroups : nblk;
+    out[3] = compact ? nblk : 0;
+    out[4] = compact ? kStatGroups : nblk;
+    return 0;
 }
+
+/* out[1] of mrfp_conv_stats_layout for a dense (ldy = N), unweighted launch; 0 on bad geometry (the value that means "no per-image
+ * use").  Kept for callers that only need the block height (the c64 kernel test). */
 int64_t mrfp_conv_stats_block_rows(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t R, int64_t S, int64_t Ho,
                                    int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t sstride) {
-    ConvP p;
-    const int esz = dtype == MRFP_F32 ? 4 : 2;
-    p.B = (int)B; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.N = (int)N; p.ldy = (int)N;
-    p.R = (int)R; p.S = (int)S; p.Ho = (int)Ho; p.Wo = (int)Wo;
-    p.stride = (int)stride; p.pad_h = (int)pad_h; p.pad_w = (int)pad_w; p.dil = (int)dil; p.sstride = (int)sstride;
-    p.M = (int)(B * Ho * Wo); p.cpr = (int)(C * esz / 16); p.kchunks = (int)(R * S * p.cpr);
-    p.classed = 0;
-    p.bias = nullptr; p.colstats = nullptr; p.rowweight = nullptr; p.addend = nullptr; p.addend_mask = nullptr;
-    return stats_block_rows(p, esz);
+    int64_t lay[5];
+    return mrfp_conv_stats_layout(dtype, B, H, W, C, N, N, R, S, Ho, Wo, stride, pad_h, pad_w, dil, sstride, 0, lay) ? 0 : lay[1];
 }
-/* rows the caller must allocate for `colstats` (row blocks + the compacted groups) */
-int64_t mrfp_conv_stats_rows(int64_t nblk) { return nblk > kCompactAbove ? nblk + kStatGroups : nblk; }
-/* where the rows to hand to mrfp_bn_finalize start, and how many there are */
-int64_t mrfp_conv_stats_final_first(int64_t nblk) { return nblk > kCompactAbove ? nblk : 0; }
-int64_t mrfp_conv_stats_final_count(int64_t nblk) { return nblk > kCompactAbove ? kStatGroups : nblk; }
 
 
 }  // extern "C"

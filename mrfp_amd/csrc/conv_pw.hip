@@ -310,15 +310,10 @@ __global__ __launch_bounds__(256, 2) void conv1x1_bstat_kernel(BsP p) {
     }
 }
 
-static int g_bstat = -1;
 // the layers the B-stationary kernel takes (MRFP_CONV_PW=0: generic kernel everywhere, for A/B runs)
 static bool use_bstat(const ConvP& p, int esz) {
-    const bool has_bias = p.bias != nullptr;
-    if (g_bstat < 0) {
-        const char* e = getenv("MRFP_CONV_PW");
-        g_bstat = e ? atoi(e) : 1;
-    }
-    if (!g_bstat || esz != 2 || has_bias || (p.colstats && p.addend)) return false;
+    static const int on = env_switch("MRFP_CONV_PW", 1);
+    if (!on || esz != 2 || p.bias != nullptr || (p.colstats && p.addend)) return false;
     if (p.R != 1 || p.S != 1 || p.stride != 1 || p.sstride != 1 || p.pad_h != 0 || p.pad_w != 0) return false;
     if (p.Ho != p.H || p.Wo != p.W || p.N < 128 || (p.N & 7) != 0) return false;
     if ((int64_t)p.M * p.ldy * esz >= (int64_t)kOOB) return false;        // the output is addressed through a buffer descriptor
@@ -326,8 +321,7 @@ static bool use_bstat(const ConvP& p, int esz) {
     // K = 32 (HALF): OFF by default.  Measured in round 5 (profiles/r05_experiments.md): with fused statistics it beats the generic
     // unaligned kernel (0.390 vs 0.458 ms at 16 x 384^2, 32 -> 256), but the two launches of the bench step -- the head's dgrads, no
     // statistics, no addend -- run SLOWER on it (390 vs 348 us, 98.9 vs 96.1 us).  MRFP_CONV_PW32=1 enables it (tests, A/B runs).
-    static int half = -1;
-    if (half < 0) { const char* e = getenv("MRFP_CONV_PW32"); half = e ? atoi(e) : 0; }
+    static const int half = env_switch("MRFP_CONV_PW32", 0);
     return rowb == 128 || rowb == 256 || rowb == 512 || (rowb == 64 && half);
 }
 
@@ -362,11 +356,8 @@ static int launch_bstat(const ConvP& c, hipStream_t st) {
     p.chunks = bstat_chunks(c.M, c.N);
     const int chunks = (p.chunks + 7) / 8 * 8;           // grid: whole groups of 8 (workgroups past p.chunks exit at once)
     p.xbytes = c.xbytes; p.wbytes = c.wbytes; p.ybytes = (unsigned)((int64_t)c.M * c.ldy * 2);
-    {   // timing-only diagnostics (MRFP_DEBUG_DROP bit 2: drop the output stores)
-        static int dbg = -1;
-        if (dbg < 0) { const char* e = getenv("MRFP_DEBUG_DROP"); dbg = e ? atoi(e) : 0; }
-        if (dbg & 4) p.ybytes = 0;
-    }
+    static const int dbg = env_switch("MRFP_DEBUG_DROP", 0);      // timing-only diagnostics (bit 2: drop the output stores)
+    if (dbg & 4) p.ybytes = 0;
     hipLaunchKernelGGL((conv1x1_bstat_kernel<T, KB, NST, STATS, ADD, HALF>), dim3((unsigned)(p.panels * chunks)), dim3(256), lds, st, p);
     MRFP_LAUNCH_CHECK();
     return 0;
@@ -387,11 +378,15 @@ static int run_bstat(const ConvP& p, hipStream_t st) {
     return run_bstat_v<T, false, false>(p, st);
 }
 
-bool pw_applicable(const ConvP& p, int esz) { return use_bstat(p, esz); }
-int64_t pw_stats_blocks(const ConvP& p) { return (int64_t)bstat_chunks(p.M, p.N); }
-int64_t pw_stats_block_rows(const ConvP& p) {      // rows of one statistics row block (a workgroup's tile range)
+bool pw_plan(const ConvP& p, int esz, ConvPlan& plan) {
+    if (!use_bstat(p, esz)) return false;
+    // one statistics row block per workgroup range: a range's tiles (the last one may hold fewer)
     const int tiles = (p.M + 63) / 64, chunks = bstat_chunks(p.M, p.N);
-    return (int64_t)((tiles + chunks - 1) / chunks) * 64;
+    plan.kind = ConvKernel::pw;
+    plan.tile_rows = 64;
+    plan.stats_blocks = chunks;
+    plan.stats_block_rows = (int64_t)((tiles + chunks - 1) / chunks) * 64;
+    return true;
 }
 int pw_run(const ConvP& p, bool is_f16, hipStream_t st) { return is_f16 ? run_bstat<f16>(p, st) : run_bstat<bf16>(p, st); }
 

@@ -469,13 +469,9 @@ __global__ __launch_bounds__(512, 2) void conv1x1_longk2_kernel(PkP p) {
     }
 }
 
-static int g_pwk = -1;
-bool pwk_applicable(const ConvP& p, int esz) {
-    if (g_pwk < 0) {
-        const char* e = getenv("MRFP_CONV_PWK");
-        g_pwk = e ? atoi(e) : 1;
-    }
-    if (!g_pwk || esz != 2 || p.bias != nullptr || (p.colstats && p.addend) || p.rowweight) return false;
+static bool pwk_applicable(const ConvP& p, int esz) {
+    static const int mode = env_switch("MRFP_CONV_PWK", 1);
+    if (!mode || esz != 2 || p.bias != nullptr || (p.colstats && p.addend) || p.rowweight) return false;
     if (p.R != 1 || p.S != 1 || p.stride != 1 || p.sstride != 1 || p.pad_h != 0 || p.pad_w != 0) return false;
     if (p.Ho != p.H || p.Wo != p.W || p.N < 128 || (p.N & 7) != 0) return false;
     if ((int64_t)p.M * p.ldy * esz >= (int64_t)kOOB) return false;
@@ -485,7 +481,7 @@ bool pwk_applicable(const ConvP& p, int esz) {
     const int rows = rowb == 2048 ? kPk2Rows : kPkRows;
     const int64_t tiles = (p.M + rows - 1) / rows, panels = (p.N + 127) / 128;
     const int64_t slots = rowb == 1024 ? 512 : 256;
-    return g_pwk >= 2 || tiles * panels >= 4 * slots;
+    return mode >= 2 || tiles * panels >= 4 * slots;
 }
 // M-tile ranges per panel: one (K >= 1024) or two (K = 512) workgroups per CU, a multiple of 8 (the XCD mapping), no range empty
 static int pwk_rows(int rowb) { return rowb == 2048 ? kPk2Rows : kPkRows; }      // tile height: K = 1 024 runs the two-group kernel
@@ -498,11 +494,15 @@ static int pwk_chunks(int M, int N, int rowb) {
     const int per = (tiles + chunks - 1) / chunks;
     return (tiles + per - 1) / per;
 }
-int64_t pwk_stats_blocks(const ConvP& p) { return (int64_t)pwk_chunks(p.M, p.N, p.C * 2); }
-int64_t pwk_stats_block_rows(const ConvP& p) {
+bool pwk_plan(const ConvP& p, int esz, ConvPlan& plan) {
+    if (!pwk_applicable(p, esz)) return false;
     const int rows = pwk_rows(p.C * 2);
     const int tiles = (p.M + rows - 1) / rows, chunks = pwk_chunks(p.M, p.N, p.C * 2);
-    return (int64_t)((tiles + chunks - 1) / chunks) * rows;
+    plan.kind = ConvKernel::pwk;
+    plan.tile_rows = rows;
+    plan.stats_blocks = chunks;
+    plan.stats_block_rows = (int64_t)((tiles + chunks - 1) / chunks) * rows;
+    return true;
 }
 
 template <typename T, bool STATS, bool ADD>
@@ -558,8 +558,7 @@ static int pwk_pick(const ConvP& p, hipStream_t st) {
 template <typename T>
 static int pwk_run_t(const ConvP& p, hipStream_t st) {
     const int kq = p.C * 2 / 512;
-    static int two = -1;               // MRFP_CONV_PWK2=0: K = 1 024 on the one-wave-per-SIMD form (A/B runs)
-    if (two < 0) { const char* e = getenv("MRFP_CONV_PWK2"); two = e ? atoi(e) : 1; }
+    static const int two = env_switch("MRFP_CONV_PWK2", 1);      // =0: K = 1 024 on the one-wave-per-SIMD form (A/B runs)
     if (kq == 4 && two) {
         if (p.colstats) return pwk2_launch<T, true, false>(p, st);
         if (p.addend) return pwk2_launch<T, false, true>(p, st);

@@ -172,13 +172,10 @@ __global__ __launch_bounds__(512, 2) void conv_wg1_kernel(Wg1P p, Wg1Group grp) 
 }
 
 // ---------------------------------------------------------------------------------------------
-static int g_wg1 = -1;
 static int wg1_mode() {
-    if (g_wg1 < 0) {
-        const char* e = getenv("MRFP_WGRAD1");      // 0: never; 1 (default): where the rule below says; 2: wherever it is legal (tests, A/B runs)
-        g_wg1 = e ? atoi(e) : 1;
-    }
-    return g_wg1;
+    // 0: never; 1 (default): where the rule below says; 2: wherever it is legal (tests, A/B runs)
+    static const int mode = env_switch("MRFP_WGRAD1", 1);
+    return mode;
 }
 struct Wg1Plan {
     int ncb, ncls, Wp, a, L, R, Wr, splits, U;

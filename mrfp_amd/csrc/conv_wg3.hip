@@ -248,13 +248,10 @@ __global__ __launch_bounds__(256, 2) void conv_wg3_kernel(Wg3P p, Wg3Group grp) 
 }
 
 // ---------------------------------------------------------------------------------------------
-static int g_wg3 = -1;
 static int wg3_mode() {
-    if (g_wg3 < 0) {
-        const char* e = getenv("MRFP_WGRAD3");      // 0: never; 1 (default): where the rule below says; 2: wherever it is legal (tests, A/B runs)
-        g_wg3 = e ? atoi(e) : 1;
-    }
-    return g_wg3;
+    // 0: never; 1 (default): where the rule below says; 2: wherever it is legal (tests, A/B runs)
+    static const int mode = env_switch("MRFP_WGRAD3", 1);
+    return mode;
 }
 // strip width / rows per unit for image width W: 64 x 1, 96 x 1 or 48 x 2 (0: none)
 static int wg3_strip(int64_t W, int& ru) {

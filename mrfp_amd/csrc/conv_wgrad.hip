@@ -422,8 +422,7 @@ static int launch_wgrad_v(const WgP& p, int splits, hipStream_t st, const WgGrou
     // MRFP_WGRAD_LDS=<bytes> (experiments: tools/overlap_micro.py): ask for at least that much LDS per workgroup, i.e. cap the
     // workgroups per CU below what the registers allow (81920: one per CU) -- how much of a concurrent HBM-bound kernel's time
     // a weight-gradient launch can hide in when it leaves register file and wave slots free
-    static int lds_min = -1;
-    if (lds_min < 0) { const char* e = getenv("MRFP_WGRAD_LDS"); lds_min = e ? atoi(e) : 0; }
+    static const int lds_min = env_switch("MRFP_WGRAD_LDS", 0);
     const int lds_need = WgTile<T>::BKP * (PY + PX);
     const int lds = lds_need > lds_min ? lds_need : lds_min;
     static bool attr_set = false;
@@ -443,11 +442,9 @@ static int launch_wgrad_v(const WgP& p, int splits, hipStream_t st, const WgGrou
 // MRFP_WGRAD_DMA=0 keeps register staging for the 16-bit types (A/B measurements); fp32 always stages in registers
 template <typename T, int WM, int WN>
 static int launch_wgrad(const WgP& p, int splits, hipStream_t st, const WgGroup* grp, int tmb = 2) {
-    static int dma = -1;
-    if (dma < 0) { const char* e = getenv("MRFP_WGRAD_DMA"); dma = e ? atoi(e) : 1; }
+    static const int dma = env_switch("MRFP_WGRAD_DMA", 1);
     if (sizeof(T) == 2 && dma) {
-        static int dense = -1;
-        if (dense < 0) { const char* e = getenv("MRFP_WGRAD_DENSE"); dense = e ? atoi(e) : 1; }
+        static const int dense = env_switch("MRFP_WGRAD_DENSE", 1);
         const bool pointwise = p.R == 1 && p.S == 1 && p.stride == 1 && p.pad_h == 0 && p.pad_w == 0 && p.H == p.Ho && p.W == p.Wo;
         if constexpr (WM == 2 && sizeof(T) == 2) {
             if (tmb == 4) {
@@ -463,13 +460,8 @@ static int launch_wgrad(const WgP& p, int splits, hipStream_t st, const WgGroup*
 
 // MRFP_WGRAD_BIG: 0 = never the 256 x 128 tile, 1 (default) = where the cost model prefers it, 2 = wherever it is legal (A/B runs)
 static int wgrad_big_mode() {
-    static int mode = -1;
-    if (mode < 0) {
-        const char* e = getenv("MRFP_WGRAD_BIG");
-        mode = e ? atoi(e) : 1;
-        const char* d = getenv("MRFP_WGRAD_DMA");      // (=0: the register-staged A/B path of the 16-bit kernels has no 256 x 128 instance)
-        if (d && atoi(d) == 0) mode = 0;
-    }
+    // (MRFP_WGRAD_DMA=0: the register-staged A/B path of the 16-bit kernels has no 256 x 128 instance)
+    static const int mode = env_switch("MRFP_WGRAD_DMA", 1) == 0 ? 0 : env_switch("MRFP_WGRAD_BIG", 1);
     return mode;
 }
 
@@ -479,11 +471,7 @@ static int wgrad_big_mode() {
 //   latency); every split adds an fp32 slab of dW that is written once and read once by the reduction (~3 TB/s).
 // MRFP_WGRAD_WGS=<n> replaces the model by "about n workgroups" (A/B measurements).
 static double wgrad_cost(int64_t tiles, int64_t nkt, int64_t group, double nq, double step, int occ, int64_t& sp_out) {
-    static int target = -1;
-    if (target < 0) {
-        const char* e = getenv("MRFP_WGRAD_WGS");
-        target = e ? atoi(e) : 0;
-    }
+    static const int target = env_switch("MRFP_WGRAD_WGS", 0);
     int64_t sp = 1;
     double best = 1e30;
     if (target > 0) {
@@ -592,12 +580,7 @@ static int wgrad_run(const void* const* xs, const void* const* dys, float* const
     MRFP_CHECK(ximg < (int64_t)kOOB && yimg < (int64_t)kOOB, "conv_wgrad: one image exceeds the 3.75 GB buffer-descriptor range");
     int64_t bmax = (int64_t)(kOOB - 1) / (ximg > yimg ? ximg : yimg);
     MRFP_CHECK(count == 1 || bmax >= B, "conv_wgrad_grouped: the activations of a grouped launch must fit one 3.75 GB buffer range each");
-    int dbg_drop = 0;
-    {   // timing-only diagnostics (see mrfp_conv_fwd)
-        static int dbg = -1;
-        if (dbg < 0) { const char* e = getenv("MRFP_DEBUG_DROP"); dbg = e ? atoi(e) : 0; }
-        dbg_drop = dbg;
-    }
+    static const int dbg_drop = env_switch("MRFP_DEBUG_DROP", 0);      // timing-only diagnostics (see mrfp_conv_fwd)
     p.div_hw = make_fastdiv((unsigned)(Ho * Wo)); p.div_w = make_fastdiv((unsigned)Wo);
     hipStream_t st = (hipStream_t)stream;
     int wm0, cap, klen0;

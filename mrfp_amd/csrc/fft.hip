@@ -292,14 +292,12 @@ __device__ __forceinline__ void two_step(float2 (&a)[N1], float2 (&b)[N2], float
 }
 
 static int fft_nopair() {        // MRFP_FFT_NOPAIR=1: band-limited row passes one channel per transform (A/B)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MRFP_FFT_NOPAIR"); v = e ? atoi(e) : 0; }
+    static const int v = env_switch("MRFP_FFT_NOPAIR", 0);
     return v;
 }
 
 static int fft_nodirect() {      // MRFP_FFT_NODIRECT=1: band-limited inverse row pass on the register FFT (A/B)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MRFP_FFT_NODIRECT"); v = e ? atoi(e) : 0; }
+    static const int v = env_switch("MRFP_FFT_NODIRECT", 0);
     return v;
 }
 
@@ -495,9 +493,8 @@ __global__ __launch_bounds__(two_nt(N1, N2)) void fft_rows_inv_pair_kernel(FftP 
 // of memory instructions, not by bytes), 64 channels per workgroup, j = slot + NSLOT i.
 constexpr int kDirCh = 64, kDirThreads = 256;
 static int dir_lines() {         // lines per workgroup of the direct pass (the trig table is built once per workgroup)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MRFP_FFT_DIRLINES"); v = e ? atoi(e) : 1; if (v < 1) v = 1; }
-    return v;
+    static const int v = env_switch("MRFP_FFT_DIRLINES", 1);
+    return v < 1 ? 1 : v;
 }
 template <typename T, int PPT, int CH>
 __global__ __launch_bounds__(kDirThreads) void dft_rows_inv_direct_kernel(FftP p) {
@@ -606,14 +603,12 @@ __device__ __forceinline__ bfx4 as_bfx4(unsigned a, unsigned b) {
 }
 
 static int fft_mfma() {          // MRFP_FFT_MFMA=0: band-limited inverse row pass as the fp32 direct sum (A/B)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MRFP_FFT_MFMA"); v = e ? atoi(e) : 1; }
+    static const int v = env_switch("MRFP_FFT_MFMA", 1);
     return v;
 }
 static int fft_mfma_wgs() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MRFP_FFT_MFMA_WGS"); v = e ? atoi(e) : 768; if (v < 8) v = 8; }
-    return v;
+    static const int v = env_switch("MRFP_FFT_MFMA_WGS", 768);
+    return v < 8 ? 8 : v;
 }
 
 // LDS image of T^t: for every (part hi / lo, k block kb, lane quarter g) an array over the pixels w of 8-byte entries
@@ -1089,13 +1084,11 @@ static bool has_fast_plan(int n) {
 }
 
 static int fft_generic() {
-    static int generic = -1;
-    if (generic < 0) { const char* e = getenv("MRFP_FFT_GENERIC"); generic = e ? atoi(e) : 0; }
+    static const int generic = env_switch("MRFP_FFT_GENERIC", 0);
     return generic;
 }
 static int fft_full() {          // MRFP_FFT_FULL=1: full half spectrum even for a low band (A/B against the band-limited path)
-    static int full = -1;
-    if (full < 0) { const char* e = getenv("MRFP_FFT_FULL"); full = e ? atoi(e) : 0; }
+    static const int full = env_switch("MRFP_FFT_FULL", 0);
     return full;
 }
 // bins along W that S / S3 / ratio hold.  Low band on the register path: the ratio differs from 1 only for

@@ -498,8 +498,7 @@ static int do_bilinear_bwd(const void* dy, void* dx, int64_t B, int64_t Hi, int6
 #define MRFP_BWD_LAUNCH(VECV, KWV, ...)                                                                                     \
     hipLaunchKernelGGL((bilinear_bwd_kernel<T, VECV, KWV, ##__VA_ARGS__>), grid, dim3(kThreads), 0, st, (const T*)dy, (T*)dx, (int)B, \
                        (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)C, (int)ldi, ly, (int)ldd)
-    static int win = -1;          // MRFP_BILINEAR_WINDOW=0: every candidate column evaluated (A/B runs, the bit-identity test)
-    if (win < 0) { const char* e = getenv("MRFP_BILINEAR_WINDOW"); win = e ? atoi(e) : 1; }
+    static const int win = env_switch("MRFP_BILINEAR_WINDOW", 1);      // =0: every candidate column evaluated (A/B runs, the bit-identity test)
     if (vec) {
         if (kw <= 4) MRFP_BWD_LAUNCH(full, 4);
         else if (kw == 7 && win) MRFP_BWD_LAUNCH(full, 8, 5);          // 2x (the loss head, the class-score upsample): 5 of 8 slots

@@ -411,15 +411,14 @@ template <typename T>
 static int run_moments(const void* a, const void* b, float* M, float* sum_a, float* ws, int64_t B, int64_t HW, int64_t C,
                        hipStream_t st) {
     const WhitenGeom g = whiten_geom(B, HW, C);
-    static int mfma = -1;              // MRFP_WHITEN_MFMA=0: the VALU kernel for 16-bit activations too (A/B runs)
-    if (mfma < 0) { const char* e = getenv("MRFP_WHITEN_MFMA"); mfma = e ? atoi(e) : 1; }
+    static const int mfma = env_switch("MRFP_WHITEN_MFMA", 1);      // =0: the VALU kernel for 16-bit activations too (A/B runs)
     if constexpr (sizeof(T) == 2) {
         if (mfma) {
             // HALF a round of resident workgroups (2 of the 4 slots per CU x 256 CUs; MRFP_WHITEN_WGS) instead of the VALU kernel's ~2 048
             // short ones: pixel chunks of whole 32-pixel tiles, never more chunks than the workspace was sized for (g.nch).  Swept at
             // 16 x 256 x 192^2 (profiles/r05_whitening.md): 256 / 384 / 512 / 640 / 768 / 1024 / 2048 workgroups -> (x,x) 3.9 / 4.7 / 5.1 / 4.7 / 4.5 / 4.2 / 3.2 TB/s
-            static int wgs = -1;
-            if (wgs < 0) { const char* e = getenv("MRFP_WHITEN_WGS"); wgs = e ? atoi(e) : 2 * kCUs; if (wgs < 64) wgs = 2 * kCUs; }
+            static const int wgs_set = env_switch("MRFP_WHITEN_WGS", 2 * kCUs);
+            const int wgs = wgs_set < 64 ? 2 * kCUs : wgs_set;
             const int slabs = (int)((C + kMmSlab - 1) / kMmSlab);
             int64_t want = (a == b ? wgs : wgs * 3 / 4) / (B * slabs);      // (a != b: two register sets of two operands, 3 per CU)
             if (want < 1) want = 1;

@@ -325,11 +325,11 @@ class _BatchNormAct(torch.autograd.Function):
         if training:
             fused = getattr(x, "_mrfp_colstats", None)
             # (statistics weighted for a resize -- conv.STAT_RESIZE -- only serve the layer that applies exactly that resize)
-            if fused is not None and (fused[6] if len(fused) > 6 else None) is not plan:
+            if fused is not None and fused.resize_plan is not plan:
                 fused = None
-            if fused is not None and fused[2] == B * Ho * Wo and fused[0].numel() == fused[1] * 2 * C:
+            if fused is not None and fused.elements == B * Ho * Wo and fused.final.numel() == fused.final_count * 2 * C:
                 # the producing convolution already summed its output per channel in its epilogue
-                ws, nb_, nslab = fused[0], 1, fused[1]
+                ws, nb_, nslab = fused.final, 1, fused.final_count
             else:
                 nslab, ws = _stats_fwd(x, plan)
                 nb_ = B
@@ -508,18 +508,19 @@ def _in_plane_sums(x):
     #  0..255 -- and the fp32 parity criteria of the ill-conditioned fixture resolve the SUMMATION ORDER of its statistics:
     #  with the epilogue's sums the stem weight gradient of mrfp_c1 moved 0.37 from fp64 where 3x the reference's own fp32
     #  distance allows 0.19; bf16 storage rounds 10^4 times coarser than that)
-    if (IN_FUSED_STATS[0] and x.element_size() == 2 and fused is not None and len(fused) >= 6 and fused[2] == B * H * W and fused[5] < 0
-            and B * (-fused[5]) == fused[4] and fused[3].numel() >= fused[4] * 2 * C):
-        # the weight-stationary 3x3 kernel (csrc/conv_c64.hip) writes its statistics rows per IMAGE: -fused[5] rows each
+    usable = (IN_FUSED_STATS[0] and x.element_size() == 2 and fused is not None and fused.elements == B * H * W
+              and fused.rows.numel() >= fused.row_blocks * 2 * C)
+    rb = fused.block_rows if usable else 0
+    if rb < 0 and B * (-rb) == fused.row_blocks:
+        # the weight-stationary 3x3 kernel (csrc/conv_c64.hip) writes its statistics rows per IMAGE: -rb rows each
         IN_FUSED_HITS[0] += 1
-        return x, -fused[5], fused[3]
-    if (IN_FUSED_STATS[0] and x.element_size() == 2 and fused is not None and len(fused) >= 6 and fused[2] == B * H * W and fused[5] > 0
-            and (H * W) % fused[5] == 0 and B * ((H * W) // fused[5]) <= fused[4] and fused[3].numel() >= fused[4] * 2 * C):
+        return x, -rb, fused.rows
+    if rb > 0 and (H * W) % rb == 0 and B * ((H * W) // rb) <= fused.row_blocks:
         # the producing convolution summed its output per row block in its epilogue, and no row block straddles an image
         # (H*W is a multiple of the block height): its rows ARE the [B][blocks per image][2][C] partials of the plane sums --
         # the statistics pass over the convolution output disappears
         IN_FUSED_HITS[0] += 1
-        return x, (H * W) // fused[5], fused[3]
+        return x, (H * W) // rb, fused.rows
     if ps is not None:
         return x, ps[0], ps[1]
     nslab, ws = _stats_fwd(x, None)

@@ -242,7 +242,7 @@ def test_repeated_launches_are_bit_identical(shape):
         ys, sts = [], []
         for _ in range(6):
             y = conv.conv2d(x, w, None, 1, pad, dil)
-            sts.append(y._mrfp_colstats[0].clone())
+            sts.append(y._mrfp_colstats.final.clone())
             ys.append(y.clone())
         ref = F.conv2d(x.float(), w.bfloat16().float(), None, 1, pad, dil)
     assert torch.isfinite(ys[0].float()).all()
@@ -496,7 +496,7 @@ def test_row_reuse_kernels_in_subprocess():
         "    yd = conv.conv2d(xd, wd, None, 1, pad, pad); yd.backward(gy.cuda().bfloat16().contiguous(memory_format=torch.channels_last))\n"
         "    rel = lambda a, b: ((a.double().cpu()-b.double()).abs().max()/b.double().abs().max()).item()\n"
         "    assert rel(yd, yc) < 1e-2 and rel(xd.grad, xc.grad) < 1e-2 and rel(wd.grad, wc.grad) < 2e-2, ((B,Cin,H,W,Cout,pad), rel(yd,yc), rel(xd.grad,xc.grad), rel(wd.grad,wc.grad))\n"
-        "    st, cnt, npix = yd._mrfp_colstats[:3]; S = st.view(cnt, 2, -1).double().sum(0); yf = yd.detach().double()\n"
+        "    cs = yd._mrfp_colstats; st, cnt, npix = cs.final, cs.final_count, cs.elements; S = st.view(cnt, 2, -1).double().sum(0); yf = yd.detach().double()\n"
         "    assert npix == B*H*W and rel(S[0], yf.sum((0,2,3)).cpu()) < 1e-4 and rel(S[1], (yf*yf).sum((0,2,3)).cpu()) < 1e-4, ('stats', (B,Cin,H,W,Cout,pad))\n"
         "    with torch.no_grad():\n"
         "        ys = [conv.conv2d(xd.detach(), wd.detach(), None, 1, pad, pad).clone() for _ in range(4)]\n"
@@ -564,12 +564,12 @@ def _c64_check(case):
     assert relerr(yd, yc) < 1e-2
     if not has_bias:        # fused statistics: rows per image, and their total
         st = yd._mrfp_colstats
-        rows, nblk, rb = st[3], st[4], st[5]
+        rows, nblk, rb = st.rows, st.row_blocks, st.block_rows
         assert rb < 0 and B * (-rb) == nblk
         per = rows[:nblk * 2 * N].view(B, -rb, 2, N).double().sum(1).cpu()
         yf = yd.detach().double().cpu()
         assert relerr(per[:, 0], yf.sum((2, 3))) < 1e-4 and relerr(per[:, 1], (yf * yf).sum((2, 3))) < 1e-4
-        tot = st[0].view(st[1], 2, N).double().sum(0).cpu()
+        tot = st.final.view(st.final_count, 2, N).double().sum(0).cpu()
         assert relerr(tot[0], yf.sum((0, 2, 3))) < 1e-4
     yd.backward(gy.to(DEV, torch.bfloat16).contiguous(memory_format=torch.channels_last))
     assert relerr(xd.grad, xc.grad) < 1e-2 and relerr(wd.grad, wc.grad) < 2e-2
@@ -609,7 +609,7 @@ for (B, H, W, C, N) in shapes:
     for rep in range(2):
         x.grad = None; w.grad = None
         y, xs = conv.conv2d(x, w, None, 1, 0, 1, want_skip=True)
-        st = y._mrfp_colstats[0].clone()
+        st = y._mrfp_colstats.final.clone()
         torch.autograd.backward([y, xs], [gy, gs])          # dgrad with the skip gradient as its epilogue addend + wgrad
         key = '%dx%dx%dx%d->%d' % (B, H, W, C, N)
         rec = [h(y), h(st), h(x.grad), h(w.grad)]
@@ -679,7 +679,7 @@ def test_long_k_pointwise_kernel(case):
     yc = F.conv2d(x, w)
     assert relerr(yd, yc) < 1e-2
     st = yd._mrfp_colstats
-    tot = st[0].view(st[1], 2, N).double().sum(0).cpu()
+    tot = st.final.view(st.final_count, 2, N).double().sum(0).cpu()
     yf = yd.detach().double().cpu()
     # (statistics of the fp32 accumulators against sums of the bf16-rounded stored values: zero-mean rounding errors)
     assert relerr(tot[0], yf.sum((0, 2, 3))) < 5e-3 and relerr(tot[1], (yf * yf).sum((0, 2, 3))) < 1e-3

@@ -12,6 +12,7 @@ sys.path.insert(0, ROOT)
 
 
 def child():
+    import ctypes
     import torch
     from mrfp_amd import _lib, conv
     from mrfp_amd._lib import call, ptr, stream
@@ -30,8 +31,9 @@ def child():
             y = torch.empty_like(add)
             call("mrfp_conv_fwd", ptr(x), ptr(pk.wf), None, ptr(y), _lib.BF16, *geo, None, None, stream())
             out.append(y.clone())
-            nblk = int(L.mrfp_conv_stats_blocks(_lib.BF16, B, H, W, C, N, 1, 1, H, W, 1, 0, 0, 1, 1))
-            st = torch.zeros(int(L.mrfp_conv_stats_rows(nblk)) * 2 * N, dtype=torch.float32, device="cuda")
+            lay = (ctypes.c_int64 * 5)()
+            assert L.mrfp_conv_stats_layout(_lib.BF16, *geo, 0, lay) == 0
+            st = torch.zeros(lay[2] * 2 * N, dtype=torch.float32, device="cuda")
             y = torch.empty_like(add)
             call("mrfp_conv_fwd", ptr(x), ptr(pk.wf), None, ptr(y), _lib.BF16, *geo, None, ptr(st), stream())
             out += [y.clone(), st.clone()]
