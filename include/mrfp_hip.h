@@ -429,6 +429,36 @@ int mrfp_phot(const float* x, float* y, void* ws, const void* twH, const void* t
  * ------------------------------------------------------------------------------------------- */
 int mrfp_kmeans1d(const double* x, int64_t n, int k, int32_t* labels, double* centroids);
 
+/* ---------------------------------------------------------------------------------------------
+ * Depthwise 3x3 convolution, groups == C_in == C_out (reference network/Mobilenet.py ConvBNReLU with groups = hidden_dim,
+ * the dw layer of every InvertedResidual; csrc/conv_dw.hip).  padding = dilation (any dilation >= 1), stride 1 or 2:
+ * Ho = (H - 1) / stride + 1.  x, y, dx, dy: NHWC with channel pitch Cp (C rounded up to a 16-byte chunk); pad channels
+ * c >= C are written as zero.  w: the fp32 OIHW master weight [C][1][3][3]; bias: fp32 [C] or NULL.  Accumulation in fp32.
+ *   fwd:   y = dwconv(x, w) (+ bias).  ws (optional): BatchNorm partial statistics of the STORED y, float ws[B][nslab][2][Cp]
+ *          with nslab = mrfp_dwconv_nslab(dtype, B, Ho, Cp) -- the layout mrfp_bn_finalize reads (B*nslab rows).  Summed in a
+ *          fixed order: the rows are bitwise reproducible.
+ *   dgrad: dx[B,H,W,Cp] (gather form: each dx pixel collects the taps that read it; no atomics).
+ *   wgrad: dw[C][3][3] fp32 (written, not added), through per-workgroup slabs summed in a fixed order; ws holds
+ *          mrfp_dwconv_wgrad_ws_bytes(dtype, B, Ho, Cp) bytes.
+ * ------------------------------------------------------------------------------------------- */
+int64_t mrfp_dwconv_nslab(int dtype, int64_t B, int64_t Ho, int64_t Cp);
+int64_t mrfp_dwconv_wgrad_ws_bytes(int dtype, int64_t B, int64_t Ho, int64_t Cp);
+int mrfp_dwconv_fwd(const void* x, const float* w, const float* bias, void* y, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp,
+                    int64_t C, int64_t Ho, int64_t Wo, int64_t stride, int64_t dil, float* ws, void* stream);
+int mrfp_dwconv_dgrad(const void* dy, const float* w, void* dx, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp, int64_t C,
+                      int64_t Ho, int64_t Wo, int64_t stride, int64_t dil, void* stream);
+int mrfp_dwconv_wgrad(const void* x, const void* dy, float* dw, void* ws, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp,
+                      int64_t C, int64_t Ho, int64_t Wo, int64_t stride, int64_t dil, void* stream);
+
+/* BatchNorm apply + ReLU6 (reference Mobilenet.py ConvBNReLU: nn.ReLU6): y = clamp(x*A[c] + S[c], 0, 6) over the dense [npix][C]
+ * tensor, and the pass mask of the fp32 PRE-activation -- bit e & 7 of byte e >> 3 = (0 < x*A + S < 6), torch's hardtanh gate --
+ * in the format of mrfp_affine_fwd_relu_mask, so mrfp_stats_bwd_mask / mrfp_affine_bwd_mask consume it unchanged (16-bit, C % 8 == 0).
+ * Every activation dtype, any C. */
+int mrfp_affine_fwd_relu6_mask(const void* x, void* y, void* mask, int dtype, int64_t npix, int64_t C, const float* A, const float* S,
+                               void* stream);
+/* out = dy * mask bit, over n elements (the gate where the masked statistics / apply kernels do not apply: fp32). */
+int mrfp_mask_gate(const void* dy, const void* mask, void* out, int dtype, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -688,7 +688,8 @@ def pad_input_channels(x: torch.Tensor, dtype) -> torch.Tensor:
     return y
 
 
-def conv2d(x, weight, bias, stride, padding, dilation, phys_out: Optional[int] = None, want_skip: bool = False):
+def conv2d(x, weight, bias, stride, padding, dilation, phys_out: Optional[int] = None, want_skip: bool = False,
+           groups: int = 1):
     """x: [B,Cphys,H,W] channels-last (Cphys >= weight.shape[1], extra channels must be zero);
     returns [B,N,Ho,Wo], or the channel-padded [B,phys_out,Ho,Wo] buffer when phys_out is given.
     want_skip: returns (y, x_skip) -- see _Conv2d."""
@@ -703,6 +704,11 @@ def conv2d(x, weight, bias, stride, padding, dilation, phys_out: Optional[int] =
         x = xp
     if x.shape[1] < C:
         raise _lib.MrfpHipError("conv2d: input has %d channels, weight expects %d" % (x.shape[1], C))
+    if groups != 1 or (C == 1 and x.shape[1] > epc):
+        # a grouped weight ([N, C/groups, R, S]; depthwise: [C, 1, 3, 3]) would run here as a dense convolution over the first
+        # input channels only: refuse it (depthwise 3x3 runs on ops.depthwise_conv2d)
+        raise _lib.MrfpHipError("conv2d: weight %s over an input of %d channels (groups=%d) is a grouped convolution; the implicit-GEMM "
+                                "path is dense only" % (tuple(weight.shape), x.shape[1], groups))
     Nphys = phys_out if phys_out is not None else _round_up(N, epc)
     _LAST_STATS[0] = None
     if _JOIN_QUEUED[0] and not _in_backward():

@@ -62,14 +62,46 @@ class HipInstanceNorm2d(nn.InstanceNorm2d):
         return self.fused(x)
 
 
-class HipConv2d(nn.Conv2d):
-    """nn.Conv2d (OIHW fp32 master weight = checkpoint ABI) on the HIP implicit-GEMM kernels."""
+class HipLocalBatchNorm2d(HipBatchNorm2d):
+    """nn.BatchNorm2d whose statistics are never synchronised across ranks (the reference's MobileNetV2 builds its norms as
+    plain nn.BatchNorm2d, network/Mobilenet.py, not Norm2d), optionally followed by ReLU6 in the same apply pass."""
+
+    def fused(self, x, *, act=None):
+        training = self.training or (self.running_mean is None)
+        if training and self.num_batches_tracked is not None:
+            self._nbt_pending += 1
+        return ops.local_batch_norm_act(x, self.weight, self.bias,
+                                        self.running_mean if self.track_running_stats else None,
+                                        self.running_var if self.track_running_stats else None,
+                                        training=training, momentum=self.momentum, eps=self.eps, act=act)
 
     def forward(self, x):
+        return self.fused(x)
+
+
+class HipConv2d(nn.Conv2d):
+    """nn.Conv2d (OIHW fp32 master weight = checkpoint ABI) on the HIP implicit-GEMM kernels; a depthwise 3x3
+    (groups == in_channels == out_channels) on the depthwise kernels.  Any other grouping raises."""
+
+    def _is_depthwise(self):
+        if self.groups == 1:
+            return False
+        if self.groups == self.in_channels == self.out_channels and tuple(self.kernel_size) == (3, 3):
+            return True
+        raise ops._lib.MrfpHipError(
+            "HipConv2d: grouped convolution in=%d out=%d kernel=%s groups=%d (weight %s) is not supported; only depthwise 3x3 "
+            "(groups == in_channels == out_channels) is" % (self.in_channels, self.out_channels, tuple(self.kernel_size),
+                                                            self.groups, tuple(self.weight.shape)))
+
+    def forward(self, x):
+        if self._is_depthwise():
+            return ops.depthwise_conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
         return ops.conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
 
     def forward_skip(self, x):
         """(conv(x), x_skip): x_skip aliases x; its gradient is folded into this conv's dgrad launch."""
+        if self._is_depthwise():
+            raise ops._lib.MrfpHipError("HipConv2d.forward_skip: not available for a depthwise convolution")
         return ops.conv2d_skip(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
 
 

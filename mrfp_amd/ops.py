@@ -1542,3 +1542,202 @@ def fourier_amplitude_mix(x, perm, radius, lam=1.0, high=False):
     """Per-(b,c) plane: swap/blend the spectral amplitude inside (low band) or outside (high band) `radius`
     with the partner sample perm[b], keep the phase."""
     return _FourierMix.apply(x, perm, radius, lam, high)
+
+
+# ------------------------------------------------------------------------------------------
+# MobileNetV2 layers: depthwise 3x3 convolution, BatchNorm (+ReLU6) that is never synchronised
+# ------------------------------------------------------------------------------------------
+_DW_LAST_STATS = [None]      # handed from _DepthwiseConv2d.forward to depthwise_conv2d() (autograd re-wraps the output tensor)
+
+
+class _DepthwiseConv2d(torch.autograd.Function):
+    """nn.Conv2d(C, C, 3, stride, padding=dilation, dilation, groups=C) (reference network/Mobilenet.py ConvBNReLU with
+    groups = hidden_dim) on csrc/conv_dw.hip.  x: [B,Cp,H,W] channels-last, Cp = C rounded up to a 16-byte chunk.  The weight
+    gradient runs inline in backward (slabs + a fixed-order sum: bitwise reproducible); it does not join the deferred wgrad
+    stream of the MFMA convolutions."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, dil, want_stats):
+        B, Cp, H, W = x.shape
+        C = weight.shape[0]
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        w32 = weight.detach().float().contiguous()
+        b32 = _f32(bias)
+        y = empty_cl(B, Cp, Ho, Wo, x.dtype, x.device)
+        ws = None
+        if want_stats:
+            nslab = int(_lib.lib().mrfp_dwconv_nslab(dt(x), B, Ho, Cp))
+            ws = torch.empty(B * nslab * 2 * Cp, dtype=torch.float32, device=x.device)
+        call("mrfp_dwconv_fwd", ptr(x), ptr(w32), ptr(b32), ptr(y), dt(x), B, H, W, Cp, C, Ho, Wo, stride, dil, ptr(ws), stream())
+        if ws is not None:
+            from .conv import ConvStats
+            _DW_LAST_STATS[0] = ConvStats(ws, B * nslab, B * Ho * Wo, ws, B * nslab, 0, None)
+        ctx.save_for_backward(x, w32)
+        ctx.geom = (B, Cp, C, H, W, Ho, Wo, stride, dil)
+        ctx.wparam, ctx.has_bias = weight, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w32 = ctx.saved_tensors
+        B, Cp, C, H, W, Ho, Wo, stride, dil = ctx.geom
+        dy = _chk(dy, "dy")
+        if dy.shape[1] != Cp:            # the caller saw the logical C channels of a padded output: back to the channel pitch
+            dp = zeros_cl(B, Cp, Ho, Wo, dy.dtype, dy.device)
+            dp[:, :dy.shape[1]] = dy
+            dy = dp
+        if dy.dtype != x.dtype:
+            raise _lib.MrfpHipError("depthwise_conv2d: gradient dtype %s differs from the activation dtype %s" % (dy.dtype, x.dtype))
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = empty_cl(B, Cp, H, W, dy.dtype, dy.device)
+            call("mrfp_dwconv_dgrad", ptr(dy), ptr(w32), ptr(dx), dt(dy), B, H, W, Cp, C, Ho, Wo, stride, dil, stream())
+        if ctx.needs_input_grad[1]:
+            nbytes = int(_lib.lib().mrfp_dwconv_wgrad_ws_bytes(dt(x), B, Ho, Cp))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+            sink = grad_sink(ctx.wparam)
+            out = sink if sink is not None else torch.empty((C, 1, 3, 3), dtype=torch.float32, device=x.device)
+            call("mrfp_dwconv_wgrad", ptr(x), ptr(dy), ptr(out), ptr(ws), dt(x), B, H, W, Cp, C, Ho, Wo, stride, dil, stream())
+            if sink is not None:
+                notify_grad(ctx.wparam)
+            else:
+                dw = out.to(ctx.wparam.dtype)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            nslab, sws = _stats_fwd(dy, None)
+            out = torch.empty(4 * Cp, dtype=torch.float32, device=dy.device)
+            call("mrfp_bn_finalize", ptr(sws), B, nslab, B * Ho * Wo, Cp, None, None, 0.0, 0.0, None, None,
+                 ptr(out[:Cp]), ptr(out[Cp:2 * Cp]), ptr(out[2 * Cp:3 * Cp]), ptr(out[3 * Cp:]), stream())
+            db = out[:C] * float(B * Ho * Wo)            # column mean * count = column sum
+        return dx, dw, db, None, None, None
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def depthwise_conv2d(x, weight, bias, stride, padding, dilation):
+    """F.conv2d(x, weight, bias, stride, padding, dilation, groups=C) for weight [C,1,3,3], padding == dilation, stride 1 or 2.
+    Returns [B,C,Ho,Wo] channels-last; a bias-free convolution tags its output with the BatchNorm partial statistics its kernel
+    wrote (y._mrfp_colstats, as the MFMA convolutions do), so the BatchNorm behind it skips its statistics pass."""
+    from . import conv
+    st, dl, pd = _pair(stride), _pair(dilation), _pair(padding)
+    C = weight.shape[0]
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (1, 3, 3) or st[0] != st[1] or st[0] not in (1, 2) \
+            or dl[0] != dl[1] or dl[0] < 1 or pd != dl:
+        raise _lib.MrfpHipError("depthwise_conv2d: weight %s stride %s padding %s dilation %s is not a depthwise 3x3 with padding = "
+                                "dilation and stride 1 or 2" % (tuple(weight.shape), st, pd, dl))
+    x = _chk(x)
+    epc = conv._epc(x.dtype)
+    Cp = conv._round_up(C, epc)
+    if x.shape[1] != Cp:
+        if x.shape[1] != C:
+            raise _lib.MrfpHipError("depthwise_conv2d: input has %d channels, weight %s expects %d" % (x.shape[1], tuple(weight.shape), C))
+        xp = zeros_cl(x.shape[0], Cp, x.shape[2], x.shape[3], x.dtype, x.device)     # chunk-pad the channels (copy)
+        xp[:, :C] = x
+        x = xp
+    _DW_LAST_STATS[0] = None
+    want_stats = bias is None and conv.FUSE_STATS[0] and Cp == C
+    y = _DepthwiseConv2d.apply(x, weight, bias, st[0], dl[0], want_stats)
+    stats, _DW_LAST_STATS[0] = _DW_LAST_STATS[0], None
+    if stats is not None:
+        y._mrfp_colstats = stats          # consumed by the BatchNorm behind it (statistics pass skipped)
+    if Cp != C:
+        y = y[:, :C].contiguous(memory_format=CL)
+    return y
+
+
+RELU6_GATE_HITS = [0]      # ReLU6 backward passes that gated with mrfp_mask_gate (fp32 / channel counts off the 8-chunk; tests)
+
+
+class _LocalBatchNormAct(torch.autograd.Function):
+    """y = act(BN(x)) for act in (None, 'relu6'), statistics over this process's batch only: the plain nn.BatchNorm2d of the
+    reference's MobileNetV2 (network/Mobilenet.py: norm_layer = nn.BatchNorm2d, never Norm2d / SyncBatchNorm).
+    ReLU6 (nn.ReLU6 = hardtanh(0, 6)): the apply pass writes a 1-bit pass mask of the fp32 PRE-activation, 0 < x*A + S < 6 -- the
+    gate torch applies -- and backward gates dy with it (a rounded 16-bit output cannot tell 5.99 from 6)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, training, momentum, eps, act):
+        x = _chk(x)
+        B, C, H, W = x.shape
+        dev = x.device
+        w32, b32 = _f32(weight), _f32(bias)
+        coef = torch.empty(4 * C, dtype=torch.float32, device=dev)
+        mean, invstd, A, S = coef[0:C], coef[C:2 * C], coef[2 * C:3 * C], coef[3 * C:4 * C]
+        if training:
+            fused = getattr(x, "_mrfp_colstats", None)
+            if fused is not None and fused.resize_plan is None and fused.elements == B * H * W \
+                    and fused.final.numel() == fused.final_count * 2 * C:
+                ws, nb_, nslab = fused.final, 1, fused.final_count
+            else:
+                nslab, ws = _stats_fwd(x, None)
+                nb_ = B
+            call("mrfp_bn_finalize", ptr(ws), nb_, nslab, B * H * W, C, ptr(w32), ptr(b32), float(eps), float(momentum),
+                 ptr(running_mean), ptr(running_var), ptr(mean), ptr(invstd), ptr(A), ptr(S), stream())
+        else:
+            call("mrfp_bn_eval_coef", C, ptr(w32), ptr(b32), ptr(running_mean), ptr(running_var), float(eps), ptr(A), ptr(S), stream())
+            if x.requires_grad or (weight is not None and weight.requires_grad):
+                mean.copy_(running_mean)
+                torch.rsqrt(running_var.float() + eps, out=invstd)
+        mask = None
+        if act == "relu6":
+            y = empty_cl(B, C, H, W, x.dtype, dev)
+            mask = torch.empty((B * H * W * C + 7) // 8, dtype=torch.uint8, device=dev)
+            call("mrfp_affine_fwd_relu6_mask", ptr(x), ptr(y), ptr(mask), dt(x), B * H * W, C, ptr(A), ptr(S), stream())
+        else:
+            y = _affine_fwd(x, None, A, S, False, False, None)
+        ctx.training = training
+        ctx.wparam, ctx.bparam = weight, bias
+        ctx.save_for_backward(x, mask, w32, mean, invstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mask, w32, mean, invstd = ctx.saved_tensors
+        dy = _chk(dy, "dy")
+        B, C, H, W = x.shape
+        masked = mask is not None and x.element_size() == 2 and C % 8 == 0 and dy.dtype == x.dtype
+        if mask is not None and not masked:
+            g = torch.empty_like(dy, memory_format=CL)
+            call("mrfp_mask_gate", ptr(dy), ptr(mask), ptr(g), dt(dy), dy.numel(), stream())
+            dy = g
+            RELU6_GATE_HITS[0] += 1
+        if masked:
+            nslab, ws = _stats_ws(B, H, C, x.device)
+            call("mrfp_stats_bwd_mask", ptr(dy), ptr(x), ptr(mask), ptr(mean), 0, dt(x), B, H, W, C, ptr(ws), stream())
+        else:
+            nslab, ws = _stats_bwd(dy, x, None, mean, False, None)
+        out = torch.empty(5 * C, dtype=torch.float32, device=dy.device)
+        dw, db, P, Q, R = (out[i * C:(i + 1) * C] for i in range(5))
+        sw = grad_sink(ctx.wparam) if ctx.needs_input_grad[1] else None
+        sb = grad_sink(ctx.bparam) if ctx.needs_input_grad[2] else None
+        call("mrfp_bn_bwd_finalize", ptr(ws), B, nslab, B * H * W, C, ptr(w32), ptr(mean), ptr(invstd),
+             ptr(sw if sw is not None else dw), ptr(sb if sb is not None else db), ptr(P), ptr(Q), ptr(R), stream())
+        if not ctx.training:
+            Q.zero_()
+            R.zero_()
+        if masked:
+            dx = empty_cl(B, C, H, W, dy.dtype, dy.device)
+            call("mrfp_affine_bwd_mask", ptr(dy), ptr(x), ptr(mask), ptr(dx), None, dt(dy), B, H, W, C, ptr(P), ptr(Q), ptr(R), 0,
+                 stream())
+        else:
+            dx, _ = _affine_bwd(dy, x, None, P, Q, R, False, None, False, x)
+        if sw is not None:
+            notify_grad(ctx.wparam)
+            dw = None
+        if sb is not None:
+            notify_grad(ctx.bparam)
+            db = None
+        return dx, dw, db, None, None, None, None, None, None
+
+
+def local_batch_norm_act(x, weight, bias, running_mean, running_var, *, training, momentum=0.1, eps=1e-5, act=None):
+    """BatchNorm over this process's batch (never synchronised across ranks) followed by `act`: None or 'relu6'."""
+    if act not in (None, "relu6"):
+        raise _lib.MrfpHipError("local_batch_norm_act: act must be None or 'relu6' (got %r)" % (act,))
+    return _LocalBatchNormAct.apply(x, weight, bias, running_mean, running_var, bool(training), momentum, eps, act)
+
+
+def batch_norm_relu6(x, weight, bias, running_mean, running_var, *, training, momentum=0.1, eps=1e-5):
+    """clamp(BN(x), 0, 6): nn.BatchNorm2d -> nn.ReLU6 (reference network/Mobilenet.py ConvBNReLU)."""
+    return local_batch_norm_act(x, weight, bias, running_mean, running_var, training=training, momentum=momentum, eps=eps,
+                                act="relu6")
