@@ -459,6 +459,32 @@ int mrfp_affine_fwd_relu6_mask(const void* x, void* y, void* mask, int dtype, in
 /* out = dy * mask bit, over n elements (the gate where the masked statistics / apply kernels do not apply: fp32). */
 int mrfp_mask_gate(const void* dy, const void* mask, void* out, int dtype, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Test-time augmentation of the eval path (build-defined: the reference scores one forward per image, main.py:887-913).
+ *
+ * mrfp_prob_accum: ONE launch per (scale, flip, window) variant.  Replaces the stock chain
+ *   acc[:, y0:y0+hd, x0:x0+wd] += weight * softmax(F.interpolate(flip(logits), (hd, wd), 'bilinear', align_corners=True), 1);
+ *   cnt[:, y0:y0+hd, x0:x0+wd] += weight
+ * (five or six passes over a [B,NC,hd,wd] fp32 tensor).  logits[B,hs,ws,ld]: low-resolution class scores in `dtype`, ld >= NC
+ * channels per pixel (any pitch; 16-byte multiples are read with 16-byte loads), NC <= 32.  acc[B,H,W,NC], cnt[B,H,W]: fp32,
+ * dense, read-modify-written inside the rectangle and untouched outside.  Destination pixel (y, x) of the rectangle takes the
+ * align_corners=True sample of the hs x ws map at the position it has in an hd x wd resize (the arithmetic of mrfp_bilinear_fwd;
+ * hs == hd and ws == wd: the identity); flip != 0 mirrors the source column (ws - 1 - column), i.e. samples flip(logits).
+ * Softmax in fp32, max-subtracted.  Every destination pixel is owned by one lane, no atomics: launches on one stream give a
+ * bitwise reproducible accumulator.
+ *
+ * mrfp_acc_argmax_hist: the closing pass.  Replaces np.argmax(acc, -1) + metrics.fast_hist (reference metrics.py:122-126) on the
+ * host.  acc[npix][NC] fp32; hist / target / pred exactly as mrfp_argmax_hist (first maximum wins; labels outside 0..NC-1 are
+ * ignored; hist is added to; pred uint8 [npix], optional).  Dividing by cnt does not change the arg-max and is not done.  A pixel
+ * that no variant covered (cnt == 0) is the caller's error: with cnt and uncovered (int64[1], added to) given, such pixels are
+ * COUNTED there so that the caller can raise; they are not hidden (their arg-max is that of whatever acc holds).
+ * ------------------------------------------------------------------------------------------- */
+int mrfp_prob_accum(const void* logits, int dtype, int64_t B, int64_t hs, int64_t ws, int64_t ld, float* acc, float* cnt,
+                    int64_t H, int64_t W, int64_t NC, int64_t y0, int64_t x0, int64_t hd, int64_t wd, int flip, float weight,
+                    void* stream);
+int mrfp_acc_argmax_hist(const float* acc, const float* cnt, const int64_t* target, int64_t npix, int64_t NC, int64_t* hist,
+                         uint8_t* pred, int64_t* uncovered, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -291,15 +291,20 @@ class _DeepLabBase(nn.Module):
         c = self.criterion
         return isinstance(c, nn.CrossEntropyLoss) and c.weight is None and c.reduction == "mean" and c.label_smoothing == 0.0
 
-    def _head(self, dec1, size, gts, training):
+    def _head(self, dec1, size, gts, training, low_res=False):
         """final2 (1x1 conv + bias) -> bilinear upsample to the input size -> loss or logits (reference
         deepv3.py:360-367).  The low-resolution class scores live in a 32-channel padded buffer so the conv stays
         chunk-aligned; in training with the plain CE criterion the upsample and the loss are one kernel and the
-        full-resolution logits are never written."""
+        full-resolution logits are never written.  low_res (eval only): return that padded low-resolution buffer
+        [B,32,h/4,w/4] itself, in the activation dtype -- harness.evaluate_tta resizes it inside ops.prob_accum."""
         f2 = self.final2[0]
         nc = f2.out_channels
         pitch = (nc + 31) // 32 * 32
         dec2 = ops.conv2d(dec1, f2.weight, f2.bias, f2.stride, f2.padding, f2.dilation, phys_out=pitch)
+        if low_res:
+            if training:
+                raise ValueError("low_res is an eval-path option (training=False)")
+            return dec2
         if training and cfg.MODEL.FUSE_UPSAMPLE_CE and self._plain_ce():
             return ops.upsample_cross_entropy(dec2, gts, size, nc, self.criterion.ignore_index)
         main_out = ops.upsample_bilinear(dec2, size, channels=nc)
@@ -407,7 +412,9 @@ class MRFPPlus(_DeepLabBase):
             self._tap("hrfp%d" % i, t)
         return dec, t, xp_alias
 
-    def forward(self, x, gts=None, training=True):
+    def forward(self, x, gts=None, training=True, low_res=False):
+        if low_res and training:
+            raise ValueError("low_res is an eval-path option (training=False)")
         p, p2, p3 = self.rng.toggles()
         h, w = x.shape[2], x.shape[3]
         o1, npp, o2 = (training == True and p < 0.5), (training == True and p2 < 0.5), (training == True and p3 < 0.5)  # noqa: E712
@@ -461,7 +468,7 @@ class MRFPPlus(_DeepLabBase):
             if cfg.MODEL.COMMUTE_O2:
                 return self._head_o2(dec1, OCout_dec, (h, w), gts, training)
             dec1 = ops.upsample_bilinear(dec1, (int(h / 2), int(w / 2)), addend=OCout_dec)   # one fused pass
-        return self._head(dec1, (h, w), gts, training)
+        return self._head(dec1, (h, w), gts, training, low_res)
 
 
 class simpleDeepV3Plus(_DeepLabBase):
@@ -480,7 +487,7 @@ class simpleDeepV3Plus(_DeepLabBase):
         self._build_trunk_and_head(num_classes, trunk, wt_layer)
         self._init_head()
 
-    def forward(self, x, gts=None, training=False):
+    def forward(self, x, gts=None, training=False, low_res=False):
         h, w = x.shape[2], x.shape[3]
         t, w_arr = self._stem(x)
         x_tuple = self.layer1([t, w_arr])
@@ -489,4 +496,4 @@ class simpleDeepV3Plus(_DeepLabBase):
         dec0_up = self.bot_aspp(self.aspp(x_tuple[0]))
         dec0_fine = self.bot_fine(low_level)
         dec1 = self._final1(ops.concat_upsample(dec0_fine, dec0_up, low_level.shape[2:], cfg.MODEL.DECODER_PAD))    # cat([dec0_fine, Upsample(dec0_up)], 1)
-        return self._head(dec1, (h, w), gts, training)
+        return self._head(dec1, (h, w), gts, training, low_res)

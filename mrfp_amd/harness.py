@@ -468,6 +468,132 @@ def evaluate(model, batches, num_classes=19):
 
 
 # ------------------------------------------------------------------------------------------
+# multi-scale / flipped / sliding-window evaluation (build-defined: the reference scores one forward per image)
+# ------------------------------------------------------------------------------------------
+def _window_starts(size: int, win: int, stride: int):
+    if size <= win:
+        return [0]
+    starts = list(range(0, size - win, stride))
+    starts.append(size - win)                 # the last window is shifted back so that it ends at the border
+    return starts
+
+
+def window_grid(height: int, width: int, window=None, stride=None):
+    """Sliding-window rectangles (y, x, h, w) over a height x width image, rows outer.  Windows start on a grid of `stride`
+    (default: two thirds of the window, rounded up); the last row / column of windows is shifted back so that it ends at the image
+    border: every pixel is covered, no window leaves the image, nothing is padded.  A dimension not larger than the window is one
+    window of the image's own size.  window=None: the whole image."""
+    height, width = int(height), int(width)
+    if height < 1 or width < 1:
+        raise ValueError("empty image %d x %d" % (height, width))
+    if window is None:
+        return [(0, 0, height, width)]
+    wh, ww = int(window[0]), int(window[1])
+    if wh < 1 or ww < 1:
+        raise ValueError("window must be positive, got %r" % (window,))
+    sy, sx = (-(-2 * wh // 3), -(-2 * ww // 3)) if stride is None else (int(stride[0]), int(stride[1]))
+    if sy < 1 or sx < 1:
+        raise ValueError("stride must be positive, got %r" % (stride,))
+    if sy > wh or sx > ww:
+        raise ValueError("stride %r larger than the window %r would leave pixels uncovered" % ((sy, sx), (wh, ww)))
+    hh, hw = min(wh, height), min(ww, width)
+    return [(y, x, hh, hw) for y in _window_starts(height, wh, sy) for x in _window_starts(width, ww, sx)]
+
+
+def window_dest_rect(win, src_size, dst_size):
+    """The rectangle (y0, x0, hd, wd) a window (y, x, h, w) of a src_size = (Hs, Ws) image has in the dst_size = (Hd, Wd)
+    accumulator.  Rounding rule, in integer arithmetic: the start is rounded DOWN, y0 = floor(y * Hd / Hs), and the end UP,
+    y0 + hd = ceil((y + h) * Hd / Hs) (columns alike).  Windows that cover the source therefore cover the destination without a
+    gap (overlaps are allowed and weighted by cnt), and for Hs == Hd the rectangle is the window itself."""
+    y, x, h, w = win
+    (Hs, Ws), (Hd, Wd) = src_size, dst_size
+    y0, y1 = (y * Hd) // Hs, -(-((y + h) * Hd) // Hs)
+    x0, x1 = (x * Wd) // Ws, -(-((x + w) * Wd) // Ws)
+    return y0, x0, y1 - y0, x1 - x0
+
+
+def _check_tta_args(scales, window, stride):
+    scales = tuple(float(s) for s in scales)
+    if not scales:
+        raise ValueError("scales must not be empty")
+    if any(not (s > 0.0) or math.isinf(s) for s in scales):
+        raise ValueError("scales must be positive and finite, got %r" % (scales,))
+    if stride is not None and window is None:
+        raise ValueError("stride given without window")
+    if window is not None:
+        window_grid(max(1, int(window[0])), max(1, int(window[1])), window, stride)      # raises on a bad window / stride
+    return scales
+
+
+def tta_variants(height, width, dst_size, scales, flip, window, stride):
+    """The (scale, scaled size, flipped, window, destination rectangle) list of one image, in issue order: what evaluate_tta runs
+    and what a restatement has to replay.  Scaled size = (round(height * s), round(width * s)), at least 1."""
+    out = []
+    for s in scales:
+        hs, ws = (height, width) if s == 1.0 else (max(1, int(round(height * s))), max(1, int(round(width * s))))
+        for win in window_grid(hs, ws, window, stride):
+            rect = window_dest_rect(win, (hs, ws), dst_size)
+            for f in ((False, True) if flip else (False,)):
+                out.append((s, (hs, ws), f, win, rect))
+    return out
+
+
+@torch.no_grad()
+def evaluate_tta(model, batches, num_classes=19, scales=(1.0,), flip=False, window=None, stride=None, resize_to_label=False,
+                 on_variant=None):
+    """evaluate() with test-time augmentation: class PROBABILITIES averaged over image scales, a horizontal flip and overlapping
+    windows, then arg-max + confusion histogram -> (hist, mIoU, dropped), the triple evaluate() returns.
+
+    Per image and per scale s the input is resized to round(H*s) x round(W*s) with the bilinear align_corners operator (s == 1.0: used
+    as it is), cut into window_grid(...) windows (window=None: one forward of the whole scaled image), and every window is forwarded
+    once, and once more horizontally mirrored with flip=True.  The model returns its LOW-resolution class scores
+    (model(x, training=False, low_res=True)); ops.prob_accum resizes them (the bilinear align_corners resize the head itself ends
+    with) straight into the window's rectangle of a full-size fp32 accumulator, soft-maxes and adds: the full-size logits are never
+    written.  For s != 1 the rectangle is the window mapped back through the scale with window_dest_rect's rule (start rounded
+    down, end rounded up).  ops.acc_argmax_hist closes each image.  Every variant has weight 1.
+
+    resize_to_label=False drops an image whose size differs from its label's, as evaluate() and the reference do (main.py:894,
+    910-912); True scores it at the label's size instead.  Histograms are summed over the data-parallel ranks as in evaluate();
+    `dropped` stays per rank.  on_variant(image index, variant, low-resolution scores): measurement / test hook."""
+    from . import metrics, ops
+    scales = _check_tta_args(scales, window, stride)
+    model.eval()
+    dev = next(model.parameters()).device
+    hist, dropped = None, 0
+    uncovered = torch.zeros(1, dtype=torch.int64, device=dev)
+    for idx, (img, label) in enumerate(batches):
+        H, W = int(img.shape[2]), int(img.shape[3])
+        Hd, Wd = int(label.shape[1]), int(label.shape[2])
+        if (H, W) != (Hd, Wd) and not resize_to_label:
+            dropped += 1
+            continue
+        B = int(img.shape[0])
+        acc = torch.zeros(B, Hd, Wd, num_classes, dtype=torch.float32, device=img.device)
+        cnt = torch.zeros(B, Hd, Wd, dtype=torch.float32, device=img.device)
+        scaled = {}
+        for var in tta_variants(H, W, (Hd, Wd), scales, flip, window, stride):
+            s, size, f, (y, x, h, w), rect = var
+            if size not in scaled:
+                scaled = {size: img if size == (H, W) else ops.upsample_bilinear(img, size)}     # one scaled copy alive at a time
+            crop = scaled[size][:, :, y:y + h, x:x + w]
+            if f:
+                crop = torch.flip(crop, dims=(3,))
+            low = model(crop, training=False, low_res=True)
+            if on_variant is not None:
+                on_variant(idx, var, low)
+            ops.prob_accum(low, acc, cnt, rect, flip=f)
+        hist, _ = ops.acc_argmax_hist(acc, cnt, label, hist, uncovered=uncovered)
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        if hist is None:                              # this rank dropped all of its batches: still take part
+            hist = torch.zeros(num_classes, num_classes, dtype=torch.int64, device=dev)
+        dist.all_reduce(hist)
+    if int(uncovered.item()) != 0:
+        raise _lib.MrfpHipError("evaluate_tta: %d pixels were covered by no window" % int(uncovered.item()))
+    h = hist.cpu().numpy() if hist is not None else None
+    return h, (metrics.miou_from_hist(h) if h is not None else 0.0), dropped
+
+
+# ------------------------------------------------------------------------------------------
 # checkpoints in the reference's format (reference main.py:867-869, 884-886)
 # ------------------------------------------------------------------------------------------
 def save_checkpoint(path, model, epoch, optimizer=None):

@@ -175,7 +175,15 @@ class DeepV3Plus(_DeepLabBase):
             return ops.cross_entropy(aux_out, aux_gts, c.ignore_index)
         return c(aux_out.float(), aux_gts)
 
-    def forward(self, x, gts=None, aux_gts=None, img_gt=None, visualize=False, cal_covstat=False, apply_wtloss=True):
+    def forward(self, x, gts=None, aux_gts=None, img_gt=None, visualize=False, cal_covstat=False, apply_wtloss=True,
+                training=None, low_res=False):
+        """training / low_res: the keywords harness.evaluate / harness.evaluate_tta call every model with.  The mode is the
+        module's own (self.training, as in the reference); `training`, when given, has to agree with it.  low_res (eval only):
+        the head's padded low-resolution class scores instead of the full-size logits (deepv3._DeepLabBase._head)."""
+        if training is not None and bool(training) != self.training:
+            raise ValueError("training=%r contradicts the module's mode (call .train() / .eval())" % (training,))
+        if low_res and self.training:
+            raise ValueError("low_res is an eval-path option")
         if cal_covstat:
             x = torch.cat(x, dim=0)
         h, w = x.shape[2], x.shape[3]
@@ -198,7 +206,7 @@ class DeepV3Plus(_DeepLabBase):
                 if visualize:
                     return_loss.append([])
             return return_loss
-        main_out = self._head(dec1, (h, w), None, False)
+        main_out = self._head(dec1, (h, w), None, False, low_res)
         if visualize:
             return main_out, []
         return main_out

@@ -976,6 +976,68 @@ def argmax_hist(logits, target, hist: Optional[torch.Tensor] = None, want_pred=F
 
 
 # ------------------------------------------------------------------------------------------
+# eval: test-time-augmentation accumulator (one launch per scale / flip / window variant) and its closing pass
+# ------------------------------------------------------------------------------------------
+def _chk_acc(acc, cnt, who):
+    for t, name, nd in ((acc, "acc", 4), (cnt, "cnt", 3)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.MrfpHipError("%s: %s must be a GPU tensor: the HIP path has no CPU fallback" % (who, name))
+        if t.dtype != torch.float32 or t.dim() != nd or not t.is_contiguous():
+            raise _lib.MrfpHipError("%s: %s must be a contiguous float32 %d-D tensor (got %s %s)"
+                                    % (who, name, nd, t.dtype, tuple(t.shape)))
+    if tuple(cnt.shape) != tuple(acc.shape[:3]) or cnt.device != acc.device:
+        raise _lib.MrfpHipError("%s: cnt %s does not match acc %s" % (who, tuple(cnt.shape), tuple(acc.shape)))
+    if not 1 <= acc.shape[3] <= 32:
+        raise _lib.MrfpHipError("%s: 1 <= classes <= 32 (acc %s)" % (who, tuple(acc.shape)))
+
+
+def prob_accum(logits, acc, cnt, rect=None, flip=False, weight=1.0):
+    """acc[:, y0:y0+hd, x0:x0+wd, :] += weight * softmax(bilinear_align_corners(flip(logits), (hd, wd))) and
+    cnt[:, y0:y0+hd, x0:x0+wd] += weight, in one pass over the rectangle (mrfp_prob_accum).
+
+    logits: class scores [B,ld,hs,ws] in NHWC storage (as the head produces them; ld >= classes, pad channels ignored), float32 /
+    bfloat16 / float16.  acc: float32 [B,H,W,classes] dense (class-minor), cnt: float32 [B,H,W]; both updated in place.
+    rect = (y0, x0, hd, wd), default the whole accumulator plane.  flip: the scores come from a horizontally mirrored input."""
+    _chk_acc(acc, cnt, "prob_accum")
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda or logits.device != acc.device:
+        raise _lib.MrfpHipError("prob_accum: logits must live on the accumulator's GPU: the HIP path has no CPU fallback")
+    if logits.dim() != 4 or not logits.is_contiguous(memory_format=CL):
+        raise _lib.MrfpHipError("prob_accum: logits must be a 4-D tensor in channels_last (NHWC) storage, got %s strides %s"
+                                % (tuple(logits.shape), tuple(logits.stride())))
+    B, ld, hs, ws = logits.shape
+    Ba, H, W, NC = acc.shape
+    if B != Ba or ld < NC:
+        raise _lib.MrfpHipError("prob_accum: logits %s do not fit acc %s" % (tuple(logits.shape), tuple(acc.shape)))
+    y0, x0, hd, wd = (0, 0, H, W) if rect is None else (int(v) for v in rect)
+    if y0 < 0 or x0 < 0 or hd < 1 or wd < 1 or y0 + hd > H or x0 + wd > W:
+        raise _lib.MrfpHipError("prob_accum: rectangle %s leaves the %d x %d accumulator" % ((y0, x0, hd, wd), H, W))
+    call("mrfp_prob_accum", ptr(logits), dt(logits), B, hs, ws, ld, ptr(acc), ptr(cnt), H, W, NC, y0, x0, hd, wd,
+         1 if flip else 0, float(weight), stream())
+
+
+def acc_argmax_hist(acc, cnt, target, hist: Optional[torch.Tensor] = None, want_pred=False, uncovered=None):
+    """arg-max over the classes of a prob_accum accumulator + confusion histogram (mrfp_acc_argmax_hist): returns (hist int64
+    [classes,classes] on the device, added to when given; pred uint8 [B,H,W] or None), as argmax_hist.  A pixel with cnt == 0 is
+    the caller's error; `uncovered` (int64 [1] on the device, added to) receives their number so that it can be checked once,
+    without a synchronisation per image."""
+    _chk_acc(acc, cnt, "acc_argmax_hist")
+    B, H, W, NC = acc.shape
+    if target is not None:
+        if not target.is_cuda or target.device != acc.device or target.dtype != torch.int64 or tuple(target.shape) != (B, H, W):
+            raise _lib.MrfpHipError("acc_argmax_hist: target must be int64 %s on the accumulator's GPU" % ((B, H, W),))
+        target = target.contiguous()
+    if hist is None:
+        hist = torch.zeros(NC, NC, dtype=torch.int64, device=acc.device)
+    elif hist.dtype != torch.int64 or tuple(hist.shape) != (NC, NC) or not hist.is_contiguous() or hist.device != acc.device:
+        raise _lib.MrfpHipError("acc_argmax_hist: hist must be a contiguous int64 %s on the accumulator's GPU" % ((NC, NC),))
+    if uncovered is not None and (uncovered.dtype != torch.int64 or uncovered.numel() != 1 or uncovered.device != acc.device):
+        raise _lib.MrfpHipError("acc_argmax_hist: uncovered must be int64 [1] on the accumulator's GPU")
+    pred = torch.empty(B, H, W, dtype=torch.uint8, device=acc.device) if want_pred else None
+    call("mrfp_acc_argmax_hist", ptr(acc), ptr(cnt), ptr(target), B * H * W, NC, ptr(hist), ptr(pred), ptr(uncovered), stream())
+    return hist, pred
+
+
+# ------------------------------------------------------------------------------------------
 # ReLU, input staging, convolution
 # ------------------------------------------------------------------------------------------
 class _ReLU(torch.autograd.Function):
