@@ -254,6 +254,30 @@ int mrfp_conv_fwd(const void* x, const void* wpack, const float* bias, void* y, 
                   int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S,
                   int64_t Ho, int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil,
                   int64_t sstride, const void* addend, float* colstats, void* stream);
+/* Folded inference form (mrfp_amd/inference.py): y = act(conv(x, wpack) + bias (+ addend)), act: 0 none, 1 ReLU (max(v, 0)),
+ *   2 ReLU6 (min(max(v, 0), 6)).  mrfp_conv_fwd's arguments without colstats, plus `act` (23 arguments).  The kernel is the one
+ *   mrfp_conv_fwd runs for the same operands without statistics; the activation is compiled into its epilogue and applied where the
+ *   value is rounded to the activation type, so the result equals clamp(mrfp_conv_fwd(...)) BIT FOR BIT (rounding is monotone, 0 and 6
+ *   are representable) and act = 0 is mrfp_conv_fwd itself.  act != 0 is a forward-launch option: sstride must be 1. */
+int mrfp_conv_fwd_act(const void* x, const void* wpack, const float* bias, void* y, int dtype,
+                      int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S,
+                      int64_t Ho, int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil,
+                      int64_t sstride, const void* addend, int act, void* stream);
+/* Fold pack: an eval-mode BatchNorm behind a convolution folded into the convolution's forward pack.  With
+ *   A[n] = bn_weight[n] / sqrt(running_var[n] + eps),  S[n] = bn_bias[n] - running_mean[n] * A[n]  (+ A[n] * conv_bias[n])
+ * it writes wf[Npad][R][S][Cpad] = round(w * A[n]) (`dtype`; the product is taken in fp32 from the OIHW fp32 master and rounded
+ * ONCE) and bias_out[Npad] = S (fp32); pad entries zero; no dgrad pack.  conv_bias, bn_weight (1) and bn_bias (0) may be NULL.
+ * Everything happens on the device, without a host synchronisation (17 arguments). */
+int mrfp_pack_weight_folded(const float* w, void* wf, const float* conv_bias, const float* bn_weight, const float* bn_bias,
+                            const float* running_mean, const float* running_var, float eps, float* bias_out, int dtype,
+                            int64_t N, int64_t C, int64_t R, int64_t S, int64_t Npad, int64_t Cpad, void* stream);
+/* All fold packs of a model in one launch.  jobs: device array of
+ *   struct { const float* w; void* wf; const float* conv_bias, *bn_weight, *bn_bias, *running_mean, *running_var; float* bias_out;
+ *            float eps; int32_t N, C, R, S, Npad, Cpad, out_f32; }                                                  (96 bytes)
+ * out_f32 = 1: wf is written as fp32 without rounding -- a depthwise weight [C][1][3][3] is the job N = Npad = C, C = Cpad = 1,
+ * R = S = 3 with out_f32 = 1 (the [C][9] fp32 taps mrfp_dwconv_fwd_act reads).  prefix: device int64[njobs + 1], exclusive prefix sum
+ * of the jobs' element counts Npad*R*S*Cpad + Npad; total = prefix[njobs] (6 arguments). */
+int mrfp_pack_weights_folded_batched(const void* jobs, const int64_t* prefix, int64_t njobs, int64_t total, int dtype, void* stream);
 /* colstats (optional): the epilogue also writes per-channel partial sums of the STORED output,
  * float [nblk][2][ldy] (sum, sum of squares per row block): the BatchNorm statistics pass over the conv output
  * disappears.  mrfp_conv_stats_layout describes that buffer for the launch with the same arguments (a statistics buffer, no
@@ -445,6 +469,10 @@ int64_t mrfp_dwconv_nslab(int dtype, int64_t B, int64_t Ho, int64_t Cp);
 int64_t mrfp_dwconv_wgrad_ws_bytes(int dtype, int64_t B, int64_t Ho, int64_t Cp);
 int mrfp_dwconv_fwd(const void* x, const float* w, const float* bias, void* y, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp,
                     int64_t C, int64_t Ho, int64_t Wo, int64_t stride, int64_t dil, float* ws, void* stream);
+/* folded inference form: y = act(dwconv(x, w) + bias), act as in mrfp_conv_fwd_act; mrfp_dwconv_fwd's arguments without ws, plus
+ * `act` (16 arguments).  Equals clamp(mrfp_dwconv_fwd(...)) bit for bit; act = 0 is mrfp_dwconv_fwd without statistics. */
+int mrfp_dwconv_fwd_act(const void* x, const float* w, const float* bias, void* y, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp,
+                        int64_t C, int64_t Ho, int64_t Wo, int64_t stride, int64_t dil, int act, void* stream);
 int mrfp_dwconv_dgrad(const void* dy, const float* w, void* dx, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp, int64_t C,
                       int64_t Ho, int64_t Wo, int64_t stride, int64_t dil, void* stream);
 int mrfp_dwconv_wgrad(const void* x, const void* dy, float* dw, void* ws, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp,

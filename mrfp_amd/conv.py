@@ -99,6 +99,228 @@ def get_pack(weight: torch.Tensor, bias: Optional[torch.Tensor], dtype, Cphys: i
     return pk
 
 
+# ---- folded inference packs (mrfp_amd/inference.py) -----------------------------------------------------------------
+# conv -> eval-mode BatchNorm as ONE convolution: forward pack round(w * A[n]) from the fp32 master, fp32 bias S (mrfp_pack_weight_folded).
+# The packs live in the per-weight cache above under keys that start with "fold".  They are stale when the weight, the convolution's
+# bias or any of the four BatchNorm tensors changed: their autograd version counters (optimizer.step of torch, load_state_dict,
+# any in-place torch operator), _EPOCH (invalidate_packs(): the fused SGD kernel, checkpoint loads, broadcasts) and
+# ops.RUNNING_STATS_EPOCH -- bumped by every training-mode BatchNorm forward, whose kernel updates the running statistics through raw
+# pointers that no version counter sees.  Nothing is read back to the host to decide.
+FOLD_PACK_LAUNCHES = [0]      # fold-pack launches so far (tests)
+_FOLD_SETS = []               # weak references to the pair lists of models with the fold enabled: a stale pack refolds its whole set
+
+
+def _fold_tensors(weight, conv_bias, norm):
+    return (weight, conv_bias, norm.weight, norm.bias, norm.running_mean, norm.running_var)
+
+
+def _fold_key(weight, conv_bias, norm, dtype, Cphys, Nphys, depthwise):
+    return ("fold", dtype, Cphys, Nphys, bool(depthwise)) + tuple(t.data_ptr() if t is not None else 0
+                                                                  for t in _fold_tensors(weight, conv_bias, norm))
+
+
+def _fold_version(weight, conv_bias, norm):
+    from . import ops
+    return tuple(t._version if t is not None else 0 for t in _fold_tensors(weight, conv_bias, norm)) + \
+        (float(norm.eps), _EPOCH[0], ops.RUNNING_STATS_EPOCH[0])
+
+
+def _fold_f32(t, what):
+    if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+        raise _lib.MrfpHipError("folded inference: %s must be a contiguous fp32 tensor (got %s)" % (what, t.dtype))
+    return t
+
+
+def _fold_slot(weight, key):
+    per_w = _PACKS.get(id(weight))
+    if per_w is None:
+        per_w = {}
+        _PACKS[id(weight)] = per_w
+        weakref.finalize(weight, _PACKS.pop, id(weight), None)
+    pk = per_w.get(key)
+    if pk is None:
+        dtype, Cphys, Nphys, depthwise = key[1:5]
+        N, _, R, S = weight.shape
+        pk = _Pack()
+        pk.wf = torch.empty(Nphys * R * S * Cphys, dtype=torch.float32 if depthwise else dtype, device=weight.device)
+        pk.wd = None
+        pk.bias = torch.empty(Nphys, dtype=torch.float32, device=weight.device)
+        pk.version = None
+        pk.wref = weakref.ref(weight)
+        pk.key = key
+        per_w[key] = pk
+    return pk
+
+
+def _fold_job(weight, conv_bias, norm, key, pk):
+    """(pointers, eps, dims) of one fold job -- the FoldJob record of csrc/conv_pack.hip"""
+    dtype, Cphys, Nphys, depthwise = key[1:5]
+    N, C, R, S = weight.shape
+    for t, what in zip(_fold_tensors(weight, conv_bias, norm), ("weight", "conv bias", "norm weight", "norm bias", "running_mean", "running_var")):
+        _fold_f32(t, what)
+    if norm.running_mean is None or norm.running_var is None:
+        raise _lib.MrfpHipError("folded inference: the BatchNorm has no running statistics")
+    ptrs = (weight.data_ptr(), pk.wf.data_ptr(), ptr(conv_bias) or 0, ptr(norm.weight) or 0, ptr(norm.bias) or 0,
+            norm.running_mean.data_ptr(), norm.running_var.data_ptr(), pk.bias.data_ptr())
+    dims = (N, 1, R, S, Nphys, 1, 1) if depthwise else (N, C, R, S, Nphys, Cphys, 0)
+    return ptrs, float(norm.eps), dims
+
+
+def fold_packs_batched(items):
+    """ONE mrfp_pack_weights_folded_batched launch per pack dtype for `items` = [(weight, conv_bias, norm, key)]."""
+    import numpy as np
+    by_dtype = {}
+    for it in items:
+        by_dtype.setdefault(it[3][1], []).append(it)
+    rec_t = np.dtype([("ptrs", "<u8", (8,)), ("eps", "<f4"), ("dims", "<i4", (7,))])
+    assert rec_t.itemsize == 96
+    for dtype, its in by_dtype.items():
+        rec = np.zeros(len(its), dtype=rec_t)
+        prefix = np.zeros(len(its) + 1, dtype=np.int64)
+        pks = []
+        for i, (w, cb, norm, key) in enumerate(its):
+            pk = _fold_slot(w, key)
+            ptrs, eps, dims = _fold_job(w, cb, norm, key, pk)
+            rec[i]["ptrs"], rec[i]["eps"], rec[i]["dims"] = ptrs, eps, dims
+            prefix[i + 1] = prefix[i] + dims[4] * dims[2] * dims[3] * dims[5] + dims[4]
+            pks.append(pk)
+        dev = its[0][0].device
+        jobs = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+        pre = torch.from_numpy(prefix).to(dev)
+        call("mrfp_pack_weights_folded_batched", ptr(jobs), ptr(pre), len(its), int(prefix[-1]), _lib._DT[dtype], stream())
+        FOLD_PACK_LAUNCHES[0] += 1
+        for (w, cb, norm, key), pk in zip(its, pks):
+            pk.version = _fold_version(w, cb, norm)
+
+
+def register_fold_set(pairs):
+    """pairs: [(conv module, norm module)] of a model whose fold was enabled (inference.fold_norms): when one of their packs is
+    found stale, every stale pack of the set is rebuilt in the same launch."""
+    _FOLD_SETS[:] = [r for r in _FOLD_SETS if r() is not None]
+    _FOLD_SETS.append(weakref.ref(pairs))
+
+
+def _refold_set(weight, dtype):
+    """Rebuilds, in one launch, the stale packs of the registered set `weight` belongs to (packs that exist, plus this dtype's
+    standard geometry for pairs that have none yet).  False: the weight is in no set."""
+    for r in _FOLD_SETS:
+        pairs = r()
+        if pairs is None or not any(c.weight is weight for c, _ in pairs):
+            continue
+        items = []
+        epc = _epc(dtype)
+        for c, n in pairs:
+            w, cb = c.weight, c.bias
+            if not w.is_cuda:
+                continue
+            depthwise = c.groups != 1
+            N, C = w.shape[0], w.shape[1]
+            keys = [k for k in _PACKS.get(id(w), {}) if k[0] == "fold"]
+            std = _fold_key(w, cb, n, dtype, 1 if depthwise else _round_up(C, epc), N if depthwise else _round_up(N, epc), depthwise)
+            if std not in keys:
+                keys.append(std)
+            ver = _fold_version(w, cb, n)
+            for k in keys:
+                pk = _PACKS.get(id(w), {}).get(k)
+                if k[5:] == std[5:] and (pk is None or pk.version != ver):
+                    items.append((w, cb, n, k))
+        if items:
+            fold_packs_batched(items)
+        return True
+    return False
+
+
+def get_folded_pack(weight, conv_bias, norm, dtype, Cphys, Nphys, depthwise=False) -> _Pack:
+    key = _fold_key(weight, conv_bias, norm, dtype, Cphys, Nphys, depthwise)
+    ver = _fold_version(weight, conv_bias, norm)
+    pk = _PACKS.get(id(weight), {}).get(key)
+    if pk is not None and pk.version == ver:
+        return pk
+    capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
+    if not capturing and _refold_set(weight, dtype):
+        pk = _PACKS.get(id(weight), {}).get(key)
+        if pk is not None and pk.version == ver:
+            return pk
+    pk = _fold_slot(weight, key)
+    ptrs, eps, dims = _fold_job(weight, conv_bias, norm, key, pk)
+    if depthwise:         # (the single entry writes the pack in `dtype`: a depthwise fp32 [C][9] pack is an fp32 job)
+        call("mrfp_pack_weight_folded", ptrs[0], ptrs[1], ptrs[2] or None, ptrs[3] or None, ptrs[4] or None, ptrs[5], ptrs[6], eps,
+             ptrs[7], _lib.F32, dims[0], 1, dims[2], dims[3], dims[4], 1, stream())
+    else:
+        call("mrfp_pack_weight_folded", ptrs[0], ptrs[1], ptrs[2] or None, ptrs[3] or None, ptrs[4] or None, ptrs[5], ptrs[6], eps,
+             ptrs[7], _lib._DT[dtype], *dims[:6], stream())
+    FOLD_PACK_LAUNCHES[0] += 1
+    if not capturing:
+        pk.version = ver
+    return pk
+
+
+def conv2d_folded(x, conv, norm, act=0, res=None):
+    """act(BN_eval(conv(x)) (+ res)) as ONE mrfp_conv_fwd_act launch (no normalisation launch).  No autograd: the caller
+    (network.mynn.conv_norm) only comes here with gradients disabled.  act: 0 none, 1 ReLU, 2 ReLU6."""
+    from .ops import _chk as chk
+    if torch.is_grad_enabled():
+        raise _lib.MrfpHipError("conv2d_folded: the folded form has no backward (call it under torch.no_grad())")
+    weight, bias = conv.weight, conv.bias
+    x = chk(x)
+    st = conv.stride[0]
+    ph, pw = conv.padding
+    dl = conv.dilation[0]
+    N, C, R, S = weight.shape
+    epc = _epc(x.dtype)
+    if x.shape[1] % epc != 0:
+        xp = zeros_cl(x.shape[0], _round_up(x.shape[1], epc), x.shape[2], x.shape[3], x.dtype, x.device)
+        xp[:, :x.shape[1]] = x
+        x = xp
+    if x.shape[1] < C:
+        raise _lib.MrfpHipError("conv2d_folded: input has %d channels, weight expects %d" % (x.shape[1], C))
+    B, Cphys, H, W = x.shape
+    Nphys = _round_up(N, epc)
+    Ho, Wo = _out_size(H, R, st, ph, dl), _out_size(W, S, st, pw, dl)
+    if res is not None:
+        res = chk(res, "res")
+        if tuple(res.shape) != (B, Nphys, Ho, Wo) or res.dtype != x.dtype:
+            raise _lib.MrfpHipError("conv2d_folded: the residual %s / %s does not match the output (%d, %d, %d, %d) / %s"
+                                    % (tuple(res.shape), res.dtype, B, Nphys, Ho, Wo, x.dtype))
+    pk = get_folded_pack(weight, bias, norm, x.dtype, Cphys, Nphys)
+    y = empty_cl(B, Nphys, Ho, Wo, x.dtype, x.device)
+    _lib.NOTE[0] = (C, N)
+    call("mrfp_conv_fwd_act", ptr(x), ptr(pk.wf), ptr(pk.bias), ptr(y), dt(x), B, H, W, Cphys, Nphys, Nphys, R, S, Ho, Wo,
+         st, ph, pw, dl, 1, ptr(res), int(act), stream())
+    if Nphys != N:
+        y = y[:, :N].contiguous(memory_format=CL)
+    return y
+
+
+def depthwise_conv2d_folded(x, conv, norm, act=0):
+    """The depthwise 3x3 form of conv2d_folded (mrfp_dwconv_fwd_act over the scaled fp32 taps)."""
+    from .ops import _chk as chk
+    if torch.is_grad_enabled():
+        raise _lib.MrfpHipError("depthwise_conv2d_folded: the folded form has no backward")
+    weight = conv.weight
+    st, dl, pd = conv.stride, conv.dilation, conv.padding
+    C = weight.shape[0]
+    if tuple(weight.shape[1:]) != (1, 3, 3) or st[0] != st[1] or st[0] not in (1, 2) or dl[0] != dl[1] or tuple(pd) != tuple(dl):
+        raise _lib.MrfpHipError("depthwise_conv2d_folded: weight %s stride %s padding %s dilation %s is not a depthwise 3x3 with "
+                                "padding = dilation and stride 1 or 2" % (tuple(weight.shape), st, pd, dl))
+    x = chk(x)
+    Cp = _round_up(C, _epc(x.dtype))
+    if x.shape[1] != Cp:
+        if x.shape[1] != C:
+            raise _lib.MrfpHipError("depthwise_conv2d_folded: input has %d channels, weight expects %d" % (x.shape[1], C))
+        xp = zeros_cl(x.shape[0], Cp, x.shape[2], x.shape[3], x.dtype, x.device)
+        xp[:, :C] = x
+        x = xp
+    B, _, H, W = x.shape
+    Ho, Wo = (H - 1) // st[0] + 1, (W - 1) // st[0] + 1
+    pk = get_folded_pack(weight, conv.bias, norm, x.dtype, 1, C, depthwise=True)
+    y = empty_cl(B, Cp, Ho, Wo, x.dtype, x.device)
+    call("mrfp_dwconv_fwd_act", ptr(x), ptr(pk.wf), ptr(pk.bias), ptr(y), dt(x), B, H, W, Cp, C, Ho, Wo, st[0], dl[0], int(act), stream())
+    if Cp != C:
+        y = y[:, :C].contiguous(memory_format=CL)
+    return y
+
+
 _BATCH = {}
 
 
@@ -157,6 +379,8 @@ def repack_all():
     todo = []
     for per_w in _PACKS.values():
         for key, pk in per_w.items():
+            if key[0] == "fold":                 # folded inference packs: rebuilt lazily (get_folded_pack)
+                continue
             w = pk.wref() if getattr(pk, "wref", None) is not None else None
             if w is None or not w.requires_grad or not _packable(pk, w):
                 continue
@@ -209,6 +433,8 @@ def _repack_selection(weights, biases):
     bmap = {id(w): b for w, b in zip(weights, biases)} if biases is not None else {}
     for w in weights:
         for key, pk in _PACKS.get(id(w), {}).items():
+            if key[0] == "fold":
+                continue
             has_b = bmap.get(id(w)) is not None
             if pk.wf is not None and _packable(pk, w, with_bias=has_b) and (pk.bias is None) == (not has_b) \
                     and key[4] == (bmap[id(w)].data_ptr() if has_b else 0):

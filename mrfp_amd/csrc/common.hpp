@@ -41,6 +41,12 @@ template <typename T> __device__ __forceinline__ T from_f(float v);
 template <> __device__ __forceinline__ float from_f<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16 from_f<bf16>(float v) { return __float2bfloat16(v); }
 template <> __device__ __forceinline__ f16 from_f<f16>(float v) { return (f16)v; }
+// epilogue activation of the folded inference kernels (compile-time ACT: 0 none, 1 ReLU, 2 ReLU6; conv_common.hpp)
+template <int ACT> __device__ __forceinline__ float act_f(float v) {
+    if constexpr (ACT == 1) return fmaxf(v, 0.f);
+    else if constexpr (ACT == 2) return fminf(fmaxf(v, 0.f), 6.f);
+    else return v;
+}
 
 // ---- 16-byte vectors of VEC elements ---------------------------------------------------------
 // VecT<T,VEC>: VEC elements moved with ONE memory instruction when VEC*sizeof(T) == 16

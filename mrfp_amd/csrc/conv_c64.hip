@@ -45,7 +45,7 @@ struct C64P {
 
 constexpr int kC64Slots = 4;
 
-template <typename T, int CB, int NCG, bool STATS, bool ADD>
+template <typename T, int CB, int NCG, bool STATS, bool ADD, int ACT = 0>
 __global__ __launch_bounds__(256, (CB == 1 ? 2 : 1)) void conv3x3_c64_kernel(C64P p) {
     constexpr int PSN = 4 / NCG;                 // pixel sub-strips per workgroup
     constexpr int SW = 64 * PSN;                 // strip width
@@ -245,15 +245,15 @@ __global__ __launch_bounds__(256, (CB == 1 ? 2 : 1)) void conv3x3_c64_kernel(C64
                     unpack2<T>(av[bk].y, a[2], a[3]);
                     unpack2<T>(av[bk].z, a[4], a[5]);
                     unpack2<T>(av[bk].w, a[6], a[7]);
-                    v.x = pack2<T>(acc[bk][0][0] + a[0], acc[bk][0][1] + a[1]);
-                    v.y = pack2<T>(acc[bk][0][2] + a[2], acc[bk][0][3] + a[3]);
-                    v.z = pack2<T>(acc[bk][1][0] + a[4], acc[bk][1][1] + a[5]);
-                    v.w = pack2<T>(acc[bk][1][2] + a[6], acc[bk][1][3] + a[7]);
+                    v.x = pack2<T>(act_f<ACT>(acc[bk][0][0] + a[0]), act_f<ACT>(acc[bk][0][1] + a[1]));
+                    v.y = pack2<T>(act_f<ACT>(acc[bk][0][2] + a[2]), act_f<ACT>(acc[bk][0][3] + a[3]));
+                    v.z = pack2<T>(act_f<ACT>(acc[bk][1][0] + a[4]), act_f<ACT>(acc[bk][1][1] + a[5]));
+                    v.w = pack2<T>(act_f<ACT>(acc[bk][1][2] + a[6]), act_f<ACT>(acc[bk][1][3] + a[7]));
                 } else {
-                    v.x = pack2<T>(acc[bk][0][0], acc[bk][0][1]);
-                    v.y = pack2<T>(acc[bk][0][2], acc[bk][0][3]);
-                    v.z = pack2<T>(acc[bk][1][0], acc[bk][1][1]);
-                    v.w = pack2<T>(acc[bk][1][2], acc[bk][1][3]);
+                    v.x = pack2<T>(act_f<ACT>(acc[bk][0][0]), act_f<ACT>(acc[bk][0][1]));
+                    v.y = pack2<T>(act_f<ACT>(acc[bk][0][2]), act_f<ACT>(acc[bk][0][3]));
+                    v.z = pack2<T>(act_f<ACT>(acc[bk][1][0]), act_f<ACT>(acc[bk][1][1]));
+                    v.w = pack2<T>(act_f<ACT>(acc[bk][1][2]), act_f<ACT>(acc[bk][1][3]));
                 }
                 if constexpr (STATS) {
                     // statistics of the STORED (rounded) values, each pixel counted wt times: what a statistics pass over the
@@ -322,29 +322,34 @@ bool c64_plan(const ConvP& p, int esz, ConvPlan& plan) {
     return true;
 }
 
-template <typename T, int CB, int NCG, bool STATS, bool ADD>
+template <typename T, int CB, int NCG, bool STATS, bool ADD, int ACT = 0>
 static int c64_launch(const C64P& q, int grid, hipStream_t st) {
     constexpr int SW = 64 * (4 / NCG), NPIECE = (SW + 4 + 7) / 8;
     const int lds = kC64Slots * CB * NPIECE * 1024 + 1024;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c64_kernel<T, CB, NCG, STATS, ADD>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c64_kernel<T, CB, NCG, STATS, ADD, ACT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set = true;
     }
-    hipLaunchKernelGGL((conv3x3_c64_kernel<T, CB, NCG, STATS, ADD>), dim3((unsigned)grid, (unsigned)((q.N + 127) / 128)), dim3(256), lds, st, q);
+    hipLaunchKernelGGL((conv3x3_c64_kernel<T, CB, NCG, STATS, ADD, ACT>), dim3((unsigned)grid, (unsigned)((q.N + 127) / 128)), dim3(256), lds, st, q);
     MRFP_LAUNCH_CHECK();
     return 0;
 }
 template <typename T, int CB, int NCG>
-static int c64_pick(const ConvP& p, const C64P& q, int grid, hipStream_t st) {
+static int c64_pick(const ConvP& p, const C64P& q, int grid, hipStream_t st, int act) {
+    if (act != 0) {       // folded inference launches (mrfp_conv_fwd_act): never with statistics
+        if (p.colstats) return -1;
+        if (act == 1) return p.addend ? c64_launch<T, CB, NCG, false, true, 1>(q, grid, st) : c64_launch<T, CB, NCG, false, false, 1>(q, grid, st);
+        return p.addend ? c64_launch<T, CB, NCG, false, true, 2>(q, grid, st) : c64_launch<T, CB, NCG, false, false, 2>(q, grid, st);
+    }
     if (p.colstats) return c64_launch<T, CB, NCG, true, false>(q, grid, st);
     if (p.addend) return c64_launch<T, CB, NCG, false, true>(q, grid, st);
     return c64_launch<T, CB, NCG, false, false>(q, grid, st);
 }
 
 template <typename T>
-static int c64_run_t(const ConvP& p, const ConvPlan& plan, hipStream_t st) {
+static int c64_run_t(const ConvP& p, const ConvPlan& plan, hipStream_t st, int act) {
     C64P q;
     q.x = p.x; q.w = p.w; q.y = p.y; q.bias = p.bias; q.addend = p.addend; q.colstats = p.colstats; q.rowweight = p.rowweight;
     q.B = p.B; q.H = p.H; q.W = p.W; q.N = p.N; q.ldy = p.ldy; q.dil = p.dil;
@@ -354,11 +359,11 @@ static int c64_run_t(const ConvP& p, const ConvPlan& plan, hipStream_t st) {
     q.spi = plan.spi;          // (the statistics rows the caller sized from the same plan: mrfp_conv_stats_layout)
     q.xbytes = p.xbytes; q.wbytes = p.wbytes; q.ybytes = (unsigned)((int64_t)p.M * p.ldy * 2);
     const int grid = plan.grid;
-    if (p.C == 64) return p.N == 64 ? c64_pick<T, 1, 2>(p, q, grid, st) : c64_pick<T, 1, 4>(p, q, grid, st);
-    return p.N == 64 ? c64_pick<T, 2, 2>(p, q, grid, st) : c64_pick<T, 2, 4>(p, q, grid, st);
+    if (p.C == 64) return p.N == 64 ? c64_pick<T, 1, 2>(p, q, grid, st, act) : c64_pick<T, 1, 4>(p, q, grid, st, act);
+    return p.N == 64 ? c64_pick<T, 2, 2>(p, q, grid, st, act) : c64_pick<T, 2, 4>(p, q, grid, st, act);
 }
-int c64_run(const ConvP& p, const ConvPlan& plan, bool is_f16, hipStream_t st) {
-    return is_f16 ? c64_run_t<f16>(p, plan, st) : c64_run_t<bf16>(p, plan, st);
+int c64_run(const ConvP& p, const ConvPlan& plan, bool is_f16, hipStream_t st, int act) {
+    return is_f16 ? c64_run_t<f16>(p, plan, st, act) : c64_run_t<bf16>(p, plan, st, act);
 }
 
 }  // namespace mrfp

@@ -287,6 +287,19 @@ template <typename T> __device__ __forceinline__ uint4 chunk_add(const uint4& a,
     return r;
 }
 
+// Epilogue activation of the folded inference launches (mrfp_conv_fwd_act, mrfp_dwconv_fwd_act): conv -> eval-mode BatchNorm -> ReLU /
+// ReLU6 as ONE launch.  ACT is a COMPILE-TIME parameter of every forward kernel (0 none, 1 ReLU, 2 ReLU6): the ACT = 0 instances are
+// the kernels they were before it existed, the others clamp where the value is rounded to the storage type.  Rounding is monotone
+// and 0 and 6 are representable in every activation type, so clamping the fp32 value before its rounding and clamping the rounded
+// value give the same bits -- act(kernel) equals clamp(kernel without act) bit for bit, whichever of the two a kernel does.
+//   (act_f: common.hpp)
+template <typename T, int ACT> __device__ __forceinline__ uint4 chunk_act(const uint4& a) {
+    uint4 r = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+    for (int u = 0; u < 16 / (int)sizeof(T); ++u) chunk_set<T>(r, u, from_f<T>(act_f<ACT>(to_f(chunk_get<T>(a, u)))));
+    return r;
+}
+
 #ifndef MRFP_RR_HOLD
 #define MRFP_RR_HOLD 1         // k steps (of the 6 per filter row) of the row-reuse kernels multiplied after the next fill has been issued
 #endif
@@ -318,11 +331,11 @@ struct ConvPlan {
 
 // ---- pointwise (1x1, stride 1) short-K kernels, conv_pw.hip ----------------------------------------------------------------
 bool pw_plan(const ConvP& p, int esz, ConvPlan& plan);        // false: not a launch for this kernel (plan untouched)
-int pw_run(const ConvP& p, bool is_f16, hipStream_t st);
+int pw_run(const ConvP& p, bool is_f16, hipStream_t st, int act = 0);      // act != 0: no statistics (mrfp_conv_fwd_act)
 
 // ---- weight-stationary kernel for the long-K pointwise layers (K = 512 / 1024 / 1280), conv_pwk.hip -------------------------------
 bool pwk_plan(const ConvP& p, int esz, ConvPlan& plan);
-int pwk_run(const ConvP& p, bool is_f16, hipStream_t st);
+int pwk_run(const ConvP& p, bool is_f16, hipStream_t st, int act = 0);
 
 // ---- weight-stationary 3x3 kernel for the 64-input-channel layers (HRFP ends, stem / layer-1 3x3), conv_c64.hip ---------------
 // accumulator-stationary weight gradient of the 3x3 / stride 1 / dilation <= 2 layers (conv_wg3.hip): slab slots per problem it may use
@@ -341,6 +354,6 @@ int wg1_run(const void* const* xs, const void* const* dys, int64_t count, float*
             unsigned xbytes, unsigned dybytes, int* splits, hipStream_t st);
 
 bool c64_plan(const ConvP& p, int esz, ConvPlan& plan);      // statistics rows: [image][sub-strip][slot], per image (not per row count)
-int c64_run(const ConvP& p, const ConvPlan& plan, bool is_f16, hipStream_t st);
+int c64_run(const ConvP& p, const ConvPlan& plan, bool is_f16, hipStream_t st, int act = 0);
 
 }  // namespace mrfp

@@ -83,7 +83,8 @@ __device__ __forceinline__ float lane_sum(float* red, const float (&v)[VEC], int
 }
 
 // y = dwconv(x, w) (+ bias); ws (STATS): float [B][nslab][2][Cp], the per-strip sums and sums of squares of the STORED y
-template <typename T, int VEC, bool STATS>
+// ACT (compile time: 0 none, 1 ReLU, 2 ReLU6 -- conv_common.hpp act_f): the folded inference form y = act(dwconv(x, w) + bias)
+template <typename T, int VEC, bool STATS, int ACT = 0>
 __global__ __launch_bounds__(kThreads) void dw_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ bias, T* __restrict__ y, DwGeom g, int nslab,
                                                           float* __restrict__ ws) {
@@ -127,6 +128,10 @@ __global__ __launch_bounds__(kThreads) void dw_fwd_kernel(const T* __restrict__ 
                 for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
                     for (int i = 0; i < VEC; ++i) acc[i] += xv[kw][i] * tap[kh * 3 + kw][i];
+            }
+            if constexpr (ACT != 0) {
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) acc[i] = act_f<ACT>(acc[i]);
             }
             store_f<T, VEC>(y + (((size_t)b * g.Ho + oh) * g.Wo + ow) * g.Cp + c0, acc);
             if constexpr (STATS) {
@@ -380,6 +385,17 @@ static int launch_dw_fwd(const void* x, const float* w, const float* bias, void*
     return 0;
 }
 
+template <typename T, int ACT>
+static int launch_dw_fwd_act(const void* x, const float* w, const float* bias, void* y, const DwGeom& g, hipStream_t st) {
+    constexpr int VEC = FullVec<T>::value;
+    const int nchunk = dw_split(g.Cp / VEC).nchunk;
+    const int nslab = dw_strips(g.B, nchunk, g.Ho, kDwFwdBlocks);      // (the grid of the plain forward launch)
+    hipLaunchKernelGGL((dw_fwd_kernel<T, VEC, false, ACT>), dim3((unsigned)nchunk, (unsigned)(g.B * nslab)), dim3(kThreads), 0, st,
+                       (const T*)x, w, bias, (T*)y, g, nslab, (float*)nullptr);
+    MRFP_LAUNCH_CHECK();
+    return 0;
+}
+
 template <typename T>
 static int launch_dw_dgrad(const void* dy, const float* w, void* dx, const DwGeom& g, hipStream_t st) {
     constexpr int VEC = FullVec<T>::value;
@@ -438,6 +454,22 @@ int mrfp_dwconv_fwd(const void* x, const float* w, const float* bias, void* y, i
     if (dtype == MRFP_BF16) return launch_dw_fwd<bf16>(x, w, bias, y, g, ws, st);
     if (dtype == MRFP_F16) return launch_dw_fwd<f16>(x, w, bias, y, g, ws, st);
     return launch_dw_fwd<float>(x, w, bias, y, g, ws, st);
+}
+
+int mrfp_dwconv_fwd_act(const void* x, const float* w, const float* bias, void* y, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp,
+                        int64_t C, int64_t Ho, int64_t Wo, int64_t stride, int64_t dil, int act, void* stream) {
+    MRFP_CHECK(act >= 0 && act <= 2, "dwconv_fwd_act: act must be 0 (none), 1 (ReLU) or 2 (ReLU6), got %d", act);
+    if (act == 0) return mrfp_dwconv_fwd(x, w, bias, y, dtype, B, H, W, Cp, C, Ho, Wo, stride, dil, nullptr, stream);
+    MRFP_CHECK(x && w && y, "dwconv_fwd_act: null pointer");
+    MRFP_CHECK(aligned16(x) && aligned16(y), "dwconv_fwd_act: tensors must be 16-byte aligned");
+    DwGeom g;
+    if (!dw_geom(dtype, B, H, W, Cp, C, Ho, Wo, stride, dil, g)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MRFP_BF16)
+        return act == 1 ? launch_dw_fwd_act<bf16, 1>(x, w, bias, y, g, st) : launch_dw_fwd_act<bf16, 2>(x, w, bias, y, g, st);
+    if (dtype == MRFP_F16)
+        return act == 1 ? launch_dw_fwd_act<f16, 1>(x, w, bias, y, g, st) : launch_dw_fwd_act<f16, 2>(x, w, bias, y, g, st);
+    return act == 1 ? launch_dw_fwd_act<float, 1>(x, w, bias, y, g, st) : launch_dw_fwd_act<float, 2>(x, w, bias, y, g, st);
 }
 
 int mrfp_dwconv_dgrad(const void* dy, const float* w, void* dx, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp, int64_t C,

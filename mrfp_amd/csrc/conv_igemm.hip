@@ -30,7 +30,7 @@ namespace mrfp {
 MRFP_STAMP_DECL(g_stamps_igemm)
 int stamps_igemm(unsigned long long* out, int n) { return MRFP_STAMP_READ(g_stamps_igemm, out, n); }
 
-template <typename T, int WM, int WN, bool ALIGNED, bool STRIDED, int TM, int TN, bool RR = false>
+template <typename T, int WM, int WN, bool ALIGNED, bool STRIDED, int TM, int TN, bool RR = false, int ACT = 0>
 __global__ __launch_bounds__(64 * WM * WN, ((RR && TM * TN >= 6) ? 2 : 3)) void conv_igemm_kernel(ConvP p) {   // 2nd = waves per SIMD
     constexpr int NT = 64 * WM * WN, BM = 32 * TM * WM, BN = 32 * TN * WN;
     constexpr int SA = BM * 8 / NT, SB = BN * 8 / NT, RSTEP = NT / 8;
@@ -525,6 +525,7 @@ __global__ __launch_bounds__(64 * WM * WN, ((RR && TM * TN >= 6) ? 2 : 3)) void 
                     }
                     v = chunk_add<T>(v, av);
                 }
+                if constexpr (ACT != 0) v = chunk_act<T, ACT>(v);       // (conv_common.hpp: on the value as it would have been stored)
                 if (full) {
                     *reinterpret_cast<uint4*>(dst) = v;
                 } else {
@@ -600,25 +601,25 @@ __global__ __launch_bounds__(256) void compact_stats_kernel(float* __restrict__ 
 
 // K tiles are staged by LDS-DMA into ONE LDS buffer per workgroup (fill, barrier, multiply, barrier, with the next fill issued
 // early: see the kernel); the 3-5 co-resident workgroups of a CU hide each other's fill latency.
-template <typename T, int WM, int WN, bool ALIGNED, bool STRIDED, int TM, int TN>
+template <typename T, int WM, int WN, bool ALIGNED, bool STRIDED, int TM, int TN, int ACT = 0>
 static int launch_igemm(const ConvP& p, hipStream_t st) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     constexpr int EP = WM * WN * 32 * (32 * TN * (int)sizeof(T) + 16);      // epilogue staging (+16 bytes of pitch per row)
     const int lds = (BM + BN) * 128 > EP ? (BM + BN) * 128 : EP;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<T, WM, WN, ALIGNED, STRIDED, TM, TN>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<T, WM, WN, ALIGNED, STRIDED, TM, TN, false, ACT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set = true;
     }
     const int64_t tiles = (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, ALIGNED, STRIDED, TM, TN>), dim3((unsigned)tiles), dim3(64 * WM * WN), lds, st, p);
+    hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, ALIGNED, STRIDED, TM, TN, false, ACT>), dim3((unsigned)tiles), dim3(64 * WM * WN), lds, st, p);
     MRFP_LAUNCH_CHECK();
     return 0;
 }
 
 // row-reuse kernels (conv_igemm_kernel<..., RR = true>): 3x3, stride 1, pad = dil, 64-channel-aligned C, W % 16 == 0
-template <typename T, int WM, int WN, int TM, int TN>
+template <typename T, int WM, int WN, int TM, int TN, int ACT = 0>
 static int launch_igemm_rr(const ConvP& p, hipStream_t st) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     constexpr int EP = WM * WN * 32 * (32 * TN * (int)sizeof(T) + 16);
@@ -626,20 +627,23 @@ static int launch_igemm_rr(const ConvP& p, hipStream_t st) {
     const int lds = fill > EP ? fill : EP;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<T, WM, WN, true, false, TM, TN, true>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<T, WM, WN, true, false, TM, TN, true, ACT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set = true;
     }
     const int64_t tiles = (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, true, false, TM, TN, true>), dim3((unsigned)tiles),
+    hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, true, false, TM, TN, true, ACT>), dim3((unsigned)tiles),
                        dim3(64 * WM * WN), lds, st, p);
     MRFP_LAUNCH_CHECK();
     return 0;
 }
 
-template <typename T, int WM, int WN, int TM, int TN>
+template <typename T, int WM, int WN, int TM, int TN, int ACT = 0>
 static int pick_igemm(const ConvP& p, hipStream_t st) {
     const bool aligned = (p.cpr & 7) == 0, strided = p.sstride > 1;
+    if constexpr (ACT != 0) {         // forward launches only (conv_fwd_act_impl refuses sstride > 1): no strided instances
+        return aligned ? launch_igemm<T, WM, WN, true, false, TM, TN, ACT>(p, st) : launch_igemm<T, WM, WN, false, false, TM, TN, ACT>(p, st);
+    }
     if (aligned) return strided ? launch_igemm<T, WM, WN, true, true, TM, TN>(p, st) : launch_igemm<T, WM, WN, true, false, TM, TN>(p, st);
     return strided ? launch_igemm<T, WM, WN, false, true, TM, TN>(p, st) : launch_igemm<T, WM, WN, false, false, TM, TN>(p, st);
 }
@@ -755,28 +759,33 @@ static ConvPlan conv_plan(const ConvP& p, int esz) {
     return tile(ConvKernel::t128x128, 2, 2);                          // <2,2,2,2>
 }
 
-template <typename T>
+template <typename T, int ACT = 0>
 static int run_igemm(const ConvP& p, const ConvPlan& plan, hipStream_t st) {
     if constexpr (sizeof(T) == 2) {      // (kernels with 16-bit instances only: conv_plan never picks them for fp32)
         const bool is_f16 = std::is_same<T, f16>::value;
         switch (plan.kind) {
-        case ConvKernel::pw: return pw_run(p, is_f16, st);
-        case ConvKernel::pwk: return pwk_run(p, is_f16, st);
-        case ConvKernel::c64: return c64_run(p, plan, is_f16, st);
-        case ConvKernel::rr384: return launch_igemm_rr<T, 4, 1, 3, 2>(p, st);
-        case ConvKernel::rr192: return launch_igemm_rr<T, 2, 2, 3, 2>(p, st);
-        case ConvKernel::t192x128: return pick_igemm<T, 2, 2, 3, 2>(p, st);
+        case ConvKernel::pw: return pw_run(p, is_f16, st, ACT);
+        case ConvKernel::pwk: return pwk_run(p, is_f16, st, ACT);
+        case ConvKernel::c64: return c64_run(p, plan, is_f16, st, ACT);
+        case ConvKernel::rr384: return launch_igemm_rr<T, 4, 1, 3, 2, ACT>(p, st);
+        case ConvKernel::rr192: return launch_igemm_rr<T, 2, 2, 3, 2, ACT>(p, st);
+        case ConvKernel::t192x128: return pick_igemm<T, 2, 2, 3, 2, ACT>(p, st);
         default: break;
         }
     }
     switch (plan.kind) {
-    case ConvKernel::t256x64: return pick_igemm<T, 4, 1, 2, 2>(p, st);
-    case ConvKernel::t96x128: return pick_igemm<T, 1, 4, 3, 1>(p, st);
-    case ConvKernel::t128x128: return pick_igemm<T, 2, 2, 2, 2>(p, st);
+    case ConvKernel::t256x64: return pick_igemm<T, 4, 1, 2, 2, ACT>(p, st);
+    case ConvKernel::t96x128: return pick_igemm<T, 1, 4, 3, 1, ACT>(p, st);
+    case ConvKernel::t128x128: return pick_igemm<T, 2, 2, 2, 2, ACT>(p, st);
     default: break;
     }
     set_error("conv_fwd: kernel %d has no fp32 instance", (int)plan.kind);
     return -1;
+}
+// (the activation is a template parameter of the kernels: the run-time value picks the instance here, once per launch)
+template <typename T>
+static int run_igemm_act(const ConvP& p, const ConvPlan& plan, hipStream_t st, int act) {
+    return act == 1 ? run_igemm<T, 1>(p, plan, st) : act == 2 ? run_igemm<T, 2>(p, plan, st) : run_igemm<T, 0>(p, plan, st);
 }
 
 // The kernel argument of a forward / dgrad launch from the mrfp_conv_fwd* arguments: geometry, M, cpr, kchunks, and the optional
@@ -810,7 +819,11 @@ extern "C" {
 static int conv_fwd_impl(const void* x, const void* wpack, const float* bias, void* y, int dtype, int64_t B, int64_t H,
                          int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S, int64_t Ho, int64_t Wo,
                          int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t sstride, const void* addend,
-                         float* colstats, void* stream, const void* addend_mask = nullptr, const unsigned char* rowweight = nullptr) {
+                         float* colstats, void* stream, const void* addend_mask = nullptr, const unsigned char* rowweight = nullptr,
+                         int act = 0) {
+    MRFP_CHECK(act >= 0 && act <= 2, "conv_fwd_act: act must be 0 (none), 1 (ReLU) or 2 (ReLU6), got %d", act);
+    MRFP_CHECK(act == 0 || (sstride == 1 && !colstats && !addend_mask && !rowweight),
+               "conv_fwd_act: an activation is a forward-launch option (sstride 1, no statistics, no gate mask)");
     MRFP_CHECK(!addend || aligned16(addend), "conv_fwd: addend must be 16-byte aligned");
     MRFP_CHECK(!rowweight || (colstats && ((uintptr_t)rowweight & 3) == 0), "conv_fwd_wstats: the row weights need statistics and 4-byte alignment");
     MRFP_CHECK(!addend_mask || (addend && dtype != MRFP_F32 && (N & 7) == 0 && ldy == N),
@@ -868,8 +881,9 @@ static int conv_fwd_impl(const void* x, const void* wpack, const float* bias, vo
         p.xbytes = (dbg_drop & 1) ? 0u : (unsigned)(bc * img);
         p.wbytes = (dbg_drop & 2) ? 0u : (unsigned)wb;
         if (chunked) plan = conv_plan(p, esz);       // a batch range is a launch of its own: a smaller M may take another kernel
-        rc = dtype == MRFP_F32 ? run_igemm<float>(p, plan, (hipStream_t)stream)
-             : dtype == MRFP_F16 ? run_igemm<f16>(p, plan, (hipStream_t)stream) : run_igemm<bf16>(p, plan, (hipStream_t)stream);
+        rc = dtype == MRFP_F32 ? run_igemm_act<float>(p, plan, (hipStream_t)stream, act)
+             : dtype == MRFP_F16 ? run_igemm_act<f16>(p, plan, (hipStream_t)stream, act)
+                                 : run_igemm_act<bf16>(p, plan, (hipStream_t)stream, act);
     }
     if (rc || !colstats) return rc;
     if (plan.stats_blocks > kCompactAbove) {
@@ -906,6 +920,16 @@ int mrfp_conv_fwd(const void* x, const void* wpack, const float* bias, void* y, 
                   float* colstats, void* stream) {
     return conv_fwd_impl(x, wpack, bias, y, dtype, B, H, W, C, N, ldy, R, S, Ho, Wo, stride, pad_h, pad_w, dil, sstride, addend,
                          colstats, stream);
+}
+
+/* the folded inference form: y = act(conv(x, wpack) + bias (+ addend)).  The kernel is the launch plan's choice for the same operands
+ * without statistics -- what mrfp_conv_fwd(..., colstats = NULL) runs -- with the activation compiled into its epilogue */
+int mrfp_conv_fwd_act(const void* x, const void* wpack, const float* bias, void* y, int dtype, int64_t B, int64_t H,
+                      int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S, int64_t Ho, int64_t Wo,
+                      int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t sstride, const void* addend,
+                      int act, void* stream) {
+    return conv_fwd_impl(x, wpack, bias, y, dtype, B, H, W, C, N, ldy, R, S, Ho, Wo, stride, pad_h, pad_w, dil, sstride, addend,
+                         nullptr, stream, nullptr, nullptr, act);
 }
 
 int mrfp_conv_fwd_wstats(const void* x, const void* wpack, const float* bias, void* y, int dtype, int64_t B, int64_t H,

@@ -127,6 +127,99 @@ __global__ __launch_bounds__(256) void pack_weights_batched_kernel(const PackJob
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Fold pack (folded inference, mrfp_amd/inference.py): an eval-mode BatchNorm behind a convolution is the per-channel affine
+//   A[n] = gamma[n] * (1 / sqrt(var[n] + eps)),   S[n] = beta[n] - mean[n] * A[n]  (+ A[n] * conv_bias[n])
+// (the expressions of bn_eval_coef_kernel, stats.hip, here with IEEE-rounded sqrt and division), so  BN(conv(x, w) + b) = conv(x, w * A) + S.  The pack is made from the fp32
+// MASTER: wf[Npad][R][S][Cpad] = round(w * A[n]) -- the product in fp32, ONE rounding to the pack type (scaling an already rounded
+// pack would round twice) -- plus the fp32 bias vector S[Npad] (pad entries zero).  No dgrad pack: the folded form has no backward.
+// A depthwise weight [C][1][3][3] is the same job with out_f32 = 1, C = Cpad = 1: wf[C][9] fp32 = w * A, no rounding.
+// One thread per destination element (the pack's, then the bias vector's); a job table in device memory folds a whole model in one
+// launch (every thread finds its job by binary search over the element-count prefix), the single form passes its job by value.
+// ---------------------------------------------------------------------------------------------
+struct FoldJob {
+    const float* w;          // OIHW fp32 master
+    void* wf;                // forward pack (T, or fp32 when out_f32)
+    const float* cbias;      // the convolution's own bias [N] or null
+    const float* gamma;      // BatchNorm weight [N] or null (1)
+    const float* beta;       // BatchNorm bias [N] or null (0)
+    const float* mean;       // running_mean [N]
+    const float* var;        // running_var [N]
+    float* sout;             // S [Npad] fp32
+    float eps;
+    int N, C, R, S, Npad, Cpad, out_f32;
+};
+static_assert(sizeof(FoldJob) == 96, "FoldJob layout is part of the C ABI (mrfp_hip.h, mrfp_amd/conv.py)");
+
+template <typename T>
+__global__ __launch_bounds__(256) void pack_weights_folded_kernel(const FoldJob* __restrict__ jobs, const int64_t* __restrict__ prefix,
+                                                                   int njobs, int64_t total, FoldJob single) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        FoldJob jb = single;
+        int64_t e = i;
+        if (jobs) {
+            int lo = 0, hi = njobs;             // largest j with prefix[j] <= i
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (prefix[mid] <= i) lo = mid; else hi = mid;
+            }
+            jb = jobs[lo];
+            e = i - prefix[lo];
+        }
+        const int64_t nf = (int64_t)jb.Npad * jb.R * jb.S * jb.Cpad;
+        const bool is_bias = e >= nf;
+        int n, c = 0, r = 0, s_ = 0;
+        if (is_bias) {
+            n = (int)(e - nf);
+        } else {
+            c = (int)(e % jb.Cpad);
+            int64_t rest = e / jb.Cpad;
+            s_ = (int)(rest % jb.S); rest /= jb.S;
+            r = (int)(rest % jb.R);
+            n = (int)(rest / jb.R);
+        }
+        float a = 0.f;
+        if (n < jb.N) {
+            // correctly rounded (IEEE) square root and division: the default `1.0f / sqrtf(v)` compiles to v_sqrt_f32 + v_rcp_f32, each good to
+            // 1 ulp -- enough for an apply coefficient, but the fold pack is specified as the fp32 product w * A rounded once, reproducible
+            // bit for bit from the same fp32 expressions anywhere (once per weight update: the cost is nothing)
+            // (through fp64, whose sqrt and division are IEEE here: rounding a 53-bit square root / quotient of 24-bit operands to 24 bits
+            //  is the correctly rounded fp32 result -- 53 >= 2 * 24 + 2)
+            const float sd = (float)sqrt((double)(jb.var[n] + jb.eps));
+            const float is = (float)(1.0 / (double)sd);
+            a = (jb.gamma ? jb.gamma[n] : 1.f) * is;
+        }
+        if (is_bias) {
+            float sv = 0.f;
+            if (n < jb.N) {
+                sv = (jb.beta ? jb.beta[n] : 0.f) - jb.mean[n] * a;
+                if (jb.cbias) sv = sv + a * jb.cbias[n];
+            }
+            jb.sout[n] = sv;
+        } else {
+            const float v = (n < jb.N && c < jb.C) ? jb.w[(((int64_t)n * jb.C + c) * jb.R + r) * jb.S + s_] * a : 0.f;
+            if (jb.out_f32) reinterpret_cast<float*>(jb.wf)[e] = v;
+            else reinterpret_cast<T*>(jb.wf)[e] = from_f<T>(v);
+        }
+    }
+}
+
+template <typename T>
+static int launch_fold(const FoldJob* jobs, const int64_t* prefix, int njobs, int64_t total, const FoldJob& single, hipStream_t st) {
+    int64_t blocks = (total + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL((pack_weights_folded_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, jobs, prefix, njobs, total, single);
+    MRFP_LAUNCH_CHECK();
+    return 0;
+}
+static int run_fold(int dtype, const FoldJob* jobs, const int64_t* prefix, int njobs, int64_t total, const FoldJob& single, hipStream_t st) {
+    if (dtype == MRFP_F32) return launch_fold<float>(jobs, prefix, njobs, total, single, st);
+    if (dtype == MRFP_BF16) return launch_fold<bf16>(jobs, prefix, njobs, total, single, st);
+    if (dtype == MRFP_F16) return launch_fold<f16>(jobs, prefix, njobs, total, single, st);
+    set_error("pack_weight_folded: unknown dtype %d", dtype);
+    return -1;
+}
+
 // network input: NCHW fp32 [B,C,H,W] -> NHWC T [B,H,W,Cpad] (pad channels zero)
 template <typename T>
 __global__ void nchw_to_nhwc_pad_kernel(const float* __restrict__ x, T* __restrict__ y, int B, int C, int H, int W, int Cpad) {
@@ -191,6 +284,23 @@ int mrfp_pack_weights_batched(const void* jobs, const int64_t* prefix, int64_t n
         MRFP_CHECK(false, "pack_weights_batched: unknown dtype %d", dtype);
     MRFP_LAUNCH_CHECK();
     return 0;
+}
+
+int mrfp_pack_weight_folded(const float* w, void* wf, const float* conv_bias, const float* bn_weight, const float* bn_bias,
+                            const float* running_mean, const float* running_var, float eps, float* bias_out, int dtype, int64_t N,
+                            int64_t C, int64_t R, int64_t S, int64_t Npad, int64_t Cpad, void* stream) {
+    MRFP_CHECK(w && wf && running_mean && running_var && bias_out && N > 0 && C > 0 && R > 0 && S > 0 && Npad >= N && Cpad >= C,
+               "pack_weight_folded: bad arguments");
+    mrfp::FoldJob jb{};
+    jb.w = w; jb.wf = wf; jb.cbias = conv_bias; jb.gamma = bn_weight; jb.beta = bn_bias; jb.mean = running_mean; jb.var = running_var;
+    jb.sout = bias_out; jb.eps = eps;
+    jb.N = (int)N; jb.C = (int)C; jb.R = (int)R; jb.S = (int)S; jb.Npad = (int)Npad; jb.Cpad = (int)Cpad; jb.out_f32 = 0;
+    return mrfp::run_fold(dtype, nullptr, nullptr, 1, Npad * R * S * Cpad + Npad, jb, (hipStream_t)stream);
+}
+
+int mrfp_pack_weights_folded_batched(const void* jobs, const int64_t* prefix, int64_t njobs, int64_t total, int dtype, void* stream) {
+    MRFP_CHECK(jobs && prefix && njobs > 0 && njobs < (1LL << 30) && total > 0, "pack_weights_folded_batched: bad arguments");
+    return mrfp::run_fold(dtype, (const mrfp::FoldJob*)jobs, prefix, (int)njobs, total, mrfp::FoldJob{}, (hipStream_t)stream);
 }
 
 int mrfp_nchw_to_nhwc_pad(const float* x, void* y, int dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t Cpad,

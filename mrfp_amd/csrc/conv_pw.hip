@@ -55,7 +55,7 @@ int stamps_pw(unsigned long long* out, int n) { return MRFP_STAMP_READ(g_stamps_
 // of every row are zero-filled by the transfer's bounds check and never read.  (The 32 -> 256 dgrads of the 19-class head at 384^2 /
 // 192^2, reference deepv3.py:214-217 `final2`: 1.2 GB written for 151 MB read -- on the generic unaligned kernel they ran at
 // 3.7 TB/s where tuned MIOpen reaches 5.5: profiles/r05_vs_stock.md.)
-template <typename T, int KB, int NST, bool STATS, bool ADD, bool HALF = false>
+template <typename T, int KB, int NST, bool STATS, bool ADD, bool HALF = false, int ACT = 0>
 __global__ __launch_bounds__(256, 2) void conv1x1_bstat_kernel(BsP p) {
     static_assert(!HALF || KB == 1, "HALF: one 128-byte LDS block per row");
     constexpr int ROWB = HALF ? 64 : KB * 128;  // bytes of one row of X (K elements)
@@ -200,15 +200,15 @@ __global__ __launch_bounds__(256, 2) void conv1x1_bstat_kernel(BsP p) {
             unpack2<T>(g.y, a[2], a[3]);
             unpack2<T>(g.z, a[4], a[5]);
             unpack2<T>(g.w, a[6], a[7]);
-            v.x = pack2<T>(acc[i][0][0] + a[0], acc[i][0][1] + a[1]);
-            v.y = pack2<T>(acc[i][0][2] + a[2], acc[i][0][3] + a[3]);
-            v.z = pack2<T>(acc[i][1][0] + a[4], acc[i][1][1] + a[5]);
-            v.w = pack2<T>(acc[i][1][2] + a[6], acc[i][1][3] + a[7]);
+            v.x = pack2<T>(act_f<ACT>(acc[i][0][0] + a[0]), act_f<ACT>(acc[i][0][1] + a[1]));
+            v.y = pack2<T>(act_f<ACT>(acc[i][0][2] + a[2]), act_f<ACT>(acc[i][0][3] + a[3]));
+            v.z = pack2<T>(act_f<ACT>(acc[i][1][0] + a[4]), act_f<ACT>(acc[i][1][1] + a[5]));
+            v.w = pack2<T>(act_f<ACT>(acc[i][1][2] + a[6]), act_f<ACT>(acc[i][1][3] + a[7]));
         } else {
-            v.x = pack2<T>(acc[i][0][0], acc[i][0][1]);
-            v.y = pack2<T>(acc[i][0][2], acc[i][0][3]);
-            v.z = pack2<T>(acc[i][1][0], acc[i][1][1]);
-            v.w = pack2<T>(acc[i][1][2], acc[i][1][3]);
+            v.x = pack2<T>(act_f<ACT>(acc[i][0][0]), act_f<ACT>(acc[i][0][1]));
+            v.y = pack2<T>(act_f<ACT>(acc[i][0][2]), act_f<ACT>(acc[i][0][3]));
+            v.z = pack2<T>(act_f<ACT>(acc[i][1][0]), act_f<ACT>(acc[i][1][1]));
+            v.w = pack2<T>(act_f<ACT>(acc[i][1][2]), act_f<ACT>(acc[i][1][3]));
         }
         const unsigned off = ok ? ((unsigned)m * (unsigned)p.ldy + (unsigned)nl) * 2u : kOOB;
         u32x4 dv;
@@ -337,14 +337,14 @@ static int bstat_chunks(int M, int N) {
     return (tiles + per - 1) / per;              // ranges that actually hold tiles (the trailing ones would be empty)
 }
 
-template <typename T, int KB, bool STATS, bool ADD, bool HALF = false>
+template <typename T, int KB, bool STATS, bool ADD, bool HALF = false, int ACT = 0>
 static int launch_bstat(const ConvP& c, hipStream_t st) {
     constexpr int NST = KB == 4 ? MRFP_PW_NST4 : 3;               // K = 256: 2 x 32 KB stages (two workgroups per CU)
     constexpr int STAGE = KB * 64 * 128;
     const int lds = NST * STAGE;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_bstat_kernel<T, KB, NST, STATS, ADD, HALF>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_bstat_kernel<T, KB, NST, STATS, ADD, HALF, ACT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set = true;
     }
@@ -358,21 +358,27 @@ static int launch_bstat(const ConvP& c, hipStream_t st) {
     p.xbytes = c.xbytes; p.wbytes = c.wbytes; p.ybytes = (unsigned)((int64_t)c.M * c.ldy * 2);
     static const int dbg = env_switch("MRFP_DEBUG_DROP", 0);      // timing-only diagnostics (bit 2: drop the output stores)
     if (dbg & 4) p.ybytes = 0;
-    hipLaunchKernelGGL((conv1x1_bstat_kernel<T, KB, NST, STATS, ADD, HALF>), dim3((unsigned)(p.panels * chunks)), dim3(256), lds, st, p);
+    hipLaunchKernelGGL((conv1x1_bstat_kernel<T, KB, NST, STATS, ADD, HALF, ACT>), dim3((unsigned)(p.panels * chunks)), dim3(256), lds, st, p);
     MRFP_LAUNCH_CHECK();
     return 0;
 }
 
-template <typename T, bool STATS, bool ADD>
+template <typename T, bool STATS, bool ADD, int ACT = 0>
 static int run_bstat_v(const ConvP& p, hipStream_t st) {
     const int kb = p.C * 2 / 128;
-    if (kb == 0) return launch_bstat<T, 1, STATS, ADD, true>(p, st);      // K = 32
-    return kb == 1 ? launch_bstat<T, 1, STATS, ADD>(p, st) : kb == 2 ? launch_bstat<T, 2, STATS, ADD>(p, st) : launch_bstat<T, 4, STATS, ADD>(p, st);
+    if (kb == 0) return launch_bstat<T, 1, STATS, ADD, true, ACT>(p, st);      // K = 32
+    return kb == 1 ? launch_bstat<T, 1, STATS, ADD, false, ACT>(p, st)
+           : kb == 2 ? launch_bstat<T, 2, STATS, ADD, false, ACT>(p, st) : launch_bstat<T, 4, STATS, ADD, false, ACT>(p, st);
 }
 template <typename T>
-static int run_bstat(const ConvP& p, hipStream_t st) {
+static int run_bstat(const ConvP& p, hipStream_t st, int act) {
     // forward launches carry the fused statistics, dgrad launches the skip-gradient addend; never both in this network
     if (p.colstats && p.addend) return -1;
+    if (act != 0) {       // folded inference launches (mrfp_conv_fwd_act): an activation, never statistics or a gate mask
+        if (p.colstats || p.addend_mask) return -1;
+        if (act == 1) return p.addend ? run_bstat_v<T, false, true, 1>(p, st) : run_bstat_v<T, false, false, 1>(p, st);
+        return p.addend ? run_bstat_v<T, false, true, 2>(p, st) : run_bstat_v<T, false, false, 2>(p, st);
+    }
     if (p.colstats) return run_bstat_v<T, true, false>(p, st);
     if (p.addend) return run_bstat_v<T, false, true>(p, st);
     return run_bstat_v<T, false, false>(p, st);
@@ -388,6 +394,6 @@ bool pw_plan(const ConvP& p, int esz, ConvPlan& plan) {
     plan.stats_block_rows = (int64_t)((tiles + chunks - 1) / chunks) * 64;
     return true;
 }
-int pw_run(const ConvP& p, bool is_f16, hipStream_t st) { return is_f16 ? run_bstat<f16>(p, st) : run_bstat<bf16>(p, st); }
+int pw_run(const ConvP& p, bool is_f16, hipStream_t st, int act) { return is_f16 ? run_bstat<f16>(p, st, act) : run_bstat<bf16>(p, st, act); }
 
 }  // namespace mrfp

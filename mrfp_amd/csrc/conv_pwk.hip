@@ -91,7 +91,7 @@ struct PkP {
 
 constexpr int kPkRows = 48;
 
-template <typename T, int KQ, int NST, bool STATS, bool ADD>
+template <typename T, int KQ, int NST, bool STATS, bool ADD, int ACT = 0>
 __global__ __launch_bounds__(256, (KQ <= 2 ? 2 : 1)) void conv1x1_longk_kernel(PkP p) {
     constexpr int ROWB = KQ * 512;               // bytes of one row of X
     constexpr int STAGE = 4 * kPkRows * 128;     // [4 blocks of 64 channels][48 rows][128 B] = 24 KB
@@ -228,15 +228,15 @@ __global__ __launch_bounds__(256, (KQ <= 2 ? 2 : 1)) void conv1x1_longk_kernel(P
                 unpack2<T>(gt.y, a[2], a[3]);
                 unpack2<T>(gt.z, a[4], a[5]);
                 unpack2<T>(gt.w, a[6], a[7]);
-                v.x = pack2<T>(acc[rb][0][0] + a[0], acc[rb][0][1] + a[1]);
-                v.y = pack2<T>(acc[rb][0][2] + a[2], acc[rb][0][3] + a[3]);
-                v.z = pack2<T>(acc[rb][1][0] + a[4], acc[rb][1][1] + a[5]);
-                v.w = pack2<T>(acc[rb][1][2] + a[6], acc[rb][1][3] + a[7]);
+                v.x = pack2<T>(act_f<ACT>(acc[rb][0][0] + a[0]), act_f<ACT>(acc[rb][0][1] + a[1]));
+                v.y = pack2<T>(act_f<ACT>(acc[rb][0][2] + a[2]), act_f<ACT>(acc[rb][0][3] + a[3]));
+                v.z = pack2<T>(act_f<ACT>(acc[rb][1][0] + a[4]), act_f<ACT>(acc[rb][1][1] + a[5]));
+                v.w = pack2<T>(act_f<ACT>(acc[rb][1][2] + a[6]), act_f<ACT>(acc[rb][1][3] + a[7]));
             } else {
-                v.x = pack2<T>(acc[rb][0][0], acc[rb][0][1]);
-                v.y = pack2<T>(acc[rb][0][2], acc[rb][0][3]);
-                v.z = pack2<T>(acc[rb][1][0], acc[rb][1][1]);
-                v.w = pack2<T>(acc[rb][1][2], acc[rb][1][3]);
+                v.x = pack2<T>(act_f<ACT>(acc[rb][0][0]), act_f<ACT>(acc[rb][0][1]));
+                v.y = pack2<T>(act_f<ACT>(acc[rb][0][2]), act_f<ACT>(acc[rb][0][3]));
+                v.z = pack2<T>(act_f<ACT>(acc[rb][1][0]), act_f<ACT>(acc[rb][1][1]));
+                v.w = pack2<T>(act_f<ACT>(acc[rb][1][2]), act_f<ACT>(acc[rb][1][3]));
             }
             u32x4 dv;
             dv.x = v.x; dv.y = v.y; dv.z = v.z; dv.w = v.w;
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256, (KQ <= 2 ? 2 : 1)) void conv1x1_longk_kernel(P
 // ---------------------------------------------------------------------------------------------------------------------------------
 constexpr int kPk2Rows = 32;
 
-template <typename T, bool STATS, bool ADD>
+template <typename T, bool STATS, bool ADD, int ACT = 0>
 __global__ __launch_bounds__(512, 2) void conv1x1_longk2_kernel(PkP p) {
     constexpr int ROWB = 2048;                   // K = 1 024 elements
     constexpr int QTR = 4 * kPk2Rows * 128;      // one K quarter of a tile: [4 blocks][32 rows][128 B] = 16 KB
@@ -432,15 +432,15 @@ __global__ __launch_bounds__(512, 2) void conv1x1_longk2_kernel(PkP p) {
                     unpack2<T>(gt.y, a[2], a[3]);
                     unpack2<T>(gt.z, a[4], a[5]);
                     unpack2<T>(gt.w, a[6], a[7]);
-                    v.x = pack2<T>(acc[rb][0][0] + a[0], acc[rb][0][1] + a[1]);
-                    v.y = pack2<T>(acc[rb][0][2] + a[2], acc[rb][0][3] + a[3]);
-                    v.z = pack2<T>(acc[rb][1][0] + a[4], acc[rb][1][1] + a[5]);
-                    v.w = pack2<T>(acc[rb][1][2] + a[6], acc[rb][1][3] + a[7]);
+                    v.x = pack2<T>(act_f<ACT>(acc[rb][0][0] + a[0]), act_f<ACT>(acc[rb][0][1] + a[1]));
+                    v.y = pack2<T>(act_f<ACT>(acc[rb][0][2] + a[2]), act_f<ACT>(acc[rb][0][3] + a[3]));
+                    v.z = pack2<T>(act_f<ACT>(acc[rb][1][0] + a[4]), act_f<ACT>(acc[rb][1][1] + a[5]));
+                    v.w = pack2<T>(act_f<ACT>(acc[rb][1][2] + a[6]), act_f<ACT>(acc[rb][1][3] + a[7]));
                 } else {
-                    v.x = pack2<T>(acc[rb][0][0], acc[rb][0][1]);
-                    v.y = pack2<T>(acc[rb][0][2], acc[rb][0][3]);
-                    v.z = pack2<T>(acc[rb][1][0], acc[rb][1][1]);
-                    v.w = pack2<T>(acc[rb][1][2], acc[rb][1][3]);
+                    v.x = pack2<T>(act_f<ACT>(acc[rb][0][0]), act_f<ACT>(acc[rb][0][1]));
+                    v.y = pack2<T>(act_f<ACT>(acc[rb][0][2]), act_f<ACT>(acc[rb][0][3]));
+                    v.z = pack2<T>(act_f<ACT>(acc[rb][1][0]), act_f<ACT>(acc[rb][1][1]));
+                    v.w = pack2<T>(act_f<ACT>(acc[rb][1][2]), act_f<ACT>(acc[rb][1][3]));
                 }
                 u32x4 dv;
                 dv.x = v.x; dv.y = v.y; dv.z = v.z; dv.w = v.w;
@@ -505,12 +505,12 @@ bool pwk_plan(const ConvP& p, int esz, ConvPlan& plan) {
     return true;
 }
 
-template <typename T, bool STATS, bool ADD>
+template <typename T, bool STATS, bool ADD, int ACT = 0>
 static int pwk2_launch(const ConvP& c, hipStream_t st) {
     constexpr int lds = 4 * 2 * 4 * kPk2Rows * 128 + kPk2Rows * 128 * 4;      // ring of four 32 KB pairs + the 16 KB exchange
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_longk2_kernel<T, STATS, ADD>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_longk2_kernel<T, STATS, ADD, ACT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set = true;
     }
@@ -522,18 +522,18 @@ static int pwk2_launch(const ConvP& c, hipStream_t st) {
     p.chunks = pwk_chunks(c.M, c.N, 2048);
     const int chunks = (p.chunks + 7) / 8 * 8;
     p.xbytes = c.xbytes; p.wbytes = c.wbytes; p.ybytes = (unsigned)((int64_t)c.M * c.ldy * 2);
-    hipLaunchKernelGGL((conv1x1_longk2_kernel<T, STATS, ADD>), dim3((unsigned)(p.panels * chunks)), dim3(512), lds, st, p);
+    hipLaunchKernelGGL((conv1x1_longk2_kernel<T, STATS, ADD, ACT>), dim3((unsigned)(p.panels * chunks)), dim3(512), lds, st, p);
     MRFP_LAUNCH_CHECK();
     return 0;
 }
 
-template <typename T, int KQ, bool STATS, bool ADD>
+template <typename T, int KQ, bool STATS, bool ADD, int ACT = 0>
 static int pwk_launch(const ConvP& c, hipStream_t st) {
     constexpr int NST = KQ <= 2 ? 3 : 6;
     constexpr int lds = NST * 4 * kPkRows * 128;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_longk_kernel<T, KQ, NST, STATS, ADD>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_longk_kernel<T, KQ, NST, STATS, ADD, ACT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set = true;
     }
@@ -545,27 +545,37 @@ static int pwk_launch(const ConvP& c, hipStream_t st) {
     p.chunks = pwk_chunks(c.M, c.N, c.C * 2);
     const int chunks = (p.chunks + 7) / 8 * 8;
     p.xbytes = c.xbytes; p.wbytes = c.wbytes; p.ybytes = (unsigned)((int64_t)c.M * c.ldy * 2);
-    hipLaunchKernelGGL((conv1x1_longk_kernel<T, KQ, NST, STATS, ADD>), dim3((unsigned)(p.panels * chunks)), dim3(256), lds, st, p);
+    hipLaunchKernelGGL((conv1x1_longk_kernel<T, KQ, NST, STATS, ADD, ACT>), dim3((unsigned)(p.panels * chunks)), dim3(256), lds, st, p);
     MRFP_LAUNCH_CHECK();
     return 0;
 }
 template <typename T, int KQ>
-static int pwk_pick(const ConvP& p, hipStream_t st) {
+static int pwk_pick(const ConvP& p, hipStream_t st, int act) {
+    if (act != 0) {       // folded inference launches (mrfp_conv_fwd_act): an activation, never statistics or a gate mask
+        if (p.colstats || p.addend_mask) return -1;
+        if (act == 1) return p.addend ? pwk_launch<T, KQ, false, true, 1>(p, st) : pwk_launch<T, KQ, false, false, 1>(p, st);
+        return p.addend ? pwk_launch<T, KQ, false, true, 2>(p, st) : pwk_launch<T, KQ, false, false, 2>(p, st);
+    }
     if (p.colstats) return pwk_launch<T, KQ, true, false>(p, st);
     if (p.addend) return pwk_launch<T, KQ, false, true>(p, st);
     return pwk_launch<T, KQ, false, false>(p, st);
 }
 template <typename T>
-static int pwk_run_t(const ConvP& p, hipStream_t st) {
+static int pwk_run_t(const ConvP& p, hipStream_t st, int act) {
     const int kq = p.C * 2 / 512;
     static const int two = env_switch("MRFP_CONV_PWK2", 1);      // =0: K = 1 024 on the one-wave-per-SIMD form (A/B runs)
     if (kq == 4 && two) {
+        if (act != 0) {
+            if (p.colstats || p.addend_mask) return -1;
+            if (act == 1) return p.addend ? pwk2_launch<T, false, true, 1>(p, st) : pwk2_launch<T, false, false, 1>(p, st);
+            return p.addend ? pwk2_launch<T, false, true, 2>(p, st) : pwk2_launch<T, false, false, 2>(p, st);
+        }
         if (p.colstats) return pwk2_launch<T, true, false>(p, st);
         if (p.addend) return pwk2_launch<T, false, true>(p, st);
         return pwk2_launch<T, false, false>(p, st);
     }
-    return kq == 2 ? pwk_pick<T, 2>(p, st) : kq == 4 ? pwk_pick<T, 4>(p, st) : pwk_pick<T, 5>(p, st);
+    return kq == 2 ? pwk_pick<T, 2>(p, st, act) : kq == 4 ? pwk_pick<T, 4>(p, st, act) : pwk_pick<T, 5>(p, st, act);
 }
-int pwk_run(const ConvP& p, bool is_f16, hipStream_t st) { return is_f16 ? pwk_run_t<f16>(p, st) : pwk_run_t<bf16>(p, st); }
+int pwk_run(const ConvP& p, bool is_f16, hipStream_t st, int act) { return is_f16 ? pwk_run_t<f16>(p, st, act) : pwk_run_t<bf16>(p, st, act); }
 
 }  // namespace mrfp

@@ -23,7 +23,7 @@ from . import ops
 from .config import cfg
 from .conv import wgrad_boundary
 from .network import Resnet
-from .network.mynn import (HipBatchNorm2d, HipConv2d, HipInstanceNorm2d, Norm2d, Upsample, initialize_weights,
+from .network.mynn import (HipBatchNorm2d, HipConv2d, HipInstanceNorm2d, Norm2d, Upsample, conv_norm, initialize_weights,
                            initialize_weights_kaimingnormal_forOC)
 
 __all__ = ["_AtrousSpatialPyramidPoolingModule", "MRFPPlus", "simpleDeepV3Plus", "ReferenceRandom", "InjectedRandom"]
@@ -140,13 +140,12 @@ class _ConvBnRelu(nn.Sequential):
                          Norm2d(cout), nn.ReLU(inplace=True))
 
     def forward(self, x):
-        return self[1].fused(self[0](x), relu=True)
+        return conv_norm(self[0], self[1], x, relu=True)
 
     def forward_skip(self, x):
         """(module(x), alias of x): gradients arriving on the alias are added by this conv's dgrad epilogue, so a
         tensor with several consumers is chained through them instead of being summed by separate passes."""
-        y, xs = self[0].forward_skip(x)
-        return self[1].fused(y, relu=True), xs
+        return conv_norm(self[0], self[1], x, want_skip=True, relu=True)
 
 
 class _AtrousSpatialPyramidPoolingModule(nn.Module):
@@ -258,7 +257,7 @@ class _DeepLabBase(nn.Module):
             return trunk.stem(x), w_arr                # WiderResNet: mod1 -> pool2 -> mod2 -> pool3
         if isinstance(trunk, Resnet.ResNet3X3):
             return trunk.stem(x, w_arr), w_arr
-        return Resnet._norm_relu_pool(self.layer0[1], trunk.wt_layer[2], self.layer0[0](ops.as_activation(x)), w_arr), w_arr
+        return Resnet._conv_norm_relu_pool(self.layer0[0], self.layer0[1], trunk.wt_layer[2], ops.as_activation(x), w_arr), w_arr
 
     def _low(self, t, w_arr):
         """stem output -> low-level features (256 ch, 1/4): layer1 (reference deepv3.py:331-333) / mod3."""
@@ -284,8 +283,8 @@ class _DeepLabBase(nn.Module):
         return wgrad_boundary(self.bn_out[0].fused(t, relu=True))
 
     def _final1(self, d):
-        d = self.final1[1].fused(self.final1[0](d), relu=True)
-        return self.final1[4].fused(self.final1[3](d), relu=True)
+        d = conv_norm(self.final1[0], self.final1[1], d, relu=True)
+        return conv_norm(self.final1[3], self.final1[4], d, relu=True)
 
     def _plain_ce(self):
         c = self.criterion
@@ -368,6 +367,9 @@ class MRFPPlus(_DeepLabBase):
         self.rng = ReferenceRandom()
         self.fourier_perturb = None      # optional build-defined extension (mrfp_amd/perturb.py); off = reference path
 
+    def _fold_skips_hrfp(self):
+        return (getattr(self, "_mrfp_fold", False) and not self.training and not torch.is_grad_enabled())
+
     def hrfp_layers(self):
         """(conv, bn) pairs in the reference's re-initialisation order (deepv3.py:291-306)."""
         enc = [(getattr(self, "OClayer%d" % i), getattr(self, "OC%d_bn" % i)) for i in range(1, 5)]
@@ -384,7 +386,9 @@ class MRFPPlus(_DeepLabBase):
         """reference deepv3.py:320-327: conv -> nearest resize -> BN(train stats) -> ReLU, x8.  The resize
         is never materialised on its own: BN statistics and apply read the conv output through the
         nearest index tables.  need_out / need_dec (cfg.MODEL.HRFP_LAZY only): whether OCout / OCout_dec are read."""
-        lazy = cfg.MODEL.HRFP_LAZY and self._taps is None
+        # (folded inference, inference.fold_norms: at training=False nothing reads the branch -- need_out / need_dec are False -- and in
+        #  eval() its BatchNorms update no running statistics, so skipping it changes no output and no state)
+        lazy = (cfg.MODEL.HRFP_LAZY or self._fold_skips_hrfp()) and self._taps is None
         if lazy and not (need_out or need_dec):
             return None, None, xp
         resize = [dict(scale=1.205), dict(scale=1.2), dict(scale=1.2), dict(size=(int(h / 2), int(w / 2))),

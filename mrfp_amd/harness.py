@@ -446,10 +446,15 @@ def graph_topology(g):
 
 
 @torch.no_grad()
-def evaluate(model, batches, num_classes=19):
+def evaluate(model, batches, num_classes=19, fold=False):
     """reference main.py:887-913: model.eval(), per-image arg-max + confusion histogram (on the device,
-    one 19x19 int64 D2H at the end instead of two full-logit copies per image), mIoU as metrics.py:60-85."""
+    one 19x19 int64 D2H at the end instead of two full-logit copies per image), mIoU as metrics.py:60-85.
+    fold=True: the forwards run inside inference.fold_norms(model) (eval-mode BatchNorms folded into their convolutions)."""
     from . import metrics, ops
+    if fold:
+        from .inference import fold_norms
+        with fold_norms(model):
+            return evaluate(model, batches, num_classes)
     model.eval()
     hist, dropped = None, 0
     for img, label in batches:
@@ -540,7 +545,7 @@ def tta_variants(height, width, dst_size, scales, flip, window, stride):
 
 @torch.no_grad()
 def evaluate_tta(model, batches, num_classes=19, scales=(1.0,), flip=False, window=None, stride=None, resize_to_label=False,
-                 on_variant=None):
+                 on_variant=None, fold=False):
     """evaluate() with test-time augmentation: class PROBABILITIES averaged over image scales, a horizontal flip and overlapping
     windows, then arg-max + confusion histogram -> (hist, mIoU, dropped), the triple evaluate() returns.
 
@@ -554,8 +559,13 @@ def evaluate_tta(model, batches, num_classes=19, scales=(1.0,), flip=False, wind
 
     resize_to_label=False drops an image whose size differs from its label's, as evaluate() and the reference do (main.py:894,
     910-912); True scores it at the label's size instead.  Histograms are summed over the data-parallel ranks as in evaluate();
-    `dropped` stays per rank.  on_variant(image index, variant, low-resolution scores): measurement / test hook."""
+    `dropped` stays per rank.  on_variant(image index, variant, low-resolution scores): measurement / test hook.
+    fold=True: the forwards run inside inference.fold_norms(model)."""
     from . import metrics, ops
+    if fold:
+        from .inference import fold_norms
+        with fold_norms(model):
+            return evaluate_tta(model, batches, num_classes, scales, flip, window, stride, resize_to_label, on_variant)
     scales = _check_tta_args(scales, window, stride)
     model.eval()
     dev = next(model.parameters()).device

@@ -77,7 +77,7 @@ class ConvBNReLU(nn.Sequential):
         x, w_arr = _unpack(x_tuple, "BN")
         if x is None:
             return None
-        x = self[1].fused(self[0](x), act="relu6")
+        x = mynn.conv_norm(self[0], self[1], x, act="relu6")
         return [_apply_iw(self[3], self.iw, x, w_arr), w_arr]
 
 
@@ -115,8 +115,7 @@ class InvertedResidual(nn.Module):
         for i in range(n - 2):
             t = self.conv[i](t)
         conv_x, w_arr = t
-        conv_x = self.conv[n - 1].fused(self.conv[n - 2](conv_x))
-        x = ops.add(x, conv_x) if self.use_res_connect else conv_x
+        x = mynn.conv_norm(self.conv[n - 2], self.conv[n - 1], conv_x, post_add=x if self.use_res_connect else None)
         return [_apply_iw(self.instance_norm_layer, self.iw, x, w_arr), w_arr]
 
 

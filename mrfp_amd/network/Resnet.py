@@ -49,12 +49,26 @@ def _norm_relu(layer, iw, x, w_arr):
     return ops.relu(layer(x))
 
 
+def _conv_norm_relu(conv, layer, iw, x, w_arr):
+    """_norm_relu(layer, iw, conv(x), w_arr) with a BatchNorm pair going through mynn.conv_norm (foldable for inference)."""
+    if iw not in (1, 2) and isinstance(layer, mynn.HipBatchNorm2d):
+        return mynn.conv_norm(conv, layer, x, relu=True)
+    return _norm_relu(layer, iw, conv(x), w_arr)
+
+
 def _norm_relu_pool(layer, iw, x, w_arr):
     """_norm_relu followed by the stem's MaxPool2d(3, 2, 1) (reference Resnet.py:549-551); an InstanceNorm there runs as one
     operator with the pool."""
     if iw not in (1, 2) and isinstance(layer, mynn.HipInstanceNorm2d):
         return layer.fused_relu_pool(x)
     return ops.max_pool_3x3_s2(_norm_relu(layer, iw, x, w_arr))
+
+
+def _conv_norm_relu_pool(conv, layer, iw, x, w_arr):
+    """_norm_relu_pool(layer, iw, conv(x), w_arr), a BatchNorm pair through mynn.conv_norm."""
+    if iw not in (1, 2) and isinstance(layer, mynn.HipBatchNorm2d):
+        return ops.max_pool_3x3_s2(mynn.conv_norm(conv, layer, x, relu=True))
+    return _norm_relu_pool(layer, iw, conv(x), w_arr)
 
 
 class _Block(nn.Module):
@@ -73,21 +87,16 @@ class _Block(nn.Module):
             return None, None
         return x_tuple[0], x_tuple[1]
 
-    def _first_conv(self, x):
-        """conv1(x) and the tensor the skip connection should read: an alias of x whose gradient the conv1 dgrad
-        kernel accumulates."""
-        # (blocks with a downsample branch feed the alias to the downsample conv: its dgrad output becomes the addend of
-        #  conv1's dgrad launch instead of a separate accumulation pass over the block input)
-        return self.conv1.forward_skip(x)
-
-    def _tail(self, last_bn, out, x, w_arr):
-        residual = x if self.downsample is None else self.downsample[1].fused(self.downsample[0](x))
+    def _tail(self, last_conv, last_bn, out, x, w_arr):
+        """`out` is the input of the block's last convolution."""
+        residual = x if self.downsample is None else mynn.conv_norm(self.downsample[0], self.downsample[1], x)
         if self.iw >= 1:
             # (iw 3 / 4: an InstanceNorm reads this output next -- the apply pass hands it the plane sums)
-            out = last_bn.fused(out, res=residual, emit_stats=self.iw in (3, 4) and isinstance(last_bn, mynn.HipBatchNorm2d))
+            out = mynn.conv_norm(last_conv, last_bn, out, res=residual,
+                                 emit_stats=self.iw in (3, 4) and isinstance(last_bn, mynn.HipBatchNorm2d))
             out = _norm_relu(self.instance_norm_layer, self.iw, out, w_arr)
         else:
-            out = last_bn.fused(out, res=residual, relu=True)
+            out = mynn.conv_norm(last_conv, last_bn, out, res=residual, relu=True)
         return [out, w_arr]
 
 
@@ -108,9 +117,10 @@ class BasicBlock(_Block):
         x, w_arr = self._unpack(x_tuple)
         if x is None:
             return None
-        out, skip = self._first_conv(x)
-        out = self.bn1.fused(out, relu=True)
-        return self._tail(self.bn2, self.conv2(out), skip, w_arr)
+        # (want_skip: the skip connection reads an alias of x whose gradient conv1's dgrad kernel accumulates; blocks with a downsample
+        #  branch feed the alias to the downsample conv, whose dgrad output becomes the addend of conv1's dgrad launch)
+        out, skip = mynn.conv_norm(self.conv1, self.bn1, x, want_skip=True, relu=True)
+        return self._tail(self.conv2, self.bn2, out, skip, w_arr)
 
 
 class Bottleneck(_Block):
@@ -132,10 +142,9 @@ class Bottleneck(_Block):
         x, w_arr = self._unpack(x_tuple)
         if x is None:
             return None
-        out, skip = self._first_conv(x)
-        out = self.bn1.fused(out, relu=True)
-        out = self.bn2.fused(self.conv2(out), relu=True)
-        return self._tail(self.bn3, self.conv3(out), skip, w_arr)
+        out, skip = mynn.conv_norm(self.conv1, self.bn1, x, want_skip=True, relu=True)
+        out = mynn.conv_norm(self.conv2, self.bn2, out, relu=True)
+        return self._tail(self.conv3, self.bn3, out, skip, w_arr)
 
 
 class _Trunk(nn.Module):
@@ -197,7 +206,7 @@ class ResNet(_Trunk):
 
     def forward(self, x):
         w_arr = []
-        x = _norm_relu_pool(self.bn1, self.wt_layer[2], self.conv1(ops.as_activation(x)), w_arr)
+        x = _conv_norm_relu_pool(self.conv1, self.bn1, self.wt_layer[2], ops.as_activation(x), w_arr)
         return self._stages(x, w_arr)
 
 
@@ -221,9 +230,9 @@ class ResNet3X3(_Trunk):
 
     def stem(self, x, w_arr):
         """conv-norm-ReLU x 3 and the max pool."""
-        x = _norm_relu(self.bn1, self.wt_layer[0], self.conv1(ops.as_activation(x)), w_arr)
-        x = _norm_relu(self.bn2, self.wt_layer[1], self.conv2(x), w_arr)
-        return _norm_relu_pool(self.bn3, self.wt_layer[2], self.conv3(x), w_arr)
+        x = _conv_norm_relu(self.conv1, self.bn1, self.wt_layer[0], ops.as_activation(x), w_arr)
+        x = _conv_norm_relu(self.conv2, self.bn2, self.wt_layer[1], x, w_arr)
+        return _conv_norm_relu_pool(self.conv3, self.bn3, self.wt_layer[2], x, w_arr)
 
     def forward(self, x):
         w_arr = []

@@ -105,6 +105,46 @@ class HipConv2d(nn.Conv2d):
         return ops.conv2d_skip(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
 
 
+def fold_state(conv, norm):
+    """True when the pair (conv, norm) runs folded NOW: the fold was enabled on the norm (inference.fold_norms), both modules are
+    in eval() and gradients are disabled.  In every other state the ordinary path runs -- an enabled fold cannot reach a
+    training step."""
+    return (getattr(norm, "_mrfp_fold", False) and not norm.training and not conv.training and not torch.is_grad_enabled())
+
+
+def conv_norm(conv, norm, x, *, want_skip=False, post_add=None, **fused):
+    """The `conv -> norm` call site of every block: `norm.fused(conv(x), **fused)`, then `post_add + y` when given; with
+    want_skip the convolution is `conv.forward_skip(x)` and the result is (y, skip alias of x).  `fused` are the keywords of the
+    norm's own `fused()` -- relu / res / emit_stats of HipBatchNorm2d, act of HipLocalBatchNorm2d -- so the norm's activation and
+    residual are known when the convolution is launched.
+    Not folded (the default, and always in training): exactly those calls.  Folded (fold_state): ONE mrfp_conv_fwd_act /
+    mrfp_dwconv_fwd_act launch over the fold pack -- y = act(conv(x, W*A) + S (+ res | post_add)) -- and no normalisation launch."""
+    if fold_state(conv, norm):
+        from .. import conv as conv_mod
+        act = 1 if fused.get("relu") else 2 if fused.get("act") == "relu6" else 0
+        if fused.get("plan") is not None or (fused.get("act") not in (None, "relu6")):
+            raise ops._lib.MrfpHipError("conv_norm: a resize plan / act=%r cannot be folded" % (fused.get("act"),))
+        res = fused.get("res")
+        if res is not None and post_add is not None:
+            raise ops._lib.MrfpHipError("conv_norm: res and post_add are the same operand (the epilogue's addend)")
+        addend = res if res is not None else post_add
+        if conv._is_depthwise():
+            if addend is not None:
+                raise ops._lib.MrfpHipError("conv_norm: a folded depthwise convolution takes no residual")
+            y = conv_mod.depthwise_conv2d_folded(x, conv, norm, act)
+        else:
+            y = conv_mod.conv2d_folded(x, conv, norm, act, addend)
+        return (y, x) if want_skip else y
+    if want_skip:
+        y, skip = conv.forward_skip(x)
+    else:
+        y = conv(x)
+    y = norm.fused(y, **fused)
+    if post_add is not None:
+        y = ops.add(post_add, y)
+    return (y, skip) if want_skip else y
+
+
 def Norm2d(in_channels):
     """reference mynn.py:19-25: the BN class comes from cfg.MODEL.BNFUNC."""
     layer = cfg.MODEL.BNFUNC or HipBatchNorm2d

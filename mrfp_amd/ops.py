@@ -473,11 +473,18 @@ def _tag_planestats(y):
         y._mrfp_planestats = (ps[0], ps[1], y._version)
 
 
+# bumped by every training-mode BatchNorm forward: its kernel updates the running statistics in place through raw pointers, which no
+# autograd version counter sees -- the folded inference packs built from those statistics (conv.get_folded_pack) key on this
+RUNNING_STATS_EPOCH = [0]
+
+
 def batch_norm_act(x, weight, bias, running_mean, running_var, *, training, momentum=0.1, eps=1e-5,
                    relu=False, res=None, plan=None, emit_stats=False):
     """emit_stats: the caller normalises the result per image next (an InstanceNorm `iw` tap behind this residual tail, reference
     Resnet.py:218-225): the apply pass also writes the partial plane sums of its output and that statistics pass is skipped."""
     _LAST_PLANESTATS[0] = None
+    if training and running_mean is not None:
+        RUNNING_STATS_EPOCH[0] += 1
     y = _BatchNormAct.apply(x, weight, bias, running_mean, running_var, res, training, momentum, eps, relu, plan, bool(emit_stats))
     _tag_planestats(y)
     if (GATED_BN[0] and GATED_SKIP[0] and SIGN_MASK[0] and not relu and res is None and plan is None and training and y.grad_fn is not None
@@ -1796,6 +1803,8 @@ def local_batch_norm_act(x, weight, bias, running_mean, running_var, *, training
     """BatchNorm over this process's batch (never synchronised across ranks) followed by `act`: None or 'relu6'."""
     if act not in (None, "relu6"):
         raise _lib.MrfpHipError("local_batch_norm_act: act must be None or 'relu6' (got %r)" % (act,))
+    if training and running_mean is not None:
+        RUNNING_STATS_EPOCH[0] += 1
     return _LocalBatchNormAct.apply(x, weight, bias, running_mean, running_var, bool(training), momentum, eps, act)
 
 
