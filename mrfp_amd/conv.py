@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import call, dt, ptr, stream
-from .ops import CL, GRAD_DEFERRED, _chk, empty_cl, grad_sink, notify_grad, zeros_cl
+from .ops import CL, GRAD_DEFERRED, _chk, channel_sums, empty_cl, grad_sink, notify_grad, zeros_cl
 
 _PACKS = {}      # id(weight Parameter) -> {key: _Pack}; entry dropped when the Parameter dies
 import os as _os
@@ -30,14 +30,10 @@ class ConvStats(NamedTuple):
     rows: torch.Tensor         # the RAW per-row-block rows (an InstanceNorm consumer needs them per image: ops._in_plane_sums)
     row_blocks: int            # ... their count
     block_rows: int            # output rows of one row block; < 0: -(rows per image); 0: resize-weighted, no per-image use
-    resize_plan: Any           # the ops.NearestPlan the statistics are weighted for (STAT_RESIZE: its one consumer), or None
+    resize_plan: Any           # the ops.NearestPlan the statistics are weighted for (conv2d(stat_resize=): its one consumer), or None
+    version: int               # the tagged tensor's _version when it was tagged: modified in place since, the tag is ignored
 
 
-_LAST_STATS = [None]  # handed from _Conv2d.forward to conv2d() (autograd re-wraps the output tensor object)
-# set by a caller right before a convolution whose output goes through a nearest-neighbour resize into a training-mode BatchNorm
-# (deepv3.MRFPPlus._hrfp): the ops.NearestPlan of that resize.  The epilogue statistics then count every output pixel as often as
-# the resize reads it (mrfp_conv_fwd_wstats), and the BatchNorm skips its statistics pass over the resized tensor.
-STAT_RESIZE = [None]
 WSTATS = [_os.environ.get("MRFP_WSTATS", "1") != "0"]
 WSTATS_HITS = [0]
 _EPOCH = [0]     # bumped by writers that bypass autograd's version counters (the fused SGD kernel)
@@ -682,31 +678,17 @@ def L_single(B, H, W, Cphys, Ho, Wo, Nphys, esz):
 
 class _Conv2d(torch.autograd.Function):
     """want_skip: also return an alias of x for a skip connection; the gradient arriving on that alias is added by
-    the dgrad kernel's epilogue (no separate accumulation pass over the activation)."""
+    the dgrad kernel's epilogue (no separate accumulation pass over the activation).
+    stats: the rows the epilogue writes its output statistics into (sized by conv2d(), which tags the output with them), or None;
+    wtab: the pixel multiplicities that weight them (conv2d(stat_resize=))."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad_h, pad_w, dil, Nphys, want_skip):
+    def forward(ctx, x, weight, bias, stride, pad_h, pad_w, dil, Nphys, want_skip, stats, wtab):
         B, Cphys, H, W = x.shape
         N, C, R, S = weight.shape
         Ho, Wo = _out_size(H, R, stride, pad_h, dil), _out_size(W, S, stride, pad_w, dil)
         pk = get_pack(weight, bias, x.dtype, Cphys, Nphys)
         y = empty_cl(B, Nphys, Ho, Wo, x.dtype, x.device)
-        stats = None
-        L = _lib.lib()
-        plan, STAT_RESIZE[0] = STAT_RESIZE[0], None
-        single = bool(L.mrfp_conv_single_launch(B, H * W * Cphys * x.element_size()))
-        wtab = None
-        if plan is not None and WSTATS[0] and FUSE_STATS[0] and single and (plan.Hs, plan.Ws) == (Ho, Wo) and R * S > 1:
-            wtab = plan.multiplicity(B)          # statistics of the nearest-resized output (see STAT_RESIZE)
-        if wtab is not None or (bias is None and FUSE_STATS[0] and single):
-            # no bias = a convolution that feeds a normalisation layer: let the epilogue produce its statistics
-            lay = (ctypes.c_int64 * 5)()
-            rc = L.mrfp_conv_stats_layout(dt(x), B, H, W, Cphys, Nphys, Nphys, R, S, Ho, Wo, stride, pad_h, pad_w, dil, 1,
-                                          int(wtab is not None), lay)
-            if rc != 0:
-                raise _lib.MrfpHipError("mrfp_conv_stats_layout failed (%d): %s" % (rc, L.mrfp_last_error().decode()))
-            nblk, rb, rows, first, cnt = lay
-            stats = torch.empty(rows * 2 * Nphys, dtype=torch.float32, device=x.device)
         _lib.NOTE[0] = (C, N)
         if wtab is not None:
             call("mrfp_conv_fwd_wstats", ptr(x), ptr(pk.wf), ptr(pk.bias), ptr(y), dt(x), B, H, W, Cphys, Nphys, Nphys, R, S,
@@ -715,15 +697,6 @@ class _Conv2d(torch.autograd.Function):
         else:
             call("mrfp_conv_fwd", ptr(x), ptr(pk.wf), ptr(pk.bias), ptr(y), dt(x), B, H, W, Cphys, Nphys, Nphys, R, S,
                  Ho, Wo, stride, pad_h, pad_w, dil, 1, None, ptr(stats), stream())
-        if stats is not None:      # the rows the BatchNorm finalize should read (compacted for large launches)
-            final = stats[first * 2 * Nphys:(first + cnt) * 2 * Nphys]
-            if wtab is not None:
-                # (element count = that of the RESIZED tensor; no per-image use; the plan identifies the one consumer they serve)
-                _LAST_STATS[0] = ConvStats(final, cnt, B * plan.Ho * plan.Wo, stats, nblk, 0, plan)
-            else:
-                _LAST_STATS[0] = ConvStats(final, cnt, B * Ho * Wo, stats, nblk, rb, None)
-        else:
-            _LAST_STATS[0] = None
         ctx.save_for_backward(x, weight, bias)
         ctx.cfg = (stride, pad_h, pad_w, dil, Nphys, Ho, Wo)
         ctx.set_materialize_grads(False)
@@ -745,7 +718,7 @@ class _Conv2d(torch.autograd.Function):
                                         "also consumed by an operator outside mrfp_amd.ops (set MRFP_GATED_SKIP=0)")
             cell[1] = False
         if dy is None:            # only the skip alias was used downstream
-            return ungate(dskip), None, None, None, None, None, None, None, None
+            return (ungate(dskip),) + (None,) * 10
         stride, pad_h, pad_w, dil, Nphys, Ho, Wo = ctx.cfg
         dy = _chk(dy, "dy")
         B, Cphys, H, W = x.shape
@@ -814,13 +787,8 @@ class _Conv2d(torch.autograd.Function):
                 elif dw.dtype != weight.dtype:
                     dw = dw.to(weight.dtype)
         if bias is not None and ctx.needs_input_grad[2]:
-            from .ops import _stats_fwd
-            nslab, sws = _stats_fwd(dy, None)
-            out = torch.empty(4 * Nphys, dtype=torch.float32, device=x.device)
-            call("mrfp_bn_finalize", ptr(sws), B, nslab, B * Ho * Wo, Nphys, None, None, 0.0, 0.0, None, None,
-                 ptr(out[:Nphys]), ptr(out[Nphys:2 * Nphys]), ptr(out[2 * Nphys:3 * Nphys]), ptr(out[3 * Nphys:]), stream())
-            db = (out[:N] * float(B * Ho * Wo)).to(bias.dtype)       # column mean * count = column sum
-        return dx, dw, db, None, None, None, None, None, None
+            db = channel_sums(dy, N).to(bias.dtype)
+        return (dx, dw, db) + (None,) * 8
 
 
 class _SharedConv1x1Pair(torch.autograd.Function):
@@ -876,14 +844,7 @@ class _SharedConv1x1Pair(torch.autograd.Function):
                      stream())
                 dws.append(dw)
         if bias is not None and ctx.needs_input_grad[3] and dy2 is not None:
-            from .ops import _stats_fwd
-            d2 = _chk(dy2, "dy")
-            B2, _, H2, W2 = d2.shape
-            nslab, sws = _stats_fwd(d2, None)
-            out = torch.empty(4 * Nphys, dtype=torch.float32, device=d2.device)
-            call("mrfp_bn_finalize", ptr(sws), B2, nslab, B2 * H2 * W2, Nphys, None, None, 0.0, 0.0, None, None,
-                 ptr(out[:Nphys]), ptr(out[Nphys:2 * Nphys]), ptr(out[2 * Nphys:3 * Nphys]), ptr(out[3 * Nphys:]), stream())
-            db = (out[:N] * float(B2 * H2 * W2)).to(bias.dtype)       # column mean * count = column sum
+            db = channel_sums(_chk(dy2, "dy"), N).to(bias.dtype)
         dw = None
         if dws:
             total = dws[0] if len(dws) == 1 else dws[0].add_(dws[1])
@@ -915,10 +876,15 @@ def pad_input_channels(x: torch.Tensor, dtype) -> torch.Tensor:
 
 
 def conv2d(x, weight, bias, stride, padding, dilation, phys_out: Optional[int] = None, want_skip: bool = False,
-           groups: int = 1):
+           groups: int = 1, stat_resize=None):
     """x: [B,Cphys,H,W] channels-last (Cphys >= weight.shape[1], extra channels must be zero);
     returns [B,N,Ho,Wo], or the channel-padded [B,phys_out,Ho,Wo] buffer when phys_out is given.
-    want_skip: returns (y, x_skip) -- see _Conv2d."""
+    want_skip: returns (y, x_skip) -- see _Conv2d.
+    A bias-free convolution feeds a normalisation layer: its epilogue also writes the per-channel partial sums of its output, and
+    the output is tagged with them (y._mrfp_colstats, a ConvStats) for that layer to take instead of a statistics pass.
+    stat_resize: the ops.NearestPlan of a nearest-neighbour resize the output goes through into a training-mode BatchNorm
+    (deepv3.MRFPPlus._hrfp).  The epilogue statistics then count every output pixel as often as the resize reads it
+    (mrfp_conv_fwd_wstats), and the BatchNorm skips its statistics pass over the resized tensor."""
     st = stride[0] if isinstance(stride, (tuple, list)) else int(stride)
     ph, pw = (padding if isinstance(padding, (tuple, list)) else (int(padding), int(padding)))
     dl = dilation[0] if isinstance(dilation, (tuple, list)) else int(dilation)
@@ -936,10 +902,24 @@ def conv2d(x, weight, bias, stride, padding, dilation, phys_out: Optional[int] =
         raise _lib.MrfpHipError("conv2d: weight %s over an input of %d channels (groups=%d) is a grouped convolution; the implicit-GEMM "
                                 "path is dense only" % (tuple(weight.shape), x.shape[1], groups))
     Nphys = phys_out if phys_out is not None else _round_up(N, epc)
-    _LAST_STATS[0] = None
+    B, Cphys, H, W = x.shape
+    R, S = weight.shape[2], weight.shape[3]
+    Ho, Wo = _out_size(H, R, st, ph, dl), _out_size(W, S, st, pw, dl)
+    L = _lib.lib()
+    single = bool(L.mrfp_conv_single_launch(B, H * W * Cphys * x.element_size()))
+    plan, wtab, stats = stat_resize, None, None
+    if plan is not None and WSTATS[0] and FUSE_STATS[0] and single and (plan.Hs, plan.Ws) == (Ho, Wo) and R * S > 1:
+        wtab = plan.multiplicity(B)
+    if wtab is not None or (bias is None and FUSE_STATS[0] and single):
+        lay = (ctypes.c_int64 * 5)()
+        rc = L.mrfp_conv_stats_layout(dt(x), B, H, W, Cphys, Nphys, Nphys, R, S, Ho, Wo, st, ph, pw, dl, 1, int(wtab is not None), lay)
+        if rc != 0:
+            raise _lib.MrfpHipError("mrfp_conv_stats_layout failed (%d): %s" % (rc, L.mrfp_last_error().decode()))
+        nblk, rb, rows, first, cnt = lay
+        stats = torch.empty(rows * 2 * Nphys, dtype=torch.float32, device=x.device)
     if _JOIN_QUEUED[0] and not _in_backward():
         _drop_stale_backward_state()
-    out = _Conv2d.apply(x, weight, bias, st, ph, pw, dl, Nphys, want_skip)
+    out = _Conv2d.apply(x, weight, bias, st, ph, pw, dl, Nphys, want_skip, stats, wtab)
     y, skip = out if want_skip else (out, None)
     if skip is not None:
         skip._mrfp_skip_alias = True      # its gradient goes to this convolution's dgrad epilogue and nowhere else
@@ -947,9 +927,15 @@ def conv2d(x, weight, bias, stride, padding, dilation, phys_out: Optional[int] =
         skip._mrfp_uses = [0, False]
         if y.grad_fn is not None:
             y.grad_fn._mrfp_cell = skip._mrfp_uses     # (the autograd node IS the ctx of _Conv2d.backward)
-    if _LAST_STATS[0] is not None and (phys_out is not None or Nphys == N):
-        y._mrfp_colstats = _LAST_STATS[0]        # consumed by ops.batch_norm_act (statistics pass skipped)
-    _LAST_STATS[0] = None
+    if stats is not None and (phys_out is not None or Nphys == N):
+        # consumed by ops.batch_norm_act (statistics pass skipped).  final: the rows a BatchNorm finalize should read (compacted for
+        # large launches); weighted statistics count the elements of the RESIZED tensor, have no per-image use, and the plan
+        # identifies the one consumer they serve.  (The channel slice below returns a new tensor, without the tag.)
+        final = stats[first * 2 * Nphys:(first + cnt) * 2 * Nphys]
+        if wtab is not None:
+            y._mrfp_colstats = ConvStats(final, cnt, B * plan.Ho * plan.Wo, stats, nblk, 0, plan, y._version)
+        else:
+            y._mrfp_colstats = ConvStats(final, cnt, B * Ho * Wo, stats, nblk, rb, None, y._version)
     if phys_out is None and Nphys != N:
         y = y[:, :N].contiguous(memory_format=CL)
     return (y, skip) if want_skip else y

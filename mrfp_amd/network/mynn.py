@@ -93,16 +93,18 @@ class HipConv2d(nn.Conv2d):
             "(groups == in_channels == out_channels) is" % (self.in_channels, self.out_channels, tuple(self.kernel_size),
                                                             self.groups, tuple(self.weight.shape)))
 
-    def forward(self, x):
+    def forward(self, x, stat_resize=None):
+        """stat_resize: the resize plan between this convolution and its training-mode BatchNorm (ops.conv2d; a depthwise
+        convolution has no weighted statistics and leaves them to the BatchNorm's own pass)."""
         if self._is_depthwise():
             return ops.depthwise_conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
-        return ops.conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
+        return ops.conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation, stat_resize=stat_resize)
 
-    def forward_skip(self, x):
+    def forward_skip(self, x, stat_resize=None):
         """(conv(x), x_skip): x_skip aliases x; its gradient is folded into this conv's dgrad launch."""
         if self._is_depthwise():
             raise ops._lib.MrfpHipError("HipConv2d.forward_skip: not available for a depthwise convolution")
-        return ops.conv2d_skip(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
+        return ops.conv2d_skip(x, self.weight, self.bias, self.stride, self.padding, self.dilation, stat_resize=stat_resize)
 
 
 def fold_state(conv, norm):

@@ -174,7 +174,6 @@ def _stats_bwd(dy, x, y, mean, per_image, plan, fA=None, fS=None):
     return nslab, ws
 
 
-_LAST_PLANESTATS = [None]     # handed from an apply pass that also summed its output to the wrapper that tags the output tensor
 PLANE_STATS = [os.environ.get("MRFP_PLANE_STATS", "1") != "0"]
 PLANE_STATS_HITS = [0]        # statistics passes replaced by the producing apply pass's sums (tests)
 
@@ -189,15 +188,74 @@ def _take_planestats(x):
     return ps[0], ps[1]
 
 
-def _affine_fwd(x, res, A, S, per_image, relu, plan, like=None, emit_stats=False):
+def _planestats_rows(x, want):
+    """(nslab, ws) for the plane sums of an apply pass over x's geometry (the wrapper allocates them, hands ws to its Function,
+    which fills it, and tags the tensor it gets back: autograd re-wraps the output, so forward cannot tag it), or None."""
+    if not (want and PLANE_STATS[0]):
+        return None
+    B, C, H, W = x.shape
+    return _stats_ws(B, H, C, x.device)
+
+
+def _tag_planestats(y, ps):
+    if ps is not None:
+        y._mrfp_planestats = (ps[0], ps[1], y._version)
+    return y
+
+
+def _serving_colstats(x, C, elements, plan, per_image):
+    """The statistics the producing convolution's epilogue wrote (x._mrfp_colstats, a conv.ConvStats) if they serve this consumer,
+    else None: x as the convolution returned it (version stamp), summed over `elements` values per channel, weighted for exactly
+    the resize this consumer applies (`plan`; statistics weighted for a resize serve that one layer only), with whole rows of C
+    channels.  per_image: the consumer needs the raw per-row-block rows (InstanceNorm), else the rows for a BatchNorm finalize."""
+    cs = getattr(x, "_mrfp_colstats", None)
+    if cs is None or cs.version != x._version or cs.resize_plan is not plan or cs.elements != elements:
+        return None
+    if not per_image:
+        return cs if cs.final.numel() == cs.final_count * 2 * C else None
+    # (16-bit activations only: behind the stem convolutions a channel's mean is tens of its standard deviations -- inputs are
+    #  0..255 -- and the fp32 parity criteria of the ill-conditioned fixture resolve the SUMMATION ORDER of its statistics:
+    #  with the epilogue's sums the stem weight gradient of mrfp_c1 moved 0.37 from fp64 where 3x the reference's own fp32
+    #  distance allows 0.19; bf16 storage rounds 10^4 times coarser than that)
+    return cs if IN_FUSED_STATS[0] and x.element_size() == 2 and cs.rows.numel() >= cs.row_blocks * 2 * C else None
+
+
+def channel_sums(dy, n):
+    """fp32 [n]: the sums of dy's first n channels over batch and pixels -- the bias gradient of a convolution.  The statistics pass
+    and a BatchNorm finalize without weights give the column means; times the count."""
+    B, C, H, W = dy.shape
+    nslab, ws = _stats_fwd(dy, None)
+    out = torch.empty(4 * C, dtype=torch.float32, device=dy.device)
+    call("mrfp_bn_finalize", ptr(ws), B, nslab, B * H * W, C, None, None, 0.0, 0.0, None, None,
+         ptr(out[:C]), ptr(out[C:2 * C]), ptr(out[2 * C:3 * C]), ptr(out[3 * C:]), stream())
+    return out[:n] * float(B * H * W)
+
+
+def _grad_dest(param, wanted, tmp):
+    """Where a backward kernel writes d(param): the parameter's slot in the flat gradient arena (grad_sink) or the temporary."""
+    sink = grad_sink(param) if wanted else None
+    return sink if sink is not None else tmp
+
+
+def _grad_result(param, dest):
+    """After the launches that wrote `dest` (_grad_dest): what backward returns for d(param) -- None for a gradient that went to the
+    arena, which is reported (notify_grad) instead."""
+    if param is None:
+        return None
+    if getattr(param, "_mrfp_direct", False) and dest is param.grad:
+        notify_grad(param)
+        return None
+    return dest
+
+
+def _affine_fwd(x, res, A, S, per_image, relu, plan, like=None, stats=None):
+    """stats: rows (_planestats_rows) that also receive the partial plane sums of the stored output."""
     src = x if x is not None else like
     B, Ho, Wo, C, Hs, Ws, tH, tW, _, _ = _geom(src, plan)
     y = empty_cl(B, C, Ho, Wo, src.dtype, src.device)
-    if emit_stats and PLANE_STATS[0] and plan is None and x is not None:
-        nslab, ws = _stats_ws(B, Ho, C, src.device)
+    if stats is not None:
         call("mrfp_affine_fwd_stats", ptr(x), ptr(res), ptr(y), dt(src), B, Ho, Wo, C, ptr(A), ptr(S), int(per_image), int(relu),
-             ptr(ws), stream())
-        _LAST_PLANESTATS[0] = (nslab, ws)
+             ptr(stats), stream())
         return y
     call("mrfp_affine_fwd", ptr(x), ptr(res), ptr(y), dt(src), B, Ho, Wo, C, Hs, Ws, ptr(tH), ptr(tW),
          ptr(A), ptr(S), int(per_image), int(relu), stream())
@@ -309,12 +367,31 @@ def _allreduce_stats(ws, rows, C, count, group):
     return torch.stack([hi, lo]).contiguous(), total
 
 
+ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2      # the activation of a normalisation's apply pass (as conv.conv2d_folded numbers them)
+GATED_BN_HITS = [0]        # BatchNorm backward passes that applied a residual tail's gate to their incoming gradient (tests)
+GATED_BN = [os.environ.get("MRFP_GATED_BN", "1") != "0"]      # (A/B switch for this form alone)
+RELU6_GATE_HITS = [0]      # ReLU6 backward passes that gated with mrfp_mask_gate (fp32 / channel counts off the 8-chunk; tests)
+
+
+def _keeps_sign_mask(x, relu, res, plan):
+    """Residual BatchNorm+ReLU on 16-bit activations: the apply pass writes the sign of its output as one bit per element."""
+    return bool(relu and res is not None and plan is None and SIGN_MASK[0] and x.element_size() == 2 and x.shape[1] % 8 == 0)
+
+
 class _BatchNormAct(torch.autograd.Function):
-    """y = act(BN(resize(x)) + res).  reference: Norm2d/SyncBatchNorm on one process = F.batch_norm
-    (mynn.py:19-25), Bottleneck tail (Resnet.py:202-225), HRFP stage (deepv3.py:320-327)."""
+    """y = act(BN(resize(x)) + res), act one of ACT_NONE / ACT_RELU / ACT_RELU6.  reference: Norm2d/SyncBatchNorm on one process =
+    F.batch_norm (mynn.py:19-25), Bottleneck tail (Resnet.py:202-225), HRFP stage (deepv3.py:320-327); with may_sync false the
+    plain nn.BatchNorm2d of the reference's MobileNetV2 (network/Mobilenet.py: never Norm2d / SyncBatchNorm), whose statistics
+    stay on this process -- it does not even ask for the statistics' communicator, which is created collectively.
+    ReLU6 (nn.ReLU6 = hardtanh(0, 6)): the apply pass writes a 1-bit pass mask of the fp32 PRE-activation, 0 < x*A + S < 6 -- the
+    gate torch applies -- and backward gates dy with it (a rounded 16-bit output cannot tell 5.99 from 6).
+    stats: rows that receive the plane sums of the output (batch_norm_act(emit_stats=True)), or None."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, res, training, momentum, eps, relu, plan, emit_stats=False):
+    def forward(ctx, x, weight, bias, running_mean, running_var, res, training, momentum, eps, act, plan, may_sync, stats):
+        relu, relu6 = act == ACT_RELU, act == ACT_RELU6
+        if relu6 and (res is not None or plan is not None):
+            raise _lib.MrfpHipError("BatchNorm + ReLU6 takes no residual and no resize plan")
         x = _chk(x)
         res = _chk(res, "res") if res is not None else None
         B, Ho, Wo, C, Hs, Ws, *_ = _geom(x, plan)
@@ -323,18 +400,15 @@ class _BatchNormAct(torch.autograd.Function):
         coef = torch.empty(4 * C, dtype=torch.float32, device=dev)
         mean, invstd, A, S = coef[0:C], coef[C:2 * C], coef[2 * C:3 * C], coef[3 * C:4 * C]
         if training:
-            fused = getattr(x, "_mrfp_colstats", None)
-            # (statistics weighted for a resize -- conv.STAT_RESIZE -- only serve the layer that applies exactly that resize)
-            if fused is not None and fused.resize_plan is not plan:
-                fused = None
-            if fused is not None and fused.elements == B * Ho * Wo and fused.final.numel() == fused.final_count * 2 * C:
+            fused = _serving_colstats(x, C, B * Ho * Wo, plan, False)
+            if fused is not None:
                 # the producing convolution already summed its output per channel in its epilogue
                 ws, nb_, nslab = fused.final, 1, fused.final_count
             else:
                 nslab, ws = _stats_fwd(x, plan)
                 nb_ = B
             count = B * Ho * Wo
-            ctx.sync = _sync_bn_group()
+            ctx.sync = _sync_bn_group() if may_sync else None
             if ctx.sync is not None:        # statistics over the batches of ALL ranks (one host synchronisation: the count)
                 ws, count = _allreduce_stats(ws, nb_ * nslab, C, count, ctx.sync)
                 nb_, nslab = 1, 2
@@ -348,39 +422,46 @@ class _BatchNormAct(torch.autograd.Function):
             if x.requires_grad or (weight is not None and weight.requires_grad):
                 mean.copy_(running_mean)                          # what the backward's x-hat is built from
                 torch.rsqrt(running_var.float() + eps, out=invstd)
-        ctx.plan, ctx.relu, ctx.training, ctx.has_res = plan, relu, training, res is not None
+        ctx.plan, ctx.act, ctx.training, ctx.has_res = plan, act, training, res is not None
         # ReLU mask for backward: without a residual it is recomputed from x and the apply coefficients
         # ((x*A+S) > 0, bit-identical to the forward expression), so y is not read again; with a residual the
         # stored output is the only place the sign lives -- and the two backward passes need nothing else of y, so
         # the apply pass also writes its sign as ONE BIT per element (16-bit activations): they then read 1/16 of y's
-        # bytes (3.7 GB of y per step of the bench workload, read twice).
-        keep_y = relu and res is not None
+        # bytes (3.7 GB of y per step of the bench workload, read twice).  (ReLU6 never recomputes: its gate is on the fp32
+        # pre-activation, and its pass mask is written for every dtype and channel count.)
+        ctx.keep_y = relu and res is not None
         ctx.remask = relu and res is None
-        ctx.ymask = bool(keep_y and plan is None and SIGN_MASK[0] and x.element_size() == 2 and C % 8 == 0)
+        ctx.ymask = _keeps_sign_mask(x, relu, res, plan)
         # res is the skip alias of a convolution (conv.conv2d(..., want_skip=True)): its gradient is consumed by that
         # convolution's dgrad epilogue only, which can apply the gate itself -- backward then hands it the incoming
         # gradient as it is, with the mask attached, instead of writing dy * [y > 0]
         ctx.gate_skip = bool(ctx.ymask and GATED_SKIP[0] and getattr(res, "_mrfp_skip_alias", False))
-        # this layer itself can take a gated gradient: plain BatchNorm (no ReLU, no residual, no resize), 16-bit, whole mask bytes
-        ctx.gate_ok = bool(not relu and res is None and plan is None and training and x.element_size() == 2 and C % 8 == 0)
+        # this layer itself can take a gated gradient: plain BatchNorm (no activation, no residual, no resize), 16-bit, whole mask bytes
+        ctx.gate_ok = bool(act == ACT_NONE and res is None and plan is None and training and x.element_size() == 2 and C % 8 == 0)
         # ... provided this tail stays the alias's ONLY consumer: with a second one autograd sums the two gradients into a fresh,
         # untagged tensor and the unmasked one would be used as if it were masked.  Every operator of this layer counts its use
         # of the alias (_chk); the count is read in backward, when the whole forward has run.
         ctx.alias_uses = getattr(res, "_mrfp_uses", None)
-        if ctx.ymask:
+        keep = None
+        if relu6:
             y = empty_cl(B, C, Ho, Wo, x.dtype, dev)
-            mask = torch.empty(B * Ho * Wo * C // 8, dtype=torch.uint8, device=dev)
-            call("mrfp_affine_fwd_relu_mask", ptr(x), ptr(res), ptr(y), ptr(mask), dt(x), B, Ho, Wo, C, ptr(A), ptr(S), 0, stream())
+            keep = torch.empty((B * Ho * Wo * C + 7) // 8, dtype=torch.uint8, device=dev)
+            call("mrfp_affine_fwd_relu6_mask", ptr(x), ptr(y), ptr(keep), dt(x), B * Ho * Wo, C, ptr(A), ptr(S), stream())
+        elif ctx.ymask:
+            y = empty_cl(B, C, Ho, Wo, x.dtype, dev)
+            keep = torch.empty(B * Ho * Wo * C // 8, dtype=torch.uint8, device=dev)
+            call("mrfp_affine_fwd_relu_mask", ptr(x), ptr(res), ptr(y), ptr(keep), dt(x), B, Ho, Wo, C, ptr(A), ptr(S), 0, stream())
         else:
-            y = _affine_fwd(x, res, A, S, False, relu, plan, emit_stats=emit_stats)
-            mask = None
+            y = _affine_fwd(x, res, A, S, False, relu, plan, stats=stats)
+            if ctx.keep_y:
+                keep = y
         ctx.wparam, ctx.bparam = weight, bias
-        ctx.save_for_backward(x, (mask if ctx.ymask else y) if keep_y else None, w32, mean, invstd, A, S)
+        ctx.save_for_backward(x, keep, w32, mean, invstd, A, S)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, y, w32, mean, invstd, A, S = ctx.saved_tensors
+        x, keep, w32, mean, invstd, A, S = ctx.saved_tensors      # keep: the sign / pass mask, or y itself (residual tail without one)
         # A residual tail may hand this layer its incoming gradient UNMASKED with its sign mask attached (this layer is the
         # BatchNorm of a downsample branch: reference Resnet.py:209-212 `residual = self.downsample(x)`; batch_norm_act() marked
         # its output as able to take that): the two passes below then gate dy while they read it, and dy * [out > 0] of the tail
@@ -404,28 +485,39 @@ class _BatchNormAct(torch.autograd.Function):
         plan = ctx.plan
         B, Ho, Wo, C, *_ = _geom(x, plan)
         fA, fS = (A, S) if ctx.remask else (None, None)
-        if gate is not None:               # plain BatchNorm behind a gated gradient: the tail's sign mask is the ReLU gate
-            nslab, ws = _stats_ws(B, Ho, C, x.device)
-            call("mrfp_stats_bwd_mask", ptr(dy), ptr(x), ptr(gate), ptr(mean), 0, dt(x), B, Ho, Wo, C, ptr(ws), stream())
-            nb_ = B
+        # the 1-bit mask the masked kernel pair gates dy with while it reads it: the tail's sign mask behind a gated gradient, this
+        # layer's own sign mask, or its ReLU6 pass mask (16-bit, whole mask bytes; otherwise dy is gated in a pass of its own first)
+        mask = y = None
+        if gate is not None:
+            mask = gate
             GATED_BN_HITS[0] += 1
-        elif ctx.ymask:                    # y holds the sign mask
+        elif ctx.ymask:
+            mask = keep
+        elif ctx.act == ACT_RELU6:
+            if x.element_size() == 2 and C % 8 == 0 and dy.dtype == x.dtype:
+                mask = keep
+            else:
+                gated = torch.empty_like(dy, memory_format=CL)
+                call("mrfp_mask_gate", ptr(dy), ptr(keep), ptr(gated), dt(dy), dy.numel(), stream())
+                dy = gated
+                RELU6_GATE_HITS[0] += 1
+        else:
+            y = keep
+        if mask is not None:
             nslab, ws = _stats_ws(B, Ho, C, x.device)
-            call("mrfp_stats_bwd_mask", ptr(dy), ptr(x), ptr(y), ptr(mean), 0, dt(x), B, Ho, Wo, C, ptr(ws), stream())
-            nb_ = B
+            call("mrfp_stats_bwd_mask", ptr(dy), ptr(x), ptr(mask), ptr(mean), 0, dt(x), B, Ho, Wo, C, ptr(ws), stream())
         else:
             nslab, ws = _stats_bwd(dy, x, y, mean, False, plan, fA, fS)
-            nb_ = B
         out = torch.empty(5 * C, dtype=torch.float32, device=dy.device)
         dw, db, P, Q, R = (out[i * C:(i + 1) * C] for i in range(5))
-        sw = grad_sink(ctx.wparam) if ctx.needs_input_grad[1] else None
-        sb = grad_sink(ctx.bparam) if ctx.needs_input_grad[2] else None
-        call("mrfp_bn_bwd_finalize", ptr(ws), nb_, nslab, B * Ho * Wo, C, ptr(w32), ptr(mean), ptr(invstd),
-             ptr(sw if sw is not None else dw), ptr(sb if sb is not None else db), ptr(P), ptr(Q), ptr(R), stream())
+        dw = _grad_dest(ctx.wparam, ctx.needs_input_grad[1], dw)
+        db = _grad_dest(ctx.bparam, ctx.needs_input_grad[2], db)
+        call("mrfp_bn_bwd_finalize", ptr(ws), B, nslab, B * Ho * Wo, C, ptr(w32), ptr(mean), ptr(invstd),
+             ptr(dw), ptr(db), ptr(P), ptr(Q), ptr(R), stream())
         if ctx.sync is not None:
             # cross-rank statistics: dweight / dbias above are this rank's LOCAL sums (the data-parallel exchange averages
             # them, as with torch.nn.SyncBatchNorm); the input-gradient coefficients use the sums over ALL ranks
-            gws, _ = _allreduce_stats(ws, nb_ * nslab, C, 0, ctx.sync)
+            gws, _ = _allreduce_stats(ws, B * nslab, C, 0, ctx.sync)
             call("mrfp_bn_bwd_finalize", ptr(gws), 1, 2, ctx.count, C, ptr(w32), ptr(mean), ptr(invstd), None, None,
                  ptr(P), ptr(Q), ptr(R), stream())
         if not ctx.training:
@@ -433,44 +525,23 @@ class _BatchNormAct(torch.autograd.Function):
             # gradient is just dy' * weight * invstd -- the batch-statistics terms Q, R vanish
             Q.zero_()
             R.zero_()
-        if gate is not None:
+        if mask is not None:
             dx = empty_cl(B, C, Ho, Wo, dy.dtype, dy.device)
-            dres = None
-            call("mrfp_affine_bwd_mask", ptr(dy), ptr(x), ptr(gate), ptr(dx), None, dt(dy), B, Ho, Wo, C, ptr(P), ptr(Q), ptr(R), 0,
-                 stream())
-        elif ctx.ymask:
-            dx = empty_cl(B, C, Ho, Wo, dy.dtype, dy.device)
-            if ctx.gate_skip and ctx.needs_input_grad[5] and ctx.alias_uses is not None and ctx.alias_uses[0] == 1:
-                dres = dy.view_as(dy)                  # unmasked; the consumer applies the mask (conv._Conv2d.backward / conv.ungate)
-                dres._mrfp_gate = (y, dres._version)
-                # told to the convolution that owns the alias: if what reaches it is not this tagged tensor (a consumer of the alias
-                # that bypassed _chk made autograd sum it into a fresh one), it raises instead of using it as if it were masked
-                ctx.alias_uses[1] = True
-                call("mrfp_affine_bwd_mask", ptr(dy), ptr(x), ptr(y), ptr(dx), None, dt(dy), B, Ho, Wo, C, ptr(P), ptr(Q), ptr(R), 0,
-                     stream())
-            else:
-                dres = empty_cl(B, C, Ho, Wo, dy.dtype, dy.device)
-                call("mrfp_affine_bwd_mask", ptr(dy), ptr(x), ptr(y), ptr(dx), ptr(dres), dt(dy), B, Ho, Wo, C, ptr(P), ptr(Q), ptr(R),
-                     0, stream())
+            dres = dres_out = None
+            if ctx.ymask:
+                if ctx.gate_skip and ctx.needs_input_grad[5] and ctx.alias_uses is not None and ctx.alias_uses[0] == 1:
+                    dres = dy.view_as(dy)                  # unmasked; the consumer applies the mask (conv._Conv2d.backward / conv.ungate)
+                    dres._mrfp_gate = (mask, dres._version)
+                    # told to the convolution that owns the alias: if what reaches it is not this tagged tensor (a consumer of the
+                    # alias that bypassed _chk made autograd sum it into a fresh one), it raises instead of using it as if it were masked
+                    ctx.alias_uses[1] = True
+                else:
+                    dres = dres_out = empty_cl(B, C, Ho, Wo, dy.dtype, dy.device)
+            call("mrfp_affine_bwd_mask", ptr(dy), ptr(x), ptr(mask), ptr(dx), ptr(dres_out), dt(dy), B, Ho, Wo, C, ptr(P), ptr(Q),
+                 ptr(R), 0, stream())
         else:
             dx, dres = _affine_bwd(dy, x, y, P, Q, R, False, plan, ctx.has_res, x, fA, fS)
-        if sw is not None:
-            notify_grad(ctx.wparam)
-            dw = None
-        if sb is not None:
-            notify_grad(ctx.bparam)
-            db = None
-        return dx, dw, db, None, None, dres, None, None, None, None, None, None
-
-
-GATED_BN_HITS = [0]        # BatchNorm backward passes that applied a residual tail's gate to their incoming gradient (tests)
-GATED_BN = [os.environ.get("MRFP_GATED_BN", "1") != "0"]      # (A/B switch for this form alone)
-
-
-def _tag_planestats(y):
-    ps, _LAST_PLANESTATS[0] = _LAST_PLANESTATS[0], None
-    if ps is not None:
-        y._mrfp_planestats = (ps[0], ps[1], y._version)
+        return (dx, _grad_result(ctx.wparam, dw), _grad_result(ctx.bparam, db), None, None, dres) + (None,) * 7
 
 
 # bumped by every training-mode BatchNorm forward: its kernel updates the running statistics in place through raw pointers, which no
@@ -482,11 +553,12 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, *, training, mome
                    relu=False, res=None, plan=None, emit_stats=False):
     """emit_stats: the caller normalises the result per image next (an InstanceNorm `iw` tap behind this residual tail, reference
     Resnet.py:218-225): the apply pass also writes the partial plane sums of its output and that statistics pass is skipped."""
-    _LAST_PLANESTATS[0] = None
     if training and running_mean is not None:
         RUNNING_STATS_EPOCH[0] += 1
-    y = _BatchNormAct.apply(x, weight, bias, running_mean, running_var, res, training, momentum, eps, relu, plan, bool(emit_stats))
-    _tag_planestats(y)
+    ps = _planestats_rows(x, emit_stats and plan is None and not _keeps_sign_mask(x, relu, res, plan))
+    y = _BatchNormAct.apply(x, weight, bias, running_mean, running_var, res, training, momentum, eps,
+                            ACT_RELU if relu else ACT_NONE, plan, True, ps[1] if ps is not None else None)
+    _tag_planestats(y, ps)
     if (GATED_BN[0] and GATED_SKIP[0] and SIGN_MASK[0] and not relu and res is None and plan is None and training and y.grad_fn is not None
             and y.element_size() == 2 and y.shape[1] % 8 == 0):
         # the plain BatchNorm of a downsample branch: a residual tail that consumes this output (and nothing else does: the use
@@ -495,6 +567,22 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, *, training, mome
         y._mrfp_uses = [0, False]
         y.grad_fn._mrfp_cell = y._mrfp_uses
     return y
+
+
+def local_batch_norm_act(x, weight, bias, running_mean, running_var, *, training, momentum=0.1, eps=1e-5, act=None):
+    """BatchNorm over this process's batch (never synchronised across ranks) followed by `act`: None or 'relu6'."""
+    if act not in (None, "relu6"):
+        raise _lib.MrfpHipError("local_batch_norm_act: act must be None or 'relu6' (got %r)" % (act,))
+    if training and running_mean is not None:
+        RUNNING_STATS_EPOCH[0] += 1
+    return _BatchNormAct.apply(x, weight, bias, running_mean, running_var, None, bool(training), momentum, eps,
+                               ACT_RELU6 if act == "relu6" else ACT_NONE, None, False, None)
+
+
+def batch_norm_relu6(x, weight, bias, running_mean, running_var, *, training, momentum=0.1, eps=1e-5):
+    """clamp(BN(x), 0, 6): nn.BatchNorm2d -> nn.ReLU6 (reference network/Mobilenet.py ConvBNReLU)."""
+    return local_batch_norm_act(x, weight, bias, running_mean, running_var, training=training, momentum=momentum, eps=eps,
+                                act="relu6")
 
 
 # ------------------------------------------------------------------------------------------
@@ -510,14 +598,8 @@ def _in_plane_sums(x):
     ps = _take_planestats(x)
     x = _chk(x)
     B, C, H, W = x.shape
-    fused = getattr(x, "_mrfp_colstats", None)
-    # (16-bit activations only: behind the stem convolutions a channel's mean is tens of its standard deviations -- inputs are
-    #  0..255 -- and the fp32 parity criteria of the ill-conditioned fixture resolve the SUMMATION ORDER of its statistics:
-    #  with the epilogue's sums the stem weight gradient of mrfp_c1 moved 0.37 from fp64 where 3x the reference's own fp32
-    #  distance allows 0.19; bf16 storage rounds 10^4 times coarser than that)
-    usable = (IN_FUSED_STATS[0] and x.element_size() == 2 and fused is not None and fused.elements == B * H * W
-              and fused.rows.numel() >= fused.row_blocks * 2 * C)
-    rb = fused.block_rows if usable else 0
+    fused = _serving_colstats(x, C, B * H * W, None, True)
+    rb = fused.block_rows if fused is not None else 0
     if rb < 0 and B * (-rb) == fused.row_blocks:
         # the weight-stationary 3x3 kernel (csrc/conv_c64.hip) writes its statistics rows per IMAGE: -rb rows each
         IN_FUSED_HITS[0] += 1
@@ -534,21 +616,43 @@ def _in_plane_sums(x):
     return x, nslab, ws
 
 
+def _in_finalize(x, nslab, ws, weight, bias, eps):
+    """-> (w32, mean, invstd, A, S): per-(image, channel) statistics and apply coefficients from the plane sums (_in_plane_sums)."""
+    B, C, H, W = x.shape
+    w32, b32 = _f32(weight), _f32(bias)
+    n = B * C
+    coef = torch.empty(4 * n, dtype=torch.float32, device=x.device)
+    mean, invstd, A, S = coef[0:n], coef[n:2 * n], coef[2 * n:3 * n], coef[3 * n:4 * n]
+    call("mrfp_in_finalize", ptr(ws), B, nslab, H * W, C, ptr(w32), ptr(b32), float(eps), ptr(mean),
+         ptr(invstd), ptr(A), ptr(S), stream())
+    return w32, mean, invstd, A, S
+
+
+def _in_bwd_finalize(ctx, x, nslab, ws, w32, mean, invstd):
+    """-> (P, Q, R, dw, db): the input-gradient coefficients from the backward plane sums; dweight / dbias are written where
+    _grad_dest says (the caller returns _grad_result of them after its apply launch)."""
+    B, C, H, W = x.shape
+    n = B * C
+    pqr = torch.empty(3 * n, dtype=torch.float32, device=x.device)
+    P, Q, R = pqr[0:n], pqr[n:2 * n], pqr[2 * n:3 * n]
+    dwb = torch.empty(2 * C, dtype=torch.float32, device=x.device)
+    dw = _grad_dest(ctx.wparam, ctx.wparam is not None, dwb[:C])
+    db = _grad_dest(ctx.bparam, ctx.bparam is not None, dwb[C:])
+    call("mrfp_in_bwd_finalize", ptr(ws), B, nslab, H * W, C, ptr(w32), ptr(mean), ptr(invstd), ptr(dw), ptr(db),
+         ptr(P), ptr(Q), ptr(R), stream())
+    return P, Q, R, dw, db
+
+
 class _InstanceNormAct(torch.autograd.Function):
-    """nn.InstanceNorm2d(affine) (+ReLU): reference Resnet.py:176-178, 218-225, 534-536."""
+    """nn.InstanceNorm2d(affine) (+ReLU): reference Resnet.py:176-178, 218-225, 534-536.
+    stats: rows that receive the plane sums of the output (instance_norm_act(emit_stats=True)), or None."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, eps, relu, emit_stats=False):
+    def forward(ctx, x, weight, bias, eps, relu, stats):
         x, nslab, ws = _in_plane_sums(x)
-        B, C, H, W = x.shape
-        w32, b32 = _f32(weight), _f32(bias)
-        coef = torch.empty(4 * B * C, dtype=torch.float32, device=x.device)
-        n = B * C
-        mean, invstd, A, S = coef[0:n], coef[n:2 * n], coef[2 * n:3 * n], coef[3 * n:4 * n]
-        call("mrfp_in_finalize", ptr(ws), B, nslab, H * W, C, ptr(w32), ptr(b32), float(eps), ptr(mean),
-             ptr(invstd), ptr(A), ptr(S), stream())
-        y = _affine_fwd(x, None, A, S, True, relu, None, emit_stats=emit_stats)
-        ctx.relu, ctx.affine = relu, weight is not None
+        w32, mean, invstd, A, S = _in_finalize(x, nslab, ws, weight, bias, eps)
+        y = _affine_fwd(x, None, A, S, True, relu, None, stats=stats)
+        ctx.relu = relu
         ctx.wparam, ctx.bparam = weight, bias
         ctx.save_for_backward(x, w32, mean, invstd, A, S)
         return y
@@ -557,36 +661,17 @@ class _InstanceNormAct(torch.autograd.Function):
     def backward(ctx, dy):
         x, w32, mean, invstd, A, S = ctx.saved_tensors
         dy = _chk(dy, "dy")
-        B, C, H, W = x.shape
         fA, fS = (A, S) if ctx.relu else (None, None)      # ReLU mask recomputed from x (see _BatchNormAct)
         nslab, ws = _stats_bwd(dy, x, None, mean, True, None, fA, fS)
-        pqr = torch.empty(3 * B * C, dtype=torch.float32, device=dy.device)
-        n = B * C
-        P, Q, R = pqr[0:n], pqr[n:2 * n], pqr[2 * n:3 * n]
-        dwb = torch.empty(2 * C, dtype=torch.float32, device=dy.device)
-        sw = grad_sink(ctx.wparam) if ctx.affine else None
-        sb = grad_sink(ctx.bparam) if ctx.affine else None
-        call("mrfp_in_bwd_finalize", ptr(ws), B, nslab, H * W, C, ptr(w32), ptr(mean), ptr(invstd),
-             ptr(sw if sw is not None else dwb[:C]), ptr(sb if sb is not None else dwb[C:]), ptr(P), ptr(Q), ptr(R), stream())
+        P, Q, R, dw, db = _in_bwd_finalize(ctx, x, nslab, ws, w32, mean, invstd)
         dx, _ = _affine_bwd(dy, x, None, P, Q, R, True, None, False, x, fA, fS)
-        if not ctx.affine:
-            return dx, None, None, None, None, None
-        dw, db = dwb[:C], dwb[C:]
-        if sw is not None:
-            notify_grad(ctx.wparam)
-            dw = None
-        if sb is not None:
-            notify_grad(ctx.bparam)
-            db = None
-        return dx, dw, db, None, None, None
+        return dx, _grad_result(ctx.wparam, dw), _grad_result(ctx.bparam, db), None, None, None
 
 
 def instance_norm_act(x, weight, bias, *, eps=1e-5, relu=False, emit_stats=False):
     """emit_stats: NP+ follows (reference deepv3.py:333-335): the apply pass also writes the partial plane sums of its output."""
-    _LAST_PLANESTATS[0] = None
-    y = _InstanceNormAct.apply(x, weight, bias, eps, relu, bool(emit_stats))
-    _tag_planestats(y)
-    return y
+    ps = _planestats_rows(x, emit_stats)
+    return _tag_planestats(_InstanceNormAct.apply(x, weight, bias, eps, relu, ps[1] if ps is not None else None), ps)
 
 
 # ------------------------------------------------------------------------------------------
@@ -750,17 +835,11 @@ class _InstanceNormReluPool(torch.autograd.Function):
     def forward(ctx, x, weight, bias, eps):
         x, nslab, ws = _in_plane_sums(x)
         B, C, H, W = x.shape
-        w32, b32 = _f32(weight), _f32(bias)
-        n = B * C
-        coef = torch.empty(4 * n, dtype=torch.float32, device=x.device)
-        mean, invstd, A, S = coef[0:n], coef[n:2 * n], coef[2 * n:3 * n], coef[3 * n:4 * n]
-        call("mrfp_in_finalize", ptr(ws), B, nslab, H * W, C, ptr(w32), ptr(b32), float(eps), ptr(mean),
-             ptr(invstd), ptr(A), ptr(S), stream())
+        w32, mean, invstd, A, S = _in_finalize(x, nslab, ws, weight, bias, eps)
         Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         y = empty_cl(B, C, Ho, Wo, x.dtype, x.device)
         idx = torch.empty(B * Ho * Wo * C, dtype=torch.uint8, device=x.device)
         call("mrfp_maxpool_affine_fwd", ptr(x), ptr(A), ptr(S), 1, 1, ptr(y), ptr(idx), dt(x), B, H, W, C, stream())
-        ctx.affine = weight is not None
         ctx.wparam, ctx.bparam = weight, bias
         ctx.save_for_backward(x, idx, w32, mean, invstd, A, S)
         POOL_FUSED_HITS[0] += 1
@@ -774,27 +853,11 @@ class _InstanceNormReluPool(torch.autograd.Function):
         nslab, ws = _stats_ws(B, H, C, x.device)
         call("mrfp_pool_norm_bwd_stats", ptr(dy), ptr(idx), ptr(x), ptr(mean), ptr(A), ptr(S), 1, 1, ptr(ws), dt(x), B, H, W, C,
              stream())
-        n = B * C
-        pqr = torch.empty(3 * n, dtype=torch.float32, device=dy.device)
-        P, Q, R = pqr[0:n], pqr[n:2 * n], pqr[2 * n:3 * n]
-        dwb = torch.empty(2 * C, dtype=torch.float32, device=dy.device)
-        sw = grad_sink(ctx.wparam) if ctx.affine else None
-        sb = grad_sink(ctx.bparam) if ctx.affine else None
-        call("mrfp_in_bwd_finalize", ptr(ws), B, nslab, H * W, C, ptr(w32), ptr(mean), ptr(invstd),
-             ptr(sw if sw is not None else dwb[:C]), ptr(sb if sb is not None else dwb[C:]), ptr(P), ptr(Q), ptr(R), stream())
+        P, Q, R, dw, db = _in_bwd_finalize(ctx, x, nslab, ws, w32, mean, invstd)
         dx = empty_cl(B, C, H, W, dy.dtype, dy.device)
         call("mrfp_pool_norm_bwd_apply", ptr(dy), ptr(idx), ptr(x), ptr(P), ptr(Q), ptr(R), ptr(A), ptr(S), 1, 1, ptr(dx), dt(x),
              B, H, W, C, stream())
-        if not ctx.affine:
-            return dx, None, None, None
-        dw, db = dwb[:C], dwb[C:]
-        if sw is not None:
-            notify_grad(ctx.wparam)
-            dw = None
-        if sb is not None:
-            notify_grad(ctx.bparam)
-            db = None
-        return dx, dw, db, None
+        return dx, _grad_result(ctx.wparam, dw), _grad_result(ctx.bparam, db), None
 
 
 def instance_norm_relu_pool(x, weight, bias, *, eps=1e-5):
@@ -1078,19 +1141,20 @@ def as_activation(x: torch.Tensor) -> torch.Tensor:
     return conv.pad_input_channels(x, cfg.MODEL.ACT_DTYPE)
 
 
-def conv2d_skip(x, weight, bias, stride, padding, dilation):
+def conv2d_skip(x, weight, bias, stride, padding, dilation, stat_resize=None):
     """(conv(x), alias of x for a skip connection): the gradient arriving on the alias is accumulated in this conv's
     dgrad epilogue."""
     from . import conv
-    return conv.conv2d(_chk(x), weight, bias, stride, padding, dilation, None, True)
+    return conv.conv2d(_chk(x), weight, bias, stride, padding, dilation, None, True, stat_resize=stat_resize)
 
 
-def conv2d(x, weight, bias, stride, padding, dilation, phys_out=None):
+def conv2d(x, weight, bias, stride, padding, dilation, phys_out=None, stat_resize=None):
     """nn.Conv2d forward/backward on the MFMA implicit-GEMM kernels (mrfp_amd/conv.py).  phys_out: return the
-    channel-padded output buffer.  There is no other backend: a stock-ROCm (MIOpen) comparison of BASELINE.json
+    channel-padded output buffer.  stat_resize: the NearestPlan of the resize the output goes through into a training-mode
+    BatchNorm (see conv.conv2d).  There is no other backend: a stock-ROCm (MIOpen) comparison of BASELINE.json
     configs[1] was measured once in round 1 and does not live in the product."""
     from . import conv
-    return conv.conv2d(_chk(x), weight, bias, stride, padding, dilation, phys_out)
+    return conv.conv2d(_chk(x), weight, bias, stride, padding, dilation, phys_out, stat_resize=stat_resize)
 
 
 class _ConcatChannels(torch.autograd.Function):
@@ -1616,9 +1680,6 @@ def fourier_amplitude_mix(x, perm, radius, lam=1.0, high=False):
 # ------------------------------------------------------------------------------------------
 # MobileNetV2 layers: depthwise 3x3 convolution, BatchNorm (+ReLU6) that is never synchronised
 # ------------------------------------------------------------------------------------------
-_DW_LAST_STATS = [None]      # handed from _DepthwiseConv2d.forward to depthwise_conv2d() (autograd re-wraps the output tensor)
-
-
 class _DepthwiseConv2d(torch.autograd.Function):
     """nn.Conv2d(C, C, 3, stride, padding=dilation, dilation, groups=C) (reference network/Mobilenet.py ConvBNReLU with
     groups = hidden_dim) on csrc/conv_dw.hip.  x: [B,Cp,H,W] channels-last, Cp = C rounded up to a 16-byte chunk.  The weight
@@ -1626,21 +1687,14 @@ class _DepthwiseConv2d(torch.autograd.Function):
     stream of the MFMA convolutions."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, dil, want_stats):
+    def forward(ctx, x, weight, bias, stride, dil, stats):
         B, Cp, H, W = x.shape
         C = weight.shape[0]
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
         w32 = weight.detach().float().contiguous()
         b32 = _f32(bias)
         y = empty_cl(B, Cp, Ho, Wo, x.dtype, x.device)
-        ws = None
-        if want_stats:
-            nslab = int(_lib.lib().mrfp_dwconv_nslab(dt(x), B, Ho, Cp))
-            ws = torch.empty(B * nslab * 2 * Cp, dtype=torch.float32, device=x.device)
-        call("mrfp_dwconv_fwd", ptr(x), ptr(w32), ptr(b32), ptr(y), dt(x), B, H, W, Cp, C, Ho, Wo, stride, dil, ptr(ws), stream())
-        if ws is not None:
-            from .conv import ConvStats
-            _DW_LAST_STATS[0] = ConvStats(ws, B * nslab, B * Ho * Wo, ws, B * nslab, 0, None)
+        call("mrfp_dwconv_fwd", ptr(x), ptr(w32), ptr(b32), ptr(y), dt(x), B, H, W, Cp, C, Ho, Wo, stride, dil, ptr(stats), stream())
         ctx.save_for_backward(x, w32)
         ctx.geom = (B, Cp, C, H, W, Ho, Wo, stride, dil)
         ctx.wparam, ctx.has_bias = weight, bias is not None
@@ -1672,11 +1726,7 @@ class _DepthwiseConv2d(torch.autograd.Function):
             else:
                 dw = out.to(ctx.wparam.dtype)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            nslab, sws = _stats_fwd(dy, None)
-            out = torch.empty(4 * Cp, dtype=torch.float32, device=dy.device)
-            call("mrfp_bn_finalize", ptr(sws), B, nslab, B * Ho * Wo, Cp, None, None, 0.0, 0.0, None, None,
-                 ptr(out[:Cp]), ptr(out[Cp:2 * Cp]), ptr(out[2 * Cp:3 * Cp]), ptr(out[3 * Cp:]), stream())
-            db = out[:C] * float(B * Ho * Wo)            # column mean * count = column sum
+            db = channel_sums(dy, C)
         return dx, dw, db, None, None, None
 
 
@@ -1704,111 +1754,14 @@ def depthwise_conv2d(x, weight, bias, stride, padding, dilation):
         xp = zeros_cl(x.shape[0], Cp, x.shape[2], x.shape[3], x.dtype, x.device)     # chunk-pad the channels (copy)
         xp[:, :C] = x
         x = xp
-    _DW_LAST_STATS[0] = None
-    want_stats = bias is None and conv.FUSE_STATS[0] and Cp == C
-    y = _DepthwiseConv2d.apply(x, weight, bias, st[0], dl[0], want_stats)
-    stats, _DW_LAST_STATS[0] = _DW_LAST_STATS[0], None
-    if stats is not None:
-        y._mrfp_colstats = stats          # consumed by the BatchNorm behind it (statistics pass skipped)
+    ws = None
+    if bias is None and conv.FUSE_STATS[0] and Cp == C:
+        B, Ho = x.shape[0], (x.shape[2] - 1) // st[0] + 1
+        rows = B * int(_lib.lib().mrfp_dwconv_nslab(dt(x), B, Ho, Cp))
+        ws = torch.empty(rows * 2 * Cp, dtype=torch.float32, device=x.device)
+    y = _DepthwiseConv2d.apply(x, weight, bias, st[0], dl[0], ws)
+    if ws is not None:                    # consumed by the BatchNorm behind it (statistics pass skipped)
+        y._mrfp_colstats = conv.ConvStats(ws, rows, y.numel() // Cp, ws, rows, 0, None, y._version)
     if Cp != C:
         y = y[:, :C].contiguous(memory_format=CL)
     return y
-
-
-RELU6_GATE_HITS = [0]      # ReLU6 backward passes that gated with mrfp_mask_gate (fp32 / channel counts off the 8-chunk; tests)
-
-
-class _LocalBatchNormAct(torch.autograd.Function):
-    """y = act(BN(x)) for act in (None, 'relu6'), statistics over this process's batch only: the plain nn.BatchNorm2d of the
-    reference's MobileNetV2 (network/Mobilenet.py: norm_layer = nn.BatchNorm2d, never Norm2d / SyncBatchNorm).
-    ReLU6 (nn.ReLU6 = hardtanh(0, 6)): the apply pass writes a 1-bit pass mask of the fp32 PRE-activation, 0 < x*A + S < 6 -- the
-    gate torch applies -- and backward gates dy with it (a rounded 16-bit output cannot tell 5.99 from 6)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, running_mean, running_var, training, momentum, eps, act):
-        x = _chk(x)
-        B, C, H, W = x.shape
-        dev = x.device
-        w32, b32 = _f32(weight), _f32(bias)
-        coef = torch.empty(4 * C, dtype=torch.float32, device=dev)
-        mean, invstd, A, S = coef[0:C], coef[C:2 * C], coef[2 * C:3 * C], coef[3 * C:4 * C]
-        if training:
-            fused = getattr(x, "_mrfp_colstats", None)
-            if fused is not None and fused.resize_plan is None and fused.elements == B * H * W \
-                    and fused.final.numel() == fused.final_count * 2 * C:
-                ws, nb_, nslab = fused.final, 1, fused.final_count
-            else:
-                nslab, ws = _stats_fwd(x, None)
-                nb_ = B
-            call("mrfp_bn_finalize", ptr(ws), nb_, nslab, B * H * W, C, ptr(w32), ptr(b32), float(eps), float(momentum),
-                 ptr(running_mean), ptr(running_var), ptr(mean), ptr(invstd), ptr(A), ptr(S), stream())
-        else:
-            call("mrfp_bn_eval_coef", C, ptr(w32), ptr(b32), ptr(running_mean), ptr(running_var), float(eps), ptr(A), ptr(S), stream())
-            if x.requires_grad or (weight is not None and weight.requires_grad):
-                mean.copy_(running_mean)
-                torch.rsqrt(running_var.float() + eps, out=invstd)
-        mask = None
-        if act == "relu6":
-            y = empty_cl(B, C, H, W, x.dtype, dev)
-            mask = torch.empty((B * H * W * C + 7) // 8, dtype=torch.uint8, device=dev)
-            call("mrfp_affine_fwd_relu6_mask", ptr(x), ptr(y), ptr(mask), dt(x), B * H * W, C, ptr(A), ptr(S), stream())
-        else:
-            y = _affine_fwd(x, None, A, S, False, False, None)
-        ctx.training = training
-        ctx.wparam, ctx.bparam = weight, bias
-        ctx.save_for_backward(x, mask, w32, mean, invstd)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, mask, w32, mean, invstd = ctx.saved_tensors
-        dy = _chk(dy, "dy")
-        B, C, H, W = x.shape
-        masked = mask is not None and x.element_size() == 2 and C % 8 == 0 and dy.dtype == x.dtype
-        if mask is not None and not masked:
-            g = torch.empty_like(dy, memory_format=CL)
-            call("mrfp_mask_gate", ptr(dy), ptr(mask), ptr(g), dt(dy), dy.numel(), stream())
-            dy = g
-            RELU6_GATE_HITS[0] += 1
-        if masked:
-            nslab, ws = _stats_ws(B, H, C, x.device)
-            call("mrfp_stats_bwd_mask", ptr(dy), ptr(x), ptr(mask), ptr(mean), 0, dt(x), B, H, W, C, ptr(ws), stream())
-        else:
-            nslab, ws = _stats_bwd(dy, x, None, mean, False, None)
-        out = torch.empty(5 * C, dtype=torch.float32, device=dy.device)
-        dw, db, P, Q, R = (out[i * C:(i + 1) * C] for i in range(5))
-        sw = grad_sink(ctx.wparam) if ctx.needs_input_grad[1] else None
-        sb = grad_sink(ctx.bparam) if ctx.needs_input_grad[2] else None
-        call("mrfp_bn_bwd_finalize", ptr(ws), B, nslab, B * H * W, C, ptr(w32), ptr(mean), ptr(invstd),
-             ptr(sw if sw is not None else dw), ptr(sb if sb is not None else db), ptr(P), ptr(Q), ptr(R), stream())
-        if not ctx.training:
-            Q.zero_()
-            R.zero_()
-        if masked:
-            dx = empty_cl(B, C, H, W, dy.dtype, dy.device)
-            call("mrfp_affine_bwd_mask", ptr(dy), ptr(x), ptr(mask), ptr(dx), None, dt(dy), B, H, W, C, ptr(P), ptr(Q), ptr(R), 0,
-                 stream())
-        else:
-            dx, _ = _affine_bwd(dy, x, None, P, Q, R, False, None, False, x)
-        if sw is not None:
-            notify_grad(ctx.wparam)
-            dw = None
-        if sb is not None:
-            notify_grad(ctx.bparam)
-            db = None
-        return dx, dw, db, None, None, None, None, None, None
-
-
-def local_batch_norm_act(x, weight, bias, running_mean, running_var, *, training, momentum=0.1, eps=1e-5, act=None):
-    """BatchNorm over this process's batch (never synchronised across ranks) followed by `act`: None or 'relu6'."""
-    if act not in (None, "relu6"):
-        raise _lib.MrfpHipError("local_batch_norm_act: act must be None or 'relu6' (got %r)" % (act,))
-    if training and running_mean is not None:
-        RUNNING_STATS_EPOCH[0] += 1
-    return _LocalBatchNormAct.apply(x, weight, bias, running_mean, running_var, bool(training), momentum, eps, act)
-
-
-def batch_norm_relu6(x, weight, bias, running_mean, running_var, *, training, momentum=0.1, eps=1e-5):
-    """clamp(BN(x), 0, 6): nn.BatchNorm2d -> nn.ReLU6 (reference network/Mobilenet.py ConvBNReLU)."""
-    return local_batch_norm_act(x, weight, bias, running_mean, running_var, training=training, momentum=momentum, eps=eps,
-                                act="relu6")

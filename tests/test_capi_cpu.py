@@ -156,3 +156,30 @@ def test_state_dict_abi():
         MRFPPlus(19, trunk="resnet-18")
     with pytest.raises(ValueError):
         simpleDeepV3Plus(19, trunk="resnet-101")
+
+
+def test_operator_layer_has_no_statistics_mailboxes_and_one_batch_norm_function():
+    """Statistics travel from a producer to its wrapper as arguments, not through module globals, and there is one BatchNorm
+    autograd Function; the public wrappers keep their documented keywords."""
+    import inspect
+    import pkgutil
+    import importlib
+    import mrfp_amd
+    from mrfp_amd import conv, ops
+    from mrfp_amd.network import mynn
+    gone = ("_LAST_STATS", "_DW_LAST_STATS", "_LAST_PLANESTATS", "STAT_RESIZE", "_LocalBatchNormAct")
+    for info in pkgutil.walk_packages(mrfp_amd.__path__, "mrfp_amd."):
+        mod = importlib.import_module(info.name)
+        for name in gone:
+            assert not hasattr(mod, name), (info.name, name)
+    kw = lambda f: {k for k, p in inspect.signature(f).parameters.items() if p.kind is p.KEYWORD_ONLY}
+    common = {"training", "momentum", "eps"}
+    assert kw(ops.batch_norm_act) == common | {"relu", "res", "plan", "emit_stats"}
+    assert kw(ops.local_batch_norm_act) == common | {"act"}
+    assert kw(ops.batch_norm_relu6) == common
+    assert kw(ops.instance_norm_act) == {"eps", "relu", "emit_stats"}
+    assert kw(mynn.HipBatchNorm2d.fused) == {"relu", "res", "plan", "emit_stats"} and kw(mynn.HipLocalBatchNorm2d.fused) == {"act"}
+    for f in (conv.conv2d, ops.conv2d, ops.conv2d_skip, mynn.HipConv2d.forward, mynn.HipConv2d.forward_skip):
+        assert "stat_resize" in inspect.signature(f).parameters, f
+    assert "version" in conv.ConvStats._fields and conv.ConvStats._fields[:7] == (
+        "final", "final_count", "elements", "rows", "row_blocks", "block_rows", "resize_plan")

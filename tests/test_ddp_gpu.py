@@ -417,3 +417,40 @@ def test_sync_batchnorm_over_rccl_at_world_size_one(tmp_path):
         for k in ("y", "dx", "dw", "db", "rm", "rv"):
             a, b = got[name][k], full[name][k]
             assert float((a - b).abs().max() / b.abs().max().clamp_min(1e-30)) < 5e-5, (name, k)
+
+
+def _worker_local_bn_never_syncs(outdir):
+    """Set up as _worker_syncbn_rccl: the process group is up and cfg.MODEL.SYNC_BN is on.  ops.local_batch_norm_act (the plain
+    nn.BatchNorm2d of MobileNetV2) exchanges nothing in forward or backward; the same layer through ops.batch_norm_act does."""
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29779", HSA_ENABLE_IPC_MODE_LEGACY="0", MRFP_FORCE_SYNC="1")
+    torch.cuda.set_device(0)
+    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+    sys.path.insert(0, ROOT)
+    from mrfp_amd import ops
+    from mrfp_amd.config import cfg
+    cfg.MODEL.SYNC_BN = True
+    x, _, gy, w, b, _ = _syncbn_case("cuda:0")
+    for fn, expect in ((ops.local_batch_norm_act, 0), (ops.batch_norm_act, 2)):
+        xs = x.detach().clone().requires_grad_(True)
+        ws, bs = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        rm, rv = torch.zeros(64, device="cuda:0"), torch.ones(64, device="cuda:0")
+        before = ops.SYNC_BN_CALLS[0]
+        fn(xs, ws, bs, rm, rv, training=True).backward(gy)
+        torch.cuda.synchronize()
+        assert ops.SYNC_BN_CALLS[0] - before == expect, (fn.__name__, ops.SYNC_BN_CALLS[0] - before)
+        if expect == 0:
+            assert ops._SYNC_BN_GROUP[0] is None          # the statistics' communicator was not even created
+    cfg.MODEL.SYNC_BN = False
+    open(os.path.join(outdir, "local_bn.ok"), "w").write("ok")
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_local_batch_norm_never_synchronises_with_sync_bn_on(tmp_path):
+    ctx = mp.get_context("spawn")
+    p = ctx.Process(target=_worker_local_bn_never_syncs, args=(str(tmp_path),))
+    p.start()
+    p.join(timeout=600)
+    assert p.exitcode == 0
+    assert os.path.exists(os.path.join(str(tmp_path), "local_bn.ok"))

@@ -102,6 +102,43 @@ def test_batch_norm_act(dtype, shape, relu, res):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
+def test_batch_norm_ignores_epilogue_statistics_of_a_convolution_output_modified_in_place(dtype):
+    """The statistics a bias-free convolution's epilogue wrote (y._mrfp_colstats) describe y as the convolution returned it: after
+    an in-place `y.mul_()` the tag's version stamp no longer matches, the BatchNorm runs its own statistics pass (a mrfp_stats_fwd
+    launch) and normalises the MODIFIED tensor -- against its fp64 evaluation, tolerances of test_batch_norm_act.  The unmodified
+    control takes the epilogue's statistics: no mrfp_stats_fwd launch."""
+    o = ops()
+    from mrfp_amd import _lib
+    B, C, N, H, W = 2, 64, 64, 12, 20
+    x = rnd(B, C, H, W, seed=61, scale=3.0, shift=1.5)        # (as test_batch_norm_act: channel means well away from zero)
+    if dtype == torch.bfloat16:
+        x = x.bfloat16().float()
+    w = rnd(N, C, 3, 3, seed=62, scale=(2.0 / (C * 9)) ** 0.5)
+    gam, bet = torch.rand(N) + 0.5, torch.randn(N) * 0.1
+    for modify in (True, False):
+        rm, rv = torch.zeros(N, device=DEV), torch.ones(N, device=DEV)
+        with torch.no_grad():
+            c = o.conv2d(dev(x, dtype).detach(), w.to(DEV), None, 1, 1, 1)
+            assert getattr(c, "_mrfp_colstats", None) is not None
+            if modify:
+                c.mul_(1.75)
+            names = []
+            _lib.HOOK[0] = lambda name, args: names.append(name)
+            try:
+                y = o.batch_norm_act(c, gam.to(DEV), bet.to(DEV), rm, rv, training=True, momentum=0.1, eps=1e-5)
+            finally:
+                _lib.HOOK[0] = None
+        assert ("mrfp_stats_fwd" in names) == modify, names
+        c64 = c.double().cpu()
+        rm64, rv64 = torch.zeros(N, dtype=torch.float64), torch.ones(N, dtype=torch.float64)
+        y64 = F.batch_norm(c64, rm64, rv64, gam.double(), bet.double(), True, 0.1, 1e-5)
+        print("modify", modify, dtype, "y", relerr(y, y64), "rm", relerr(rm, rm64), "rv", relerr(rv, rv64))
+        if modify:
+            assert relerr(y, y64) < tol(dtype)
+            assert relerr(rm, rm64) < 1e-5 and relerr(rv, rv64) < 1e-5 + (0 if dtype == torch.float32 else 1e-2)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("shape", SHAPES[:4])
 @pytest.mark.parametrize("relu,affine", [(False, True), (True, True), (False, False)])
 def test_instance_norm_act(dtype, shape, relu, affine):
@@ -357,9 +394,7 @@ def test_batch_norm_behind_a_resize_takes_its_statistics_from_the_convolution_ep
             rm, rv = torch.zeros(N, device=DEV), torch.ones(N, device=DEV)
             plan = o.nearest_plan(H, W, device=DEV, **rs)
             hits = cv.WSTATS_HITS[0]
-            cv.STAT_RESIZE[0] = plan
-            c = o.conv2d(xd, wd, bd, 1, dil, dil)
-            assert cv.STAT_RESIZE[0] is None
+            c = o.conv2d(xd, wd, bd, 1, dil, dil, stat_resize=plan)
             assert cv.WSTATS_HITS[0] == hits + (1 if fused else 0)
             assert (getattr(c, "_mrfp_colstats", None) is not None) == fused
             y = o.batch_norm_act(c, g, be, rm, rv, training=True, momentum=0.1, eps=1e-5, relu=True, plan=plan)
