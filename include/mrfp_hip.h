@@ -340,6 +340,15 @@ int mrfp_conv_wgrad(const void* x, const void* dy, float* dw, void* ws, int dtyp
  * it differs from the single launch's only in the association of the K' splits.  Each activation must fit one 3.75 GB range. */
 int64_t mrfp_conv_wgrad_group_max(void);
 int64_t mrfp_conv_wgrad_grouped_ws_bytes(int64_t M, int64_t N, int64_t Q, int64_t count);
+/* Host only: the launch plan of mrfp_conv_wgrad (count = 1) / mrfp_conv_wgrad_grouped with the same arguments, after the same argument
+ * checks (of a call that is walked in batch ranges: its first range).
+ *   out[0] kernel   0 conv_wg3_kernel, 1 conv_wg1_kernel, conv_wgrad_kernel's tiles: 2 = 64 x 256, 3 = 128 x 128, 4 = 256 x 128
+ *   out[1] variant  conv_wg3_kernel: strip form 0 / 1 / 2 = 64 x 1, 96 x 1, 48 x 2; the tiles: bit 0 LDS-DMA fill, bit 1 dense X rows
+ *   out[2] splits   fp32 slab slots per problem (splits * count * N * Q * 4 bytes <= what the workspace queries return)
+ *   out[3] klen     pixels behind one slot (K' range of a split; main chunk of the accumulator-stationary kernels)
+ *   out[4] grid     workgroups */
+int mrfp_conv_wgrad_plan(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldn, int64_t R, int64_t S, int64_t Ho,
+                         int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t count, int64_t* out);
 int mrfp_conv_wgrad_grouped(const void* const* xs, const void* const* dys, float* const* dws, int64_t count, void* ws, int dtype,
                             int64_t B, int64_t H, int64_t W, int64_t C, int64_t Ctrue, int64_t N, int64_t ldn,
                             int64_t R, int64_t S, int64_t Ho, int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w,

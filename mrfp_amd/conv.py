@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import call, dt, ptr, stream
-from .ops import CL, GRAD_DEFERRED, _chk, channel_sums, empty_cl, grad_sink, notify_grad, zeros_cl
+from .ops import CL, GRAD_DEFERRED, _chk, channel_sums, empty_cl, grad_sink, notify_grad, wgrad_workspace, zeros_cl
 
 _PACKS = {}      # id(weight Parameter) -> {key: _Pack}; entry dropped when the Parameter dies
 import os as _os
@@ -532,17 +532,16 @@ def _issue_wgrads(sig, items):
     x0 = items[0][0]
     M, Q = B * Ho * Wo, R * S * Cphys
     side = wgrad_stream(x0.device)
-    L = _lib.lib()
 
     def run():
         n = len(items)
         if n == 1:
             x, dy, sink, _ = items[0]
-            ws = torch.empty(int(L.mrfp_conv_wgrad_ws_bytes(M, N, Q)), dtype=torch.uint8, device=x.device)
+            ws = wgrad_workspace(M, N, Q, x.device)
             call("mrfp_conv_wgrad", ptr(x), ptr(dy), ptr(sink), ptr(ws), _lib._DT[dtype], B, H, W, Cphys, C, N, Nphys, R, S,
                  Ho, Wo, stride, pad_h, pad_w, dil, stream())
             return
-        ws = torch.empty(int(L.mrfp_conv_wgrad_grouped_ws_bytes(M, N, Q, n)), dtype=torch.uint8, device=x0.device)
+        ws = wgrad_workspace(M, N, Q, x0.device, n)
         arr = ctypes.c_void_p * n
         xs, dys, dws = arr(*[ptr(i[0]) for i in items]), arr(*[ptr(i[1]) for i in items]), arr(*[ptr(i[2]) for i in items])
         call("mrfp_conv_wgrad_grouped", xs, dys, dws, n, ptr(ws), _lib._DT[dtype], B, H, W, Cphys, C, N, Nphys, R, S,
@@ -765,7 +764,7 @@ class _Conv2d(torch.autograd.Function):
                 main = torch.cuda.current_stream()
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    ws = torch.empty(int(_lib.lib().mrfp_conv_wgrad_ws_bytes(M, N, Q)), dtype=torch.uint8, device=x.device)
+                    ws = wgrad_workspace(M, N, Q, x.device)
                     call("mrfp_conv_wgrad", ptr(x), ptr(dy), ptr(sink), ptr(ws), dt(x), B, H, W, Cphys, C, N, Nphys, R, S,
                          Ho, Wo, stride, pad_h, pad_w, dil, stream())
                 dy.record_stream(side)
@@ -777,7 +776,7 @@ class _Conv2d(torch.autograd.Function):
                 notify_grad(weight)
                 dw = None
             else:
-                ws = torch.empty(int(_lib.lib().mrfp_conv_wgrad_ws_bytes(M, N, Q)), dtype=torch.uint8, device=x.device)
+                ws = wgrad_workspace(M, N, Q, x.device)
                 dw = sink if sink is not None else torch.empty((N, C, R, S), dtype=torch.float32, device=x.device)
                 call("mrfp_conv_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(ws), dt(x), B, H, W, Cphys, C, N, Nphys, R, S, Ho, Wo,
                      stride, pad_h, pad_w, dil, stream())
@@ -838,7 +837,7 @@ class _SharedConv1x1Pair(torch.autograd.Function):
             dxs.append(dx)
             if ctx.needs_input_grad[2]:
                 M = B * H * W
-                ws = torch.empty(int(_lib.lib().mrfp_conv_wgrad_ws_bytes(M, N, C)), dtype=torch.uint8, device=x.device)
+                ws = wgrad_workspace(M, N, C, x.device)
                 dw = torch.empty((N, C, 1, 1), dtype=torch.float32, device=x.device)
                 call("mrfp_conv_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(ws), dt(x), B, H, W, C, C, N, Nphys, 1, 1, H, W, 1, 0, 0, 1,
                      stream())

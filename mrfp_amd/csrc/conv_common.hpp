@@ -23,11 +23,12 @@
 namespace mrfp {
 
 // Launch geometry of the PERSISTENT kernels (conv_c64.hip, conv_wg3.hip, conv_wg1.hip): their grids are "one round" of resident
-// workgroups, and the statistics / slab buffers their callers allocate (the ConvPlan of conv_c64, wg3_splits_bound, wg1_splits_bound,
-// mrfp_conv_wgrad*_ws_bytes) are sized FROM these grids -- every such rule derives from the two constants below.  conv_c64 launches
-// the grid and statistics slots of the same plan its caller's workspace was sized from (conv_plan); the weight-gradient kernels plan
-// their splits separately from their bound functions, so wg3_run / wg1_run check the split they chose against the bound before they
-// launch (an error, never a write past a buffer sized elsewhere).
+// workgroups, and the statistics / slab buffers their callers allocate (the ConvPlan of conv_c64, mrfp_conv_wgrad*_ws_bytes) are sized
+// FROM these grids -- every such rule derives from the two constants below.  conv_c64 launches the grid and statistics slots of the
+// same plan its caller's workspace was sized from (conv_plan).  The weight-gradient workspace is sized from (M, N, Q, count) alone, so
+// its slot bound (class_walk_slots) and the launch plan (class_walk, inside wgrad_plan) are separate code paths over the same
+// constants, and wgrad_run checks the splits of a wg3 / wg1 plan it is about to launch against the slots that bound grants the same
+// call (an error, never a write past a buffer sized elsewhere; a tile plan is the workspace query's own arm).
 //   (kCUs: common.hpp)
 constexpr int kGrid1PerCU = kCUs;               // one resident workgroup per CU (512-register waves: conv_c64 at 128 channels, conv_wg1)
 constexpr int kGrid2PerCU = 2 * kCUs;           // two per CU (conv_c64 at 64 channels, conv_wg3)
@@ -338,22 +339,78 @@ bool pwk_plan(const ConvP& p, int esz, ConvPlan& plan);
 int pwk_run(const ConvP& p, bool is_f16, hipStream_t st, int act = 0);
 
 // ---- weight-stationary 3x3 kernel for the 64-input-channel layers (HRFP ends, stem / layer-1 3x3), conv_c64.hip ---------------
-// accumulator-stationary weight gradient of the 3x3 / stride 1 / dilation <= 2 layers (conv_wg3.hip): slab slots per problem it may use
-// (0: never applicable to such a problem), the rule, the launch (slab layout and reduction: conv_wgrad.hip)
-int64_t wg3_splits_bound(int64_t N, int64_t Q, int64_t count);
-bool wg3_applicable(int dtype_size, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldn, int64_t R, int64_t S, int64_t Ho,
-                    int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t count);
-int wg3_run(const void* const* xs, const void* const* dys, int64_t count, float* slab, bool is_f16, int64_t B, int64_t H, int64_t W, int64_t C,
-            int64_t N, int64_t ldn, int64_t dil, unsigned xbytes, unsigned dybytes, int* splits, hipStream_t st);
-
-// accumulator-stationary weight gradient of the pointwise layers with C % 256 == N % 256 == 0 (conv_wg1.hip)
-int64_t wg1_splits_bound(int64_t N, int64_t Q, int64_t count);
-bool wg1_applicable(int dtype_size, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldn, int64_t R, int64_t S, int64_t Ho,
-                    int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t count);
-int wg1_run(const void* const* xs, const void* const* dys, int64_t count, float* slab, bool is_f16, int64_t M, int64_t C, int64_t N, int64_t ldn,
-            unsigned xbytes, unsigned dybytes, int* splits, hipStream_t st);
-
 bool c64_plan(const ConvP& p, int esz, ConvPlan& plan);      // statistics rows: [image][sub-strip][slot], per image (not per row count)
 int c64_run(const ConvP& p, const ConvPlan& plan, bool is_f16, hipStream_t st, int act = 0);
+
+// ---- launch plan of a weight gradient (conv_wgrad.hip: wgrad_plan) -----------------------------------------------------------------
+// Host only.  The kernels in wgrad_plan's priority order: the accumulator-stationary 3x3 kernel (conv_wg3.hip), the accumulator-stationary
+// pointwise kernel (conv_wg1.hip), then conv_wgrad_kernel's tiles (64 x 256 for N <= 64, 128 x 128, 256 x 128).  All of them write `splits`
+// fp32 slab slots per problem, which wgrad_reduce_kernel sums in a fixed order.
+constexpr int kWgMaxGroup = 32;     // problems of one geometry in one launch
+struct WgGroup {                    // their operand pointers, as a kernel argument of all three kernels
+    const char* x[kWgMaxGroup];
+    const char* dy[kWgMaxGroup];
+};
+inline WgGroup make_wg_group(const void* const* xs, const void* const* dys, int64_t count) {
+    WgGroup g;
+    for (int i = 0; i < kWgMaxGroup; ++i) {
+        g.x[i] = (const char*)xs[i < count ? i : 0];
+        g.dy[i] = (const char*)dys[i < count ? i : 0];
+    }
+    return g;
+}
+
+// The walk of the persistent weight-gradient kernels: `ncls` classes (one accumulator tile each) of U units (pixel runs), `count`
+// problems sharing one round of `per_round` workgroups.  A problem's Wp workgroups: a main chunks of L units per class, walked side by
+// side by the classes; the R units per class they leave go to Wr remainder workgroups (slots a and a + 1 of a class).
+struct ClassWalk {
+    int Wp, a, L, R, Wr, splits;
+};
+inline bool class_walk(int64_t ncls, int64_t U, int per_round, int64_t count, ClassWalk& w) {
+    w.Wp = (int)(per_round / count);
+    if (ncls * U < w.Wp) w.Wp = (int)(ncls * U);
+    w.a = (int)(w.Wp / ncls);
+    if (w.a < 1) return false;                   // fewer workgroups than classes: no side-by-side walk
+    w.L = (int)((ncls * U + w.Wp - 1) / w.Wp);
+    const int64_t main = (int64_t)w.a * w.L < U ? (int64_t)w.a * w.L : U;
+    w.R = (int)(U - main);
+    w.Wr = (int)(w.Wp - w.a * ncls);
+    if (w.R > 0 && w.Wr == 0) return false;      // (cannot happen: Wr == 0 means a * ncls == Wp, so a * L >= U)
+    w.splits = w.a + (w.R > 0 ? 2 : 0);
+    return true;
+}
+// upper bound of ClassWalk::splits over every U, from what mrfp_conv_wgrad*_ws_bytes knows (0: no walk for so many classes)
+inline int64_t class_walk_slots(int64_t ncls, int per_round, int64_t count) {
+    const int64_t a = (per_round / count) / ncls;
+    return a < 1 ? 0 : a + 2;
+}
+struct WgradGeom {                  // one call's arguments (a batch range of it: B, and cap > 0)
+    int esz;                        // bytes per activation element
+    int64_t B, H, W, C, N, ldn, R, S, Ho, Wo, stride, pad_h, pad_w, dil, count;
+    int64_t M() const { return B * Ho * Wo; }
+    int64_t Q() const { return R * S * C; }
+    bool pointwise() const { return R == 1 && S == 1 && stride == 1 && pad_h == 0 && pad_w == 0 && H == Ho && W == Wo; }
+};
+enum class WgradKernel { wg3, wg1, t64x256, t128x128, t256x128 };
+enum { kWgDma = 1, kWgDense = 2 };  // variant bits of the tile kernels: LDS-DMA fill (16-bit types), dense X rows (pointwise)
+struct WgradPlan {
+    WgradKernel kind;
+    int variant;                    // wg3: strip form 0 / 1 / 2 = 64 x 1, 96 x 1, 48 x 2 (pixels x rows per unit); tiles: kWgDma | kWgDense
+    int splits;                     // slab slots per problem
+    int klen;                       // pixels per slot: the K' range of a split (tiles), of a main chunk (wg3 / wg1)
+    int grid;                       // workgroups of the launch
+    int tiles;                      // tile kernels: output tiles per split
+    ClassWalk walk;                 // wg3 / wg1: the walk, units per class, channel blocks of C, classes per problem
+    int U, ncb, ncls;
+    int strips, ups;                // wg3: strips per image row, units per (image, strip, dilation class)
+};
+bool wg3_plan(const WgradGeom& g, WgradPlan& plan);      // false: not a launch for this kernel (plan untouched)
+int64_t wg3_slots(int64_t N, int64_t Q, int64_t count);  // slab slots per problem such a launch may use (0: never applicable)
+int wg3_run(const void* const* xs, const void* const* dys, float* slab, bool is_f16, const WgradGeom& g, const WgradPlan& plan,
+            unsigned xbytes, unsigned dybytes, hipStream_t st);
+bool wg1_plan(const WgradGeom& g, WgradPlan& plan);
+int64_t wg1_slots(int64_t N, int64_t Q, int64_t count);
+int wg1_run(const void* const* xs, const void* const* dys, float* slab, bool is_f16, const WgradGeom& g, const WgradPlan& plan,
+            unsigned xbytes, unsigned dybytes, hipStream_t st);
 
 }  // namespace mrfp

@@ -15,11 +15,6 @@ namespace mrfp {
 typedef __attribute__((ext_vector_type(4))) short wg1_short4;
 typedef __attribute__((address_space(3))) wg1_short4 wg1_lds_short4;
 
-constexpr int kWg1MaxGroup = 32;
-struct Wg1Group {
-    const char* x[kWg1MaxGroup];
-    const char* dy[kWg1MaxGroup];
-};
 struct Wg1P {
     float* slab;             // [problem][splits][N][C] fp32
     int C, N, ldn;
@@ -43,7 +38,7 @@ __device__ __forceinline__ uint4 wg1_frag(const char* lo) {        // pixels 4q 
 }
 
 template <typename T>
-__global__ __launch_bounds__(512, 2) void conv_wg1_kernel(Wg1P p, Wg1Group grp) {
+__global__ __launch_bounds__(512, 2) void conv_wg1_kernel(Wg1P p, WgGroup grp) {
     constexpr int HALF = 4 * 32 * 128;           // one operand of a stage: [4 blocks of 64 channels][32 pixels][128 B] = 16 KB
     constexpr int STAGE = 2 * HALF;
     constexpr int NST = 4;
@@ -172,52 +167,39 @@ __global__ __launch_bounds__(512, 2) void conv_wg1_kernel(Wg1P p, Wg1Group grp) 
 }
 
 // ---------------------------------------------------------------------------------------------
+// MRFP_WGRAD1: 0 = never this kernel, 1 (default) = where the rule in wg1_plan says it pays, 2 = wherever it is legal (tests, A/B runs)
 static int wg1_mode() {
-    // 0: never; 1 (default): where the rule below says; 2: wherever it is legal (tests, A/B runs)
     static const int mode = env_switch("MRFP_WGRAD1", 1);
     return mode;
 }
-struct Wg1Plan {
-    int ncb, ncls, Wp, a, L, R, Wr, splits, U;
-};
-static bool wg1_plan(int64_t M, int64_t C, int64_t N, int64_t count, Wg1Plan& pl) {
-    if (C % 256 || N % 256 || M % 32 || count < 1 || count > kWg1MaxGroup) return false;
-    pl.ncb = (int)(C / 256);
-    pl.ncls = (int)(N / 256) * pl.ncb;
+int64_t wg1_slots(int64_t N, int64_t Q, int64_t count) {
+    if (wg1_mode() == 0 || Q % 256 || N % 256 || count < 1) return 0;
+    return class_walk_slots((N / 256) * (Q / 256), kGrid1PerCU, count);
+}
+bool wg1_plan(const WgradGeom& g, WgradPlan& plan) {
+    if (wg1_mode() == 0 || g.esz != 2) return false;
+    if (!g.pointwise() || (g.ldn & 7) || g.ldn < g.N) return false;
+    const int64_t M = g.M();
+    if (g.C % 256 || g.N % 256 || M % 32 || g.count < 1 || g.count > kWgMaxGroup) return false;
+    WgradPlan pl = {};
+    pl.kind = WgradKernel::wg1;
+    pl.ncb = (int)(g.C / 256);
+    pl.ncls = (int)(g.N / 256) * pl.ncb;
     const int64_t U = M / 32;
     if (U >= (1LL << 30)) return false;
     pl.U = (int)U;
-    pl.Wp = (int)(kGrid1PerCU / count);          // one 512-thread workgroup per CU, one round
-    if ((int64_t)pl.ncls * U < pl.Wp) pl.Wp = (int)((int64_t)pl.ncls * U);
-    pl.a = pl.Wp / pl.ncls;
-    if (pl.a < 1) return false;
-    pl.L = (int)(((int64_t)pl.ncls * U + pl.Wp - 1) / pl.Wp);
-    const int64_t main = (int64_t)pl.a * pl.L < U ? (int64_t)pl.a * pl.L : U;
-    pl.R = (int)(U - main);
-    pl.Wr = pl.Wp - pl.a * pl.ncls;
-    if (pl.R > 0 && pl.Wr == 0) return false;
-    pl.splits = pl.a + (pl.R > 0 ? 2 : 0);
+    if (!class_walk(pl.ncls, U, kGrid1PerCU, g.count, pl.walk)) return false;      // one 512-thread workgroup per CU, one round
+    if (M * g.C * 2 >= (int64_t)kOOB || M * g.ldn * 2 >= (int64_t)kOOB) return false;
+    // a workgroup ends with 256 KB of slab stores: it needs a K' loop in front of them
+    if (wg1_mode() < 2 && pl.walk.L < 48) return false;
+    pl.splits = pl.walk.splits;
+    pl.klen = pl.walk.L * 32;
+    pl.grid = (int)(g.count * pl.walk.Wp);
+    plan = pl;
     return true;
 }
-int64_t wg1_splits_bound(int64_t N, int64_t Q, int64_t count) {
-    if (wg1_mode() == 0 || Q % 256 || N % 256 || count < 1) return 0;
-    const int64_t ncls = (N / 256) * (Q / 256);
-    const int64_t a = (kGrid1PerCU / count) / ncls;
-    return a < 1 ? 0 : a + 2;
-}
-bool wg1_applicable(int dtype_size, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldn, int64_t R, int64_t S, int64_t Ho,
-                    int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t count) {
-    if (wg1_mode() == 0 || dtype_size != 2) return false;
-    if (R != 1 || S != 1 || stride != 1 || Ho != H || Wo != W || pad_h != 0 || pad_w != 0 || (ldn & 7) || ldn < N) return false;
-    Wg1Plan pl;
-    const int64_t M = B * H * W;
-    if (!wg1_plan(M, C, N, count, pl)) return false;
-    if (M * C * 2 >= (int64_t)kOOB || M * ldn * 2 >= (int64_t)kOOB) return false;
-    if (wg1_mode() >= 2) return true;
-    return pl.L >= 48;          // a workgroup ends with 256 KB of slab stores: it needs a K' loop in front of them
-}
 template <typename T>
-static int wg1_launch(const Wg1P& q, const Wg1Group& g, int grid, hipStream_t st) {
+static int wg1_launch(const Wg1P& q, const WgGroup& g, int grid, hipStream_t st) {
     const int lds = 4 * 32768;
     static bool attr_set = false;
     if (!attr_set) {
@@ -228,29 +210,18 @@ static int wg1_launch(const Wg1P& q, const Wg1Group& g, int grid, hipStream_t st
     MRFP_LAUNCH_CHECK();
     return 0;
 }
-// the caller (wgrad_run, conv_wgrad.hip) has checked wg1_applicable(); returns the slab slots per problem in *splits
-int wg1_run(const void* const* xs, const void* const* dys, int64_t count, float* slab, bool is_f16, int64_t M, int64_t C, int64_t N, int64_t ldn,
-            unsigned xbytes, unsigned dybytes, int* splits, hipStream_t st) {
-    Wg1Plan pl;
-    if (!wg1_plan(M, C, N, count, pl)) return -1;
-    // the slab the caller sized through wg1_splits_bound() holds that many slots per problem
-    MRFP_CHECK(pl.splits <= wg1_splits_bound(N, C, count) && (int64_t)count * pl.Wp <= kGrid1PerCU,
-               "conv_wg1: %d slab slots per problem / %lld workgroups exceed the workspace rule (%lld)", pl.splits,
-               (long long)(count * pl.Wp), (long long)wg1_splits_bound(N, C, count));
+// `plan`: what wg1_plan() filled for this g
+int wg1_run(const void* const* xs, const void* const* dys, float* slab, bool is_f16, const WgradGeom& g, const WgradPlan& plan,
+            unsigned xbytes, unsigned dybytes, hipStream_t st) {
+    const ClassWalk& w = plan.walk;
     Wg1P q;
     q.slab = slab;
-    q.C = (int)C; q.N = (int)N; q.ldn = (int)ldn;
-    q.U = pl.U; q.ncb = pl.ncb; q.ncls = pl.ncls;
-    q.Wp = pl.Wp; q.a = pl.a; q.L = pl.L; q.R = pl.R; q.Wr = pl.Wr; q.splits = pl.splits;
+    q.C = (int)g.C; q.N = (int)g.N; q.ldn = (int)g.ldn;
+    q.U = plan.U; q.ncb = plan.ncb; q.ncls = plan.ncls;
+    q.Wp = w.Wp; q.a = w.a; q.L = w.L; q.R = w.R; q.Wr = w.Wr; q.splits = plan.splits;
     q.xbytes = xbytes; q.dybytes = dybytes;
-    Wg1Group g;
-    for (int i = 0; i < kWg1MaxGroup; ++i) {
-        g.x[i] = (const char*)xs[i < count ? i : 0];
-        g.dy[i] = (const char*)dys[i < count ? i : 0];
-    }
-    *splits = pl.splits;
-    const int grid = (int)(count * pl.Wp);
-    return is_f16 ? wg1_launch<f16>(q, g, grid, st) : wg1_launch<bf16>(q, g, grid, st);
+    const WgGroup grp = make_wg_group(xs, dys, g.count);
+    return is_f16 ? wg1_launch<f16>(q, grp, plan.grid, st) : wg1_launch<bf16>(q, grp, plan.grid, st);
 }
 
 }  // namespace mrfp

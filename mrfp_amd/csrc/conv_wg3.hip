@@ -25,11 +25,6 @@ namespace mrfp {
 typedef __attribute__((ext_vector_type(4))) short wg3_short4;
 typedef __attribute__((address_space(3))) wg3_short4 wg3_lds_short4;
 
-constexpr int kWg3MaxGroup = 32;
-struct Wg3Group {
-    const char* x[kWg3MaxGroup];
-    const char* dy[kWg3MaxGroup];
-};
 struct Wg3P {
     float* slab;             // [problem][splits][N][Q] fp32
     int B, H, W, C, N, ldn, d;
@@ -55,7 +50,7 @@ __device__ __forceinline__ uint4 wg3_frag(const char* lo, const char* hi) {
 
 // SW: strip width in pixels (a multiple of 16); RU: output rows per unit (RU * SW a multiple of 32)
 template <typename T, int SW, int RU>
-__global__ __launch_bounds__(256, 2) void conv_wg3_kernel(Wg3P p, Wg3Group grp) {
+__global__ __launch_bounds__(256, 2) void conv_wg3_kernel(Wg3P p, WgGroup grp) {
     constexpr int HL = 2;                          // halo pixels either side of a window row (the largest dilation)
     constexpr int NPX = (SW + 2 * HL + 7) / 8;     // 1 KiB pieces (8 pixels x 128 B) per window row
     constexpr int XSLOT = NPX * 1024;
@@ -248,65 +243,46 @@ __global__ __launch_bounds__(256, 2) void conv_wg3_kernel(Wg3P p, Wg3Group grp) 
 }
 
 // ---------------------------------------------------------------------------------------------
+// MRFP_WGRAD3: 0 = never this kernel, 1 (default) = where the rule in wg3_plan says it pays, 2 = wherever it is legal (tests, A/B runs)
 static int wg3_mode() {
-    // 0: never; 1 (default): where the rule below says; 2: wherever it is legal (tests, A/B runs)
     static const int mode = env_switch("MRFP_WGRAD3", 1);
     return mode;
 }
-// strip width / rows per unit for image width W: 64 x 1, 96 x 1 or 48 x 2 (0: none)
-static int wg3_strip(int64_t W, int& ru) {
-    ru = 1;
-    if (W % 64 == 0) return 64;
-    if (W % 96 == 0) return 96;
-    if (W % 48 == 0) { ru = 2; return 48; }
-    return 0;
+// slab slots per problem a launch of this kernel may use, from what mrfp_conv_wgrad*_ws_bytes knows (N, Q, count)
+int64_t wg3_slots(int64_t N, int64_t Q, int64_t count) {
+    if (wg3_mode() == 0 || Q % (9 * 64) || N % 64 || count < 1) return 0;
+    return class_walk_slots((N / 64) * (Q / (9 * 64)), kGrid2PerCU, count);
 }
-struct Wg3Plan {
-    int sw, ru, ncb, ncls, Wp, a, L, R, Wr, splits, ups, strips, U;
-};
-static bool wg3_plan(int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t dil, int64_t count, Wg3Plan& pl) {
-    pl.sw = wg3_strip(W, pl.ru);
-    if (!pl.sw || C % 64 || N % 64 || dil < 1 || dil > 2 || H % (dil * pl.ru)) return false;
-    pl.ncb = (int)(C / 64);
-    pl.ncls = (int)(N / 64) * pl.ncb;
-    pl.strips = (int)(W / pl.sw);
-    pl.ups = (int)(H / (dil * pl.ru));
-    const int64_t U = B * pl.strips * dil * pl.ups;
+bool wg3_plan(const WgradGeom& g, WgradPlan& plan) {
+    if (wg3_mode() == 0 || g.esz != 2) return false;
+    if (g.R != 3 || g.S != 3 || g.stride != 1 || g.Ho != g.H || g.Wo != g.W || g.pad_h != g.dil || g.pad_w != g.dil || (g.ldn & 7)) return false;
+    // strip width x rows per unit for the image width: 64 x 1, 96 x 1 or 48 x 2
+    WgradPlan pl = {};
+    pl.kind = WgradKernel::wg3;
+    pl.variant = g.W % 64 == 0 ? 0 : g.W % 96 == 0 ? 1 : g.W % 48 == 0 ? 2 : -1;
+    if (pl.variant < 0) return false;
+    const int sw = pl.variant == 0 ? 64 : pl.variant == 1 ? 96 : 48, ru = pl.variant == 2 ? 2 : 1;
+    if (g.C % 64 || g.N % 64 || g.dil < 1 || g.dil > 2 || g.H % (g.dil * ru) || g.count < 1 || g.count > kWgMaxGroup) return false;
+    pl.ncb = (int)(g.C / 64);
+    pl.ncls = (int)(g.N / 64) * pl.ncb;
+    pl.strips = (int)(g.W / sw);
+    pl.ups = (int)(g.H / (g.dil * ru));
+    const int64_t U = g.B * pl.strips * g.dil * pl.ups;
     if (U >= (1LL << 30)) return false;
     pl.U = (int)U;
-    pl.Wp = (int)(kGrid2PerCU / count);          // two workgroups per CU, one round
-    if ((int64_t)pl.ncls * U < pl.Wp) pl.Wp = (int)((int64_t)pl.ncls * U);
-    pl.a = pl.Wp / pl.ncls;
-    if (pl.a < 1) return false;                  // fewer workgroups than classes: no side-by-side walk
-    pl.L = (int)(((int64_t)pl.ncls * U + pl.Wp - 1) / pl.Wp);
-    const int64_t main = (int64_t)pl.a * pl.L < U ? (int64_t)pl.a * pl.L : U;
-    pl.R = (int)(U - main);
-    pl.Wr = pl.Wp - pl.a * pl.ncls;
-    if (pl.R > 0 && pl.Wr == 0) return false;    // (cannot happen: Wr == 0 means a * ncls == Wp, so a * L >= U)
-    pl.splits = pl.a + (pl.R > 0 ? 2 : 0);
-    return true;
-}
-// upper bound of the slab slots per problem such a launch may use, from what mrfp_conv_wgrad*_ws_bytes knows (N, Q, count)
-int64_t wg3_splits_bound(int64_t N, int64_t Q, int64_t count) {
-    if (wg3_mode() == 0 || Q % (9 * 64) || N % 64 || count < 1) return 0;
-    const int64_t ncls = (N / 64) * (Q / (9 * 64));
-    const int64_t a = (kGrid2PerCU / count) / ncls;
-    return a < 1 ? 0 : a + 2;
-}
-bool wg3_applicable(int dtype_size, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldn, int64_t R, int64_t S, int64_t Ho,
-                    int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t count) {
-    if (wg3_mode() == 0 || dtype_size != 2) return false;
-    if (R != 3 || S != 3 || stride != 1 || Ho != H || Wo != W || pad_h != dil || pad_w != dil || (ldn & 7)) return false;
-    Wg3Plan pl;
-    if (!wg3_plan(B, H, W, C, N, dil, count, pl)) return false;
-    if (B * H * W * C * 2 >= (int64_t)kOOB || B * H * W * ldn * 2 >= (int64_t)kOOB) return false;
-    if (wg3_mode() >= 2) return true;
+    if (!class_walk(pl.ncls, U, kGrid2PerCU, g.count, pl.walk)) return false;      // two workgroups per CU, one round
+    if (g.B * g.H * g.W * g.C * 2 >= (int64_t)kOOB || g.B * g.H * g.W * g.ldn * 2 >= (int64_t)kOOB) return false;
     // every workgroup first fills a window (RU + 2 rows) and ends with 144 KB of slab stores: it needs a K' loop behind them
-    return pl.L >= 24;
+    if (wg3_mode() < 2 && pl.walk.L < 24) return false;
+    pl.splits = pl.walk.splits;
+    pl.klen = pl.walk.L * ru * sw;
+    pl.grid = (int)(g.count * pl.walk.Wp);
+    plan = pl;
+    return true;
 }
 
 template <typename T, int SW, int RU>
-static int wg3_launch(const Wg3P& q, const Wg3Group& g, int grid, hipStream_t st) {
+static int wg3_launch(const Wg3P& q, const WgGroup& g, int grid, hipStream_t st) {
     constexpr int NPX = (SW + 4 + 7) / 8;
     const int lds = (2 * RU + 2) * NPX * 1024 + 2 * (RU * SW / 8) * 1024;
     static bool attr_set = false;
@@ -319,35 +295,24 @@ static int wg3_launch(const Wg3P& q, const Wg3Group& g, int grid, hipStream_t st
     return 0;
 }
 template <typename T>
-static int wg3_pick(const Wg3Plan& pl, const Wg3P& q, const Wg3Group& g, int grid, hipStream_t st) {
-    if (pl.sw == 64) return wg3_launch<T, 64, 1>(q, g, grid, st);
-    if (pl.sw == 96) return wg3_launch<T, 96, 1>(q, g, grid, st);
+static int wg3_pick(int form, const Wg3P& q, const WgGroup& g, int grid, hipStream_t st) {
+    if (form == 0) return wg3_launch<T, 64, 1>(q, g, grid, st);
+    if (form == 1) return wg3_launch<T, 96, 1>(q, g, grid, st);
     return wg3_launch<T, 48, 2>(q, g, grid, st);
 }
 
-// the caller (wgrad_run, conv_wgrad.hip) has checked wg3_applicable(); returns the slab slots per problem in *splits
-int wg3_run(const void* const* xs, const void* const* dys, int64_t count, float* slab, bool is_f16, int64_t B, int64_t H, int64_t W, int64_t C,
-            int64_t N, int64_t ldn, int64_t dil, unsigned xbytes, unsigned dybytes, int* splits, hipStream_t st) {
-    Wg3Plan pl;
-    if (!wg3_plan(B, H, W, C, N, dil, count, pl) || count > kWg3MaxGroup) return -1;
-    // the slab the caller sized through wg3_splits_bound() holds that many slots per problem
-    MRFP_CHECK(pl.splits <= wg3_splits_bound(N, 9 * C, count) && (int64_t)count * pl.Wp <= kGrid2PerCU,
-               "conv_wg3: %d slab slots per problem / %lld workgroups exceed the workspace rule (%lld)", pl.splits,
-               (long long)(count * pl.Wp), (long long)wg3_splits_bound(N, 9 * C, count));
+// `plan`: what wg3_plan() filled for this g
+int wg3_run(const void* const* xs, const void* const* dys, float* slab, bool is_f16, const WgradGeom& g, const WgradPlan& plan,
+            unsigned xbytes, unsigned dybytes, hipStream_t st) {
+    const ClassWalk& w = plan.walk;
     Wg3P q;
     q.slab = slab;
-    q.B = (int)B; q.H = (int)H; q.W = (int)W; q.C = (int)C; q.N = (int)N; q.ldn = (int)ldn; q.d = (int)dil;
-    q.strips = pl.strips; q.ups = pl.ups; q.U = pl.U; q.ncb = pl.ncb; q.ncls = pl.ncls;
-    q.Wp = pl.Wp; q.a = pl.a; q.L = pl.L; q.R = pl.R; q.Wr = pl.Wr; q.splits = pl.splits; q.Q = (int)(9 * C);
+    q.B = (int)g.B; q.H = (int)g.H; q.W = (int)g.W; q.C = (int)g.C; q.N = (int)g.N; q.ldn = (int)g.ldn; q.d = (int)g.dil;
+    q.strips = plan.strips; q.ups = plan.ups; q.U = plan.U; q.ncb = plan.ncb; q.ncls = plan.ncls;
+    q.Wp = w.Wp; q.a = w.a; q.L = w.L; q.R = w.R; q.Wr = w.Wr; q.splits = plan.splits; q.Q = (int)(9 * g.C);
     q.xbytes = xbytes; q.dybytes = dybytes;
-    Wg3Group g;
-    for (int i = 0; i < kWg3MaxGroup; ++i) {
-        g.x[i] = (const char*)xs[i < count ? i : 0];
-        g.dy[i] = (const char*)dys[i < count ? i : 0];
-    }
-    *splits = pl.splits;
-    const int grid = (int)(count * pl.Wp);
-    return is_f16 ? wg3_pick<f16>(pl, q, g, grid, st) : wg3_pick<bf16>(pl, q, g, grid, st);
+    const WgGroup grp = make_wg_group(xs, dys, g.count);
+    return is_f16 ? wg3_pick<f16>(plan.variant, q, grp, plan.grid, st) : wg3_pick<bf16>(plan.variant, q, grp, plan.grid, st);
 }
 
 }  // namespace mrfp

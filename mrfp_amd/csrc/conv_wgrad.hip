@@ -50,15 +50,10 @@ struct WgP {
 };
 
 // GROUPED launch: up to kWgMaxGroup weight-gradient problems of ONE geometry (the repeated blocks of a ResNet stage:
-// reference network/Resnet.py:579-585 _make_layer) in one grid.  The operand pointers travel in the kernel arguments (no
-// device-side table, no copy, graph-capturable); the work index is problem-major, so with the XCD-chunked order the tiles of
-// one problem share one L2.  22x the tiles of a layer-3 launch means 2-3 K' splits instead of 21-32: K' loops of ~190 tiles
-// per workgroup instead of 12 behind the same prologue, and 1/10 of the fp32 slab traffic.
-constexpr int kWgMaxGroup = 32;
-struct WgGroup {
-    const char* x[kWgMaxGroup];
-    const char* dy[kWgMaxGroup];
-};
+// reference network/Resnet.py:579-585 _make_layer) in one grid.  The operand pointers travel in the kernel arguments (WgGroup,
+// conv_common.hpp: no device-side table, no copy, graph-capturable); the work index is problem-major, so with the XCD-chunked order
+// the tiles of one problem share one L2.  22x the tiles of a layer-3 launch means 2-3 K' splits instead of 21-32: K' loops of ~190
+// tiles per workgroup instead of 12 behind the same prologue, and 1/10 of the fp32 slab traffic.
 struct WgOut {
     float* dw[kWgMaxGroup];
 };
@@ -416,7 +411,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 }
 
 template <typename T, int WM, int WN, bool DMA, bool DENSE = false, int TMB = 2>
-static int launch_wgrad_v(const WgP& p, int splits, hipStream_t st, const WgGroup* grp) {
+static int launch_wgrad_v(const WgP& p, const WgradPlan& pl, hipStream_t st, const WgGroup* grp) {
     constexpr int BNN = 32 * TMB * WM;
     constexpr int PY = BNN * (int)sizeof(T) + (DMA ? 0 : 64), PX = 64 * WN * (int)sizeof(T) + (DMA ? 0 : 64);
     // MRFP_WGRAD_LDS=<bytes> (experiments: tools/overlap_micro.py): ask for at least that much LDS per workgroup, i.e. cap the
@@ -432,37 +427,49 @@ static int launch_wgrad_v(const WgP& p, int splits, hipStream_t st, const WgGrou
         attr_set = true;
     }
     WgP q = p;
-    q.tiles = ((p.N + BNN - 1) / BNN) * ((p.Q + 64 * WN - 1) / (64 * WN));
-    q.splits = splits;
-    hipLaunchKernelGGL((conv_wgrad_kernel<T, WM, WN, DMA, DENSE, TMB>), dim3((unsigned)(q.tiles * splits * q.ngroup)), dim3(256), lds, st, q, *grp);
+    q.tiles = pl.tiles;
+    q.splits = pl.splits;
+    q.klen = pl.klen;
+    hipLaunchKernelGGL((conv_wgrad_kernel<T, WM, WN, DMA, DENSE, TMB>), dim3((unsigned)pl.grid), dim3(256), lds, st, q, *grp);
     MRFP_LAUNCH_CHECK();
     return 0;
 }
 
-// MRFP_WGRAD_DMA=0 keeps register staging for the 16-bit types (A/B measurements); fp32 always stages in registers
+// the instance of conv_wgrad_kernel a tile plan names (WM = 1: the 64 x 256 tile)
 template <typename T, int WM, int WN>
-static int launch_wgrad(const WgP& p, int splits, hipStream_t st, const WgGroup* grp, int tmb = 2) {
-    static const int dma = env_switch("MRFP_WGRAD_DMA", 1);
-    if (sizeof(T) == 2 && dma) {
-        static const int dense = env_switch("MRFP_WGRAD_DENSE", 1);
-        const bool pointwise = p.R == 1 && p.S == 1 && p.stride == 1 && p.pad_h == 0 && p.pad_w == 0 && p.H == p.Ho && p.W == p.Wo;
+static int launch_wgrad(const WgP& p, const WgradPlan& pl, hipStream_t st, const WgGroup* grp) {
+    if (pl.variant & kWgDma) {
+        const bool dense = pl.variant & kWgDense;
         if constexpr (WM == 2 && sizeof(T) == 2) {
-            if (tmb == 4) {
-                if (dense && pointwise) return launch_wgrad_v<T, WM, WN, true, true, 4>(p, splits, st, grp);
-                return launch_wgrad_v<T, WM, WN, true, false, 4>(p, splits, st, grp);
+            if (pl.kind == WgradKernel::t256x128) {
+                if (dense) return launch_wgrad_v<T, WM, WN, true, true, 4>(p, pl, st, grp);
+                return launch_wgrad_v<T, WM, WN, true, false, 4>(p, pl, st, grp);
             }
         }
-        if (dense && pointwise) return launch_wgrad_v<T, WM, WN, sizeof(T) == 2, true>(p, splits, st, grp);
-        return launch_wgrad_v<T, WM, WN, sizeof(T) == 2>(p, splits, st, grp);
+        if (dense) return launch_wgrad_v<T, WM, WN, sizeof(T) == 2, true>(p, pl, st, grp);
+        return launch_wgrad_v<T, WM, WN, sizeof(T) == 2>(p, pl, st, grp);
     }
-    return launch_wgrad_v<T, WM, WN, false>(p, splits, st, grp);
+    return launch_wgrad_v<T, WM, WN, false>(p, pl, st, grp);
+}
+template <typename T>
+static int launch_wgrad_tiles(const WgP& p, const WgradPlan& pl, hipStream_t st, const WgGroup* grp) {
+    return pl.kind == WgradKernel::t64x256 ? launch_wgrad<T, 1, 4>(p, pl, st, grp) : launch_wgrad<T, 2, 2>(p, pl, st, grp);
 }
 
+// MRFP_WGRAD_DMA=0 keeps register staging for the 16-bit types (A/B measurements); fp32 always stages in registers
+static int wgrad_dma_mode() {
+    static const int dma = env_switch("MRFP_WGRAD_DMA", 1);
+    return dma;
+}
 // MRFP_WGRAD_BIG: 0 = never the 256 x 128 tile, 1 (default) = where the cost model prefers it, 2 = wherever it is legal (A/B runs)
 static int wgrad_big_mode() {
     // (MRFP_WGRAD_DMA=0: the register-staged A/B path of the 16-bit kernels has no 256 x 128 instance)
-    static const int mode = env_switch("MRFP_WGRAD_DMA", 1) == 0 ? 0 : env_switch("MRFP_WGRAD_BIG", 1);
+    static const int mode = wgrad_dma_mode() == 0 ? 0 : env_switch("MRFP_WGRAD_BIG", 1);
     return mode;
+}
+static int wgrad_debug_drop() {      // timing-only diagnostics (see mrfp_conv_fwd)
+    static const int dbg_drop = env_switch("MRFP_DEBUG_DROP", 0);
+    return dbg_drop;
 }
 
 // Split count from a small cost model (times in us, constants fitted to the bench workload's per-launch timings):
@@ -470,37 +477,33 @@ static int wgrad_big_mode() {
 //   by a latency-hiding efficiency (fewer co-resident workgroups than the kernel's occupancy hide less of each other's fill
 //   latency); every split adds an fp32 slab of dW that is written once and read once by the reduction (~3 TB/s).
 // MRFP_WGRAD_WGS=<n> replaces the model by "about n workgroups" (A/B measurements).
-static double wgrad_cost(int64_t tiles, int64_t nkt, int64_t group, double nq, double step, int occ, int64_t& sp_out) {
+static int64_t wgrad_cost_splits(int64_t tiles, int64_t nkt, int64_t group, double nq, double step, int occ) {
     static const int target = env_switch("MRFP_WGRAD_WGS", 0);
+    if (target > 0) return target / tiles;
     int64_t sp = 1;
     double best = 1e30;
-    if (target > 0) {
-        sp = target / tiles;
-    } else {
-        int64_t smax = 1024 / tiles > 96 ? 1024 / tiles : 96;      // few tiles: enough splits to fill the chip
-        if (smax > nkt) smax = nkt;
-        for (int64_t c = 1; c <= smax; ++c) {
-            const int64_t w = (tiles * c + 255) / 256, iters = (nkt + c - 1) / c;
-            const double eff = occ == 4 ? (w >= 3 ? 1.0 : w == 2 ? 0.85 : 0.6) : (w >= 2 ? 1.0 : 0.7);
-            const double cost = (double)w * (double)iters * step / eff + (double)c * (double)group * (nq * 8.0 / 3.0e6);
-            if (cost < best * 0.999) { best = cost; sp = c; }
-        }
+    int64_t smax = 1024 / tiles > 96 ? 1024 / tiles : 96;      // few tiles: enough splits to fill the chip
+    if (smax > nkt) smax = nkt;
+    for (int64_t c = 1; c <= smax; ++c) {
+        const int64_t w = (tiles * c + 255) / 256, iters = (nkt + c - 1) / c;
+        const double eff = occ == 4 ? (w >= 3 ? 1.0 : w == 2 ? 0.85 : 0.6) : (w >= 2 ? 1.0 : 0.7);
+        const double cost = (double)w * (double)iters * step / eff + (double)c * (double)group * (nq * 8.0 / 3.0e6);
+        if (cost < best * 0.999) { best = cost; sp = c; }
     }
-    sp_out = sp;
-    return best;
+    return sp;
 }
 
-// wm: wave rows (1: the 64 x 256 tile for N <= 64; 2: 128 x 128 or, tmb = 4, 256 x 128); splits / klen: K' splits and pixels per split
-static void wgrad_plan(int64_t M, int64_t N, int64_t Q, int bkp, int& wm, int& splits, int& klen, int64_t cap = 0, int64_t group = 1,
-                       int* tmb_out = nullptr, bool pointwise = false) {
-    wm = N <= 64 ? 1 : 2;
-    const int wn = 4 / wm;
+// The conv_wgrad_kernel arm of wgrad_plan: tile, K' splits and grid for `group` problems of M pixels, N output channels and Q = R*S*C
+// columns -- all the workspace queries know of a call, so they read this arm directly.  cap > 0: at most that many splits.
+static WgradPlan wgrad_tile_plan(int64_t M, int64_t N, int64_t Q, int esz, bool pointwise, int64_t group, int64_t cap) {
+    WgradPlan pl = {};
+    const int bkp = esz == 4 ? 32 : 64;          // pixels per K' tile (WgTile)
+    const int wm = N <= 64 ? 1 : 2, wn = 4 / wm;
     // (a grouped launch: `group` problems of this geometry fill the chip together; the split count is per problem)
-    const int64_t tiles = group * ((N + 64 * wm - 1) / (64 * wm)) * ((Q + 64 * wn - 1) / (64 * wn));
+    int64_t tiles = ((N + 64 * wm - 1) / (64 * wm)) * ((Q + 64 * wn - 1) / (64 * wn));
     const int64_t nkt = (M + bkp - 1) / bkp;
-    int64_t sp = 1;
-    (void)wgrad_cost(tiles, nkt, group, (double)N * (double)Q, 0.84, 4, sp);
-    int tmb = 2;
+    int64_t sp = wgrad_cost_splits(group * tiles, nkt, group, (double)N * (double)Q, 0.84, 4);
+    pl.kind = wm == 1 ? WgradKernel::t64x256 : WgradKernel::t128x128;
     // The 256 x 128 tile: 16-bit LDS-DMA kernels (K' tile of 64 pixels), whole 256-channel tiles.  Two workgroups per CU hide less
     // fill latency than four, so it needs LONG K' loops to pay -- measured per launch class of the bench step (tools/wgrad_micro.py,
     // MRFP_WGRAD_BIG=0 / 2, same box): the grouped layer-3 pointwise launches 28.7 -> 26.0 us per problem, 512 <-> 2048 grouped
@@ -508,24 +511,72 @@ static void wgrad_plan(int64_t M, int64_t N, int64_t Q, int bkp, int& wm, int& s
     // (every split gets ~10 K' tiles), and the 3x3 layers at 48^2 47.2 -> 49.2 us per problem even grouped.  Rule: enough K' tile-steps
     // per CU (`load`, in 256 x 128 units), and for the gather (non-pointwise) form only the large images.
     if (bkp == 64 && wm == 2 && N % 256 == 0 && wgrad_big_mode() > 0) {
-        const int64_t tiles4 = group * (N / 256) * ((Q + 127) / 128);
-        const int64_t load = tiles4 * nkt / 256;
+        const int64_t tiles4 = (N / 256) * ((Q + 127) / 128);
+        const int64_t load = group * tiles4 * nkt / 256;
         const bool want = load >= 100 && (pointwise || M >= 65536);
         if (wgrad_big_mode() >= 2 || want) {
-            int64_t sp4 = 1;
-            (void)wgrad_cost(tiles4, nkt, group, (double)N * (double)Q, 1.30, 2, sp4);
-            tmb = 4;
-            sp = sp4;
+            sp = wgrad_cost_splits(group * tiles4, nkt, group, (double)N * (double)Q, 1.30, 2);
+            tiles = tiles4;
+            pl.kind = WgradKernel::t256x128;
         }
     }
-    if (tmb_out) *tmb_out = tmb;
+    if (esz == 2 && wgrad_dma_mode()) {
+        static const int dense = env_switch("MRFP_WGRAD_DENSE", 1);
+        pl.variant = kWgDma | (dense && pointwise ? kWgDense : 0);
+    }
     if (sp < 1) sp = 1;
     if (sp > nkt) sp = nkt;
-    if (cap > 0 && sp > cap) sp = cap;         // (a batch range of a larger call: the workspace was sized for the whole call)
-    int64_t per = (nkt + sp - 1) / sp;        // K' tiles per split
-    sp = (nkt + per - 1) / per;
-    splits = (int)sp;
-    klen = (int)(per * bkp);
+    if (cap > 0 && sp > cap) sp = cap;
+    const int64_t per = (nkt + sp - 1) / sp;      // K' tiles per split
+    pl.splits = (int)((nkt + per - 1) / per);
+    pl.klen = (int)(per * bkp);
+    pl.tiles = (int)tiles;
+    pl.grid = (int)(tiles * pl.splits * group);
+    return pl;
+}
+
+// The launch plan of one weight-gradient call.  cap > 0: g is a batch range of a larger call whose workspace holds `cap` slots per
+// problem (the whole call's own split count) -- the tile kernels only, as the accumulator-stationary ones walk whole activations.
+static WgradPlan wgrad_plan(const WgradGeom& g, int64_t cap = 0) {
+    WgradPlan pl;
+    if (cap == 0 && !wgrad_debug_drop() && (wg3_plan(g, pl) || wg1_plan(g, pl))) return pl;
+    return wgrad_tile_plan(g.M(), g.N, g.Q(), g.esz, g.pointwise(), g.count, cap);
+}
+
+// slab slots per problem the workspace of a call holds: the maximum over what (M, N, Q, count) leaves open -- the slot bounds of the
+// accumulator-stationary kernels, if Q could be 9 * C resp. C, and the element size and pointwise form of the tile arm
+static int64_t wgrad_ws_slots(int64_t M, int64_t N, int64_t Q, int64_t count) {
+    int64_t slots = wg3_slots(N, Q, count);
+    if (wg1_slots(N, Q, count) > slots) slots = wg1_slots(N, Q, count);
+    for (int arm = 0; arm < 3; ++arm) {      // 16-bit gather, 16-bit pointwise, fp32 (no pointwise rule)
+        const int s = wgrad_tile_plan(M, N, Q, arm < 2 ? 2 : 4, arm == 1, count, 0).splits;
+        if (s > slots) slots = s;
+    }
+    return slots;
+}
+
+// The argument checks of a call that its plan depends on (the launch and mrfp_conv_wgrad_plan); fills g with the whole call.
+// Both operands are read through 32-bit buffer-descriptor offsets: an activation above kOOB bytes is walked in ranges of `bmax` images
+struct WgradCall {
+    WgradGeom g;
+    int64_t ximg, yimg, bmax;       // bytes of one image of x / dy; images per launch
+};
+static int wgrad_call(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldn, int64_t R, int64_t S, int64_t Ho,
+                      int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t count, WgradCall& c) {
+    MRFP_CHECK(count > 0 && count <= kWgMaxGroup && B > 0 && H > 0 && W > 0 && C > 0 && N > 0 && R > 0 && S > 0 && Ho > 0 && Wo > 0,
+               "conv_wgrad: bad arguments");
+    MRFP_CHECK(dtype == MRFP_F32 || dtype == MRFP_BF16 || dtype == MRFP_F16, "conv_wgrad: unknown dtype %d", dtype);
+    const int esz = dtype == MRFP_F32 ? 4 : 2;
+    MRFP_CHECK((C * esz) % 16 == 0 && (ldn * esz) % 16 == 0 && ldn >= N,
+               "conv_wgrad: channel counts must make 16-byte chunks (C=%lld ldn=%lld)", (long long)C, (long long)ldn);
+    MRFP_CHECK(B * Ho * Wo < (1LL << 31), "conv_wgrad: tensor too large");
+    c.g = WgradGeom{esz, B, H, W, C, N, ldn, R, S, Ho, Wo, stride, pad_h, pad_w, dil, count};
+    c.ximg = H * W * C * esz;
+    c.yimg = Ho * Wo * ldn * esz;
+    MRFP_CHECK(c.ximg < (int64_t)kOOB && c.yimg < (int64_t)kOOB, "conv_wgrad: one image exceeds the 3.75 GB buffer-descriptor range");
+    c.bmax = (int64_t)(kOOB - 1) / (c.ximg > c.yimg ? c.ximg : c.yimg);
+    MRFP_CHECK(count == 1 || c.bmax >= B, "conv_wgrad_grouped: the activations of a grouped launch must fit one 3.75 GB buffer range each");
+    return 0;
 }
 
 }  // namespace mrfp
@@ -534,80 +585,77 @@ using namespace mrfp;
 
 extern "C" {
 
-int64_t mrfp_conv_wgrad_ws_bytes(int64_t M, int64_t N, int64_t Q) {
-    int wm, s32, s64, klen;
-    int s64p;
-    mrfp::wgrad_plan(M, N, Q, 32, wm, s32, klen);         // fp32 K' tile
-    mrfp::wgrad_plan(M, N, Q, 64, wm, s64, klen);         // bf16 K' tile
-    mrfp::wgrad_plan(M, N, Q, 64, wm, s64p, klen, 0, 1, nullptr, true);      // ... of a pointwise launch (its tile rule differs)
-    if (s64p > s64) s64 = s64p;
-    const int64_t s3 = mrfp::wg3_splits_bound(N, Q, 1);       // the accumulator-stationary 3x3 kernel (conv_wg3.hip), if Q could be 9 * C
-    if (s3 > s64) s64 = (int)s3;
-    const int64_t s1 = mrfp::wg1_splits_bound(N, Q, 1);       // ... and the pointwise one (conv_wg1.hip)
-    if (s1 > s64) s64 = (int)s1;
-    return (int64_t)(s32 > s64 ? s32 : s64) * N * Q * 4;
+int64_t mrfp_conv_wgrad_grouped_ws_bytes(int64_t M, int64_t N, int64_t Q, int64_t count) {
+    return wgrad_ws_slots(M, N, Q, count) * count * N * Q * 4;
+}
+int64_t mrfp_conv_wgrad_ws_bytes(int64_t M, int64_t N, int64_t Q) { return mrfp_conv_wgrad_grouped_ws_bytes(M, N, Q, 1); }
+
+int mrfp_conv_wgrad_plan(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldn, int64_t R, int64_t S, int64_t Ho,
+                         int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t count, int64_t* out) {
+    MRFP_CHECK(out, "conv_wgrad_plan: null output");
+    WgradCall c;
+    if (int rc = wgrad_call(dtype, B, H, W, C, N, ldn, R, S, Ho, Wo, stride, pad_h, pad_w, dil, count, c)) return rc;
+    WgradPlan pl = wgrad_plan(c.g);
+    if (c.bmax < B) {                // (walked in batch ranges: the first one's launch)
+        c.g.B = c.bmax;
+        pl = wgrad_plan(c.g, pl.splits);
+    }
+    out[0] = (int64_t)pl.kind; out[1] = pl.variant; out[2] = pl.splits; out[3] = pl.klen; out[4] = pl.grid;
+    return 0;
 }
 
 static int wgrad_run(const void* const* xs, const void* const* dys, float* const* dws, int64_t count, void* ws, int dtype, int64_t B,
                      int64_t H, int64_t W, int64_t C, int64_t Ctrue, int64_t N, int64_t ldn, int64_t R, int64_t S, int64_t Ho,
                      int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, void* stream) {
-    MRFP_CHECK(xs && dys && dws && ws && count > 0 && count <= kWgMaxGroup && B > 0 && H > 0 && W > 0 && C > 0 && N > 0 && R > 0 && S > 0 &&
-               Ho > 0 && Wo > 0, "conv_wgrad: bad arguments");
-    MRFP_CHECK(dtype == MRFP_F32 || dtype == MRFP_BF16 || dtype == MRFP_F16, "conv_wgrad: unknown dtype %d", dtype);
-    const int esz = dtype == MRFP_F32 ? 4 : 2;
-    MRFP_CHECK((C * esz) % 16 == 0 && (ldn * esz) % 16 == 0 && ldn >= N && Ctrue <= C,
-               "conv_wgrad: channel counts must make 16-byte chunks (C=%lld ldn=%lld)", (long long)C, (long long)ldn);
+    MRFP_CHECK(xs && dys && dws && ws, "conv_wgrad: bad arguments");
+    WgradCall c;
+    if (int rc = wgrad_call(dtype, B, H, W, C, N, ldn, R, S, Ho, Wo, stride, pad_h, pad_w, dil, count, c)) return rc;
+    MRFP_CHECK(Ctrue <= C, "conv_wgrad: Ctrue=%lld exceeds the channel pitch C=%lld", (long long)Ctrue, (long long)C);
     for (int64_t g = 0; g < count; ++g)
         MRFP_CHECK(xs[g] && dys[g] && dws[g] && aligned16(xs[g]) && aligned16(dys[g]), "conv_wgrad: x / dy must be 16-byte aligned, dw non-null");
-    MRFP_CHECK(B * Ho * Wo < (1LL << 31), "conv_wgrad: tensor too large");
     WgP p;
-    p.x = (const char*)xs[0]; p.dy = (const char*)dys[0]; p.slab = (float*)ws;
-    p.B = (int)B; p.H = (int)H; p.W = (int)W; p.C = (int)C; p.N = (int)N; p.ldn = (int)ldn;
+    p.slab = (float*)ws;
+    p.H = (int)H; p.W = (int)W; p.C = (int)C; p.N = (int)N; p.ldn = (int)ldn;
     p.R = (int)R; p.S = (int)S; p.Ho = (int)Ho; p.Wo = (int)Wo;
     p.stride = (int)stride; p.pad_h = (int)pad_h; p.pad_w = (int)pad_w; p.dil = (int)dil;
     p.Q = (int)(R * S * C);
     p.ngroup = (int)count;
-    WgGroup grp;
-    WgOut outs;
-    for (int g = 0; g < kWgMaxGroup; ++g) {
-        grp.x[g] = (const char*)xs[g < count ? g : 0];
-        grp.dy[g] = (const char*)dys[g < count ? g : 0];
-        outs.dw[g] = dws[g < count ? g : 0];
-    }
-    // Both operands are read through 32-bit buffer-descriptor offsets: an activation above kOOB bytes is walked in batch
-    // ranges, every range one wgrad + reduction pair on the stream, the later ones adding to dw (fixed order: reproducible)
-    const int64_t ximg = H * W * C * esz, yimg = Ho * Wo * ldn * esz;
-    MRFP_CHECK(ximg < (int64_t)kOOB && yimg < (int64_t)kOOB, "conv_wgrad: one image exceeds the 3.75 GB buffer-descriptor range");
-    int64_t bmax = (int64_t)(kOOB - 1) / (ximg > yimg ? ximg : yimg);
-    MRFP_CHECK(count == 1 || bmax >= B, "conv_wgrad_grouped: the activations of a grouped launch must fit one 3.75 GB buffer range each");
-    static const int dbg_drop = env_switch("MRFP_DEBUG_DROP", 0);      // timing-only diagnostics (see mrfp_conv_fwd)
     p.div_hw = make_fastdiv((unsigned)(Ho * Wo)); p.div_w = make_fastdiv((unsigned)Wo);
+    const WgGroup grp = make_wg_group(xs, dys, count);
+    WgOut outs;
+    for (int g = 0; g < kWgMaxGroup; ++g) outs.dw[g] = dws[g < count ? g : 0];
     hipStream_t st = (hipStream_t)stream;
-    int wm0, cap, klen0;
-    const bool pointwise = R == 1 && S == 1 && stride == 1 && pad_h == 0 && pad_w == 0 && H == Ho && W == Wo;
-    wgrad_plan(B * Ho * Wo, N, p.Q, dtype == MRFP_F32 ? 32 : 64, wm0, cap, klen0, 0, count, nullptr, pointwise);     // what `ws` was sized for
-    for (int64_t b0 = 0; b0 < B; b0 += bmax) {
-        const int64_t bc = B - b0 < bmax ? B - b0 : bmax;
-        p.B = (int)bc;
-        p.M = (int)(bc * Ho * Wo);
-        p.x = (const char*)xs[0] + b0 * ximg;
-        p.dy = (const char*)dys[0] + b0 * yimg;
-        p.xbytes = (dbg_drop & 1) ? 0u : (unsigned)(bc * ximg);
-        p.dybytes = (dbg_drop & 2) ? 0u : (unsigned)(bc * yimg);
-        int wm, splits, tmb = 2;
-        wgrad_plan(p.M, N, p.Q, dtype == MRFP_F32 ? 32 : 64, wm, splits, p.klen, cap, count, &tmb, pointwise);
+    // the plan of the whole call: its splits are what `ws` must hold, and the cap of the batch ranges of a call that is walked in several
+    const WgradPlan whole = wgrad_plan(c.g);
+    // A tile plan is the workspace query's own arm for this element size and form.  The accumulator-stationary kernels plan through
+    // class_walk and are granted slots through class_walk_slots, a term of the query's maximum: that pair is checked here.
+    if (whole.kind == WgradKernel::wg3 || whole.kind == WgradKernel::wg1) {
+        const int64_t slots = whole.kind == WgradKernel::wg3 ? wg3_slots(N, p.Q, count) : wg1_slots(N, p.Q, count);
+        MRFP_CHECK(whole.splits <= slots, "conv_wgrad: the launch plan needs %d slab slots per problem, mrfp_conv_wgrad*_ws_bytes grants %lld",
+                   whole.splits, (long long)slots);
+    }
+    const int dbg_drop = wgrad_debug_drop();
+    // every range is one wgrad + reduction pair on the stream, the later ones adding to dw (fixed order: reproducible)
+    for (int64_t b0 = 0; b0 < B; b0 += c.bmax) {
+        WgradGeom g = c.g;
+        g.B = B - b0 < c.bmax ? B - b0 : c.bmax;
+        const WgradPlan pl = g.B == B ? whole : wgrad_plan(g, whole.splits);
+        p.B = (int)g.B;
+        p.M = (int)g.M();
+        p.x = (const char*)xs[0] + b0 * c.ximg;
+        p.dy = (const char*)dys[0] + b0 * c.yimg;
+        p.xbytes = (dbg_drop & 1) ? 0u : (unsigned)(g.B * c.ximg);
+        p.dybytes = (dbg_drop & 2) ? 0u : (unsigned)(g.B * c.yimg);
         int rc;
-        if (bc == B && !dbg_drop && wg3_applicable(esz, B, H, W, C, N, ldn, R, S, Ho, Wo, stride, pad_h, pad_w, dil, count))
-            rc = wg3_run(xs, dys, count, (float*)ws, dtype == MRFP_F16, B, H, W, C, N, ldn, dil, p.xbytes, p.dybytes, &splits, st);
-        else if (bc == B && !dbg_drop && wg1_applicable(esz, B, H, W, C, N, ldn, R, S, Ho, Wo, stride, pad_h, pad_w, count))
-            rc = wg1_run(xs, dys, count, (float*)ws, dtype == MRFP_F16, B * H * W, C, N, ldn, p.xbytes, p.dybytes, &splits, st);
-        else if (dtype == MRFP_F32) rc = wm == 1 ? launch_wgrad<float, 1, 4>(p, splits, st, &grp) : launch_wgrad<float, 2, 2>(p, splits, st, &grp);
-        else if (dtype == MRFP_F16) rc = wm == 1 ? launch_wgrad<f16, 1, 4>(p, splits, st, &grp) : launch_wgrad<f16, 2, 2>(p, splits, st, &grp, tmb);
-        else rc = wm == 1 ? launch_wgrad<bf16, 1, 4>(p, splits, st, &grp) : launch_wgrad<bf16, 2, 2>(p, splits, st, &grp, tmb);
+        if (pl.kind == WgradKernel::wg3) rc = wg3_run(xs, dys, (float*)ws, dtype == MRFP_F16, g, pl, p.xbytes, p.dybytes, st);
+        else if (pl.kind == WgradKernel::wg1) rc = wg1_run(xs, dys, (float*)ws, dtype == MRFP_F16, g, pl, p.xbytes, p.dybytes, st);
+        else if (dtype == MRFP_F32) rc = launch_wgrad_tiles<float>(p, pl, st, &grp);
+        else if (dtype == MRFP_F16) rc = launch_wgrad_tiles<f16>(p, pl, st, &grp);
+        else rc = launch_wgrad_tiles<bf16>(p, pl, st, &grp);
         if (rc) return rc;
         const int64_t total4 = N * (int64_t)p.Q / 4;          // Q = R*S*C and C*esz % 16 == 0  =>  Q % 4 == 0
         const int64_t blocks = (total4 + 63) / 64;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks, (unsigned)count), dim3(256), 0, st, (const float*)ws, splits, (int)N,
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks, (unsigned)count), dim3(256), 0, st, (const float*)ws, pl.splits, (int)N,
                            p.Q, (int)C, (int)Ctrue, (int)(R * S), dws[0], b0 > 0 ? 1 : 0, outs);
         MRFP_LAUNCH_CHECK();
     }
@@ -621,20 +669,6 @@ int mrfp_conv_wgrad(const void* x, const void* dy, float* dw, void* ws, int dtyp
 }
 
 int64_t mrfp_conv_wgrad_group_max(void) { return kWgMaxGroup; }
-
-int64_t mrfp_conv_wgrad_grouped_ws_bytes(int64_t M, int64_t N, int64_t Q, int64_t count) {
-    int wm, s32, s64, klen;
-    int s64p;
-    mrfp::wgrad_plan(M, N, Q, 32, wm, s32, klen, 0, count);
-    mrfp::wgrad_plan(M, N, Q, 64, wm, s64, klen, 0, count);
-    mrfp::wgrad_plan(M, N, Q, 64, wm, s64p, klen, 0, count, nullptr, true);
-    if (s64p > s64) s64 = s64p;
-    const int64_t s3 = mrfp::wg3_splits_bound(N, Q, count);
-    if (s3 > s64) s64 = (int)s3;
-    const int64_t s1 = mrfp::wg1_splits_bound(N, Q, count);
-    if (s1 > s64) s64 = (int)s1;
-    return (int64_t)(s32 > s64 ? s32 : s64) * count * N * Q * 4;
-}
 
 int mrfp_conv_wgrad_grouped(const void* const* xs, const void* const* dys, float* const* dws, int64_t count, void* ws, int dtype,
                             int64_t B, int64_t H, int64_t W, int64_t C, int64_t Ctrue, int64_t N, int64_t ldn, int64_t R, int64_t S,

@@ -30,6 +30,11 @@ GRAD_DEFERRED = set()      # id(param) of weights whose gradient launch is queue
                            # post-accumulate hook fires for them all the same and must not count them as arrived (harness.GradSync)
 
 
+def wgrad_workspace(M, N, Q, device, n=1):
+    """Scratch of one mrfp_conv_wgrad (n = 1) / mrfp_conv_wgrad_grouped launch: n problems of M pixels, N output channels, Q = R*S*C."""
+    return torch.empty(int(_lib.lib().mrfp_conv_wgrad_grouped_ws_bytes(M, N, Q, n)), dtype=torch.uint8, device=device)
+
+
 def grad_sink(param):
     """The tensor a backward kernel should write d(param) into, or None for the ordinary autograd return path."""
     if param is not None and getattr(param, "_mrfp_direct", False) and param.grad is not None \
@@ -1292,7 +1297,7 @@ class _CrossGram(torch.autograd.Function):
         if (Ca * esz) % 16 or (Cb * esz) % 16 or a.dtype != b.dtype or b.shape[0] != B or b.shape[2:] != a.shape[2:]:
             raise _lib.MrfpHipError("cross_gram: channel counts must make 16-byte chunks and shapes must match")
         G = torch.empty(B, Ca, Cb, dtype=torch.float32, device=a.device)
-        ws = torch.empty(int(_lib.lib().mrfp_conv_wgrad_ws_bytes(H * W, Ca, Cb)), dtype=torch.uint8, device=a.device)
+        ws = wgrad_workspace(H * W, Ca, Cb, a.device)
         abytes, bbytes = H * W * Ca * esz, H * W * Cb * esz
         for i in range(B):
             call("mrfp_conv_wgrad", b.data_ptr() + i * bbytes, a.data_ptr() + i * abytes, G.data_ptr() + i * Ca * Cb * 4,

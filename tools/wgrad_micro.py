@@ -20,6 +20,7 @@ SHAPES = [(16, 48, 48, 256, 1024, 1, 1, 0, 1, 23), (16, 48, 48, 1024, 256, 1, 1,
           (16, 192, 192, 64, 256, 1, 1, 0, 1, 3), (16, 96, 96, 512, 256, 1, 1, 0, 1, 1), (16, 48, 48, 1280, 256, 1, 1, 0, 1, 1),
           (16, 384, 384, 64, 64, 3, 1, 1, 1, 1), (16, 384, 384, 64, 128, 3, 1, 1, 1, 1), (16, 192, 192, 64, 64, 3, 1, 1, 1, 3), (16, 96, 96, 128, 128, 3, 1, 1, 1, 3)]
 L = _lib.lib()
+KERNELS = ("wg3", "wg1", "64x256", "128x128", "256x128")
 if len(sys.argv) > 2:
     SHAPES = [SHAPES[int(sys.argv[2])]]
 FORMS = sys.argv[3:4] or ["singles", "grouped"]
@@ -59,5 +60,10 @@ for (B, H, W, C, N, k, st, pad, dil, G) in SHAPES:
             best = min(best, a.elapsed_time(b) / reps / G * 1e3)
         out.append(best)
     fl = 2.0 * M * N * Q
-    print("%-44s G %2d  single %7.1f us %5.0f TF/s | grouped %7.1f us/problem %5.0f TF/s  (slab MB: single %.0f, grouped %.0f)" % (
-        str((H, C, N, k, st, dil)), G, out[0], fl / out[0] / 1e6, out[1], fl / out[1] / 1e6, ws1.numel() / 1e6, wsg.numel() / 1e6 / G), flush=True)
+    plans = []                      # what each form launches: kernel/variant, splits x klen, grid (mrfp_conv_wgrad_plan)
+    for count in (1, G):
+        pl = (ctypes.c_int64 * 5)()
+        call("mrfp_conv_wgrad_plan", _lib.BF16, B, H, W, C, N, N, k, k, Ho, Wo, st, pad, pad, dil, count, pl)
+        plans.append("%s/%d %dx%d g%d" % (KERNELS[pl[0]], pl[1], pl[2], pl[3], pl[4]))
+    print("%-44s G %2d  single %7.1f us %5.0f TF/s | grouped %7.1f us/problem %5.0f TF/s  (slab MB: single %.0f, grouped %.0f)  [%s | %s]" % (
+        str((H, C, N, k, st, dil)), G, out[0], fl / out[0] / 1e6, out[1], fl / out[1] / 1e6, ws1.numel() / 1e6, wsg.numel() / 1e6 / G, *plans), flush=True)
