@@ -422,13 +422,8 @@ static int launch_copy_channels(const void* src, void* dst, int64_t npix, int64_
     int64_t blocks = (total + 4 * kThreads - 1) / (4 * kThreads);
     if (blocks > 16384) blocks = 16384;
     if (blocks < 1) blocks = 1;
-    if (vec_ok)
-        hipLaunchKernelGGL((copy_channels_kernel<T, FullVec<T>::value>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
-                           (const T*)src, (T*)dst, npix, (int)C, (int)lds, (int)c0s, (int)ldd, (int)c0d);
-    else
-        hipLaunchKernelGGL((copy_channels_kernel<T, 1>), dim3((unsigned)blocks), dim3(kThreads), 0, st, (const T*)src, (T*)dst,
-                           npix, (int)C, (int)lds, (int)c0s, (int)ldd, (int)c0d);
-    MRFP_LAUNCH_CHECK();
+    MRFP_LAUNCH_VEC(vec_ok, (copy_channels_kernel<T, FullVec<T>::value>), (copy_channels_kernel<T, 1>), dim3((unsigned)blocks), st,
+                    (const T*)src, (T*)dst, npix, (int)C, (int)lds, (int)c0s, (int)ldd, (int)c0d);
     return 0;
 }
 
@@ -444,14 +439,13 @@ static int launch_affine_fwd(const void* x, const void* res, void* y, int64_t B,
     if (mask_out && !(vec_ok && FullVec<T>::value == 8)) { set_error("affine_fwd_mask: 16-bit activations with C %% 8 == 0, 16-byte aligned"); return -1; }
     const bool resize = tabH != nullptr || tabW != nullptr;
     if (resize && !(tabH && tabW)) { set_error("affine_fwd: both index tables or none"); return -1; }
-#define MRFP_AFF_LAUNCH(VECV, RS)                                                                                      \
-    hipLaunchKernelGGL((affine_fwd_kernel<T, VECV, RS>), grid, dim3(kThreads), 0, st, (const T*)x, (const T*)res,      \
-                       (T*)y, g, ly, A, S, cpi, relu, mask_out)
-    if (vec_ok) { if (resize) MRFP_AFF_LAUNCH(FullVec<T>::value, true); else MRFP_AFF_LAUNCH(FullVec<T>::value, false); }
-    else { if (resize) MRFP_AFF_LAUNCH(1, true); else MRFP_AFF_LAUNCH(1, false); }
-#undef MRFP_AFF_LAUNCH
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    auto launch = [&](auto rs) {      // RS: through the index tables or not
+        constexpr bool RS = decltype(rs)::value != 0;
+        MRFP_LAUNCH_VEC(vec_ok, (affine_fwd_kernel<T, FullVec<T>::value, RS>), (affine_fwd_kernel<T, 1, RS>), grid, st, (const T*)x,
+                        (const T*)res, (T*)y, g, ly, A, S, cpi, relu, mask_out);
+        return 0;
+    };
+    return resize ? launch(Int<1>{}) : launch(Int<0>{});
 }
 
 template <typename T>
@@ -473,9 +467,6 @@ static int launch_affine_bwd(const void* dy, const void* x, const void* y, void*
         const int64_t k = kh > kw ? kh : kw;
         kr = k <= 3 ? (int)k : 0;
     }
-#define MRFP_AFFB_LAUNCH(VECV, KRV)                                                                                    \
-    hipLaunchKernelGGL((affine_bwd_kernel<T, VECV, KRV>), grid, dim3(kThreads), 0, st, (const T*)dy, (const T*)x,      \
-                       (const T*)y, (T*)dx, (T*)dres, g, ly, invH, invW, P, Q, R, fA, fS, cpi)
     const bool identity = !invH && !invW;
     if (ymask) {
         if constexpr (FullVec<T>::value == 8) {
@@ -489,22 +480,17 @@ static int launch_affine_bwd(const void* dy, const void* x, const void* y, void*
             return -1;
         }
     }
-    if (vec_ok) {
-        if (identity) MRFP_AFFB_LAUNCH(FullVec<T>::value, -1);
-        else if (kr == 1) MRFP_AFFB_LAUNCH(FullVec<T>::value, 1);
-        else if (kr == 2) MRFP_AFFB_LAUNCH(FullVec<T>::value, 2);
-        else if (kr == 3) MRFP_AFFB_LAUNCH(FullVec<T>::value, 3);
-        else MRFP_AFFB_LAUNCH(FullVec<T>::value, 0);
-    } else {
-        if (identity) MRFP_AFFB_LAUNCH(1, -1);
-        else if (kr == 1) MRFP_AFFB_LAUNCH(1, 1);
-        else if (kr == 2) MRFP_AFFB_LAUNCH(1, 2);
-        else if (kr == 3) MRFP_AFFB_LAUNCH(1, 3);
-        else MRFP_AFFB_LAUNCH(1, 0);
-    }
-#undef MRFP_AFFB_LAUNCH
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    auto launch = [&](auto k) {       // KR: -1 identity geometry, 1..3 the unrolled fan-in, 0 the plain loops
+        constexpr int KR = decltype(k)::value;
+        MRFP_LAUNCH_VEC(vec_ok, (affine_bwd_kernel<T, FullVec<T>::value, KR>), (affine_bwd_kernel<T, 1, KR>), grid, st, (const T*)dy,
+                        (const T*)x, (const T*)y, (T*)dx, (T*)dres, g, ly, invH, invW, P, Q, R, fA, fS, cpi);
+        return 0;
+    };
+    if (identity) return launch(Int<-1>{});
+    if (kr == 1) return launch(Int<1>{});
+    if (kr == 2) return launch(Int<2>{});
+    if (kr == 3) return launch(Int<3>{});
+    return launch(Int<0>{});
 }
 
 template <typename T>
@@ -515,13 +501,8 @@ static int launch_add(const void* a, const void* b, void* y, int64_t n, hipStrea
     int64_t blocks = (nvec + kThreads - 1) / kThreads;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    if (vec_ok)
-        hipLaunchKernelGGL((add_kernel<T, FullVec<T>::value>), dim3((unsigned)blocks), dim3(kThreads), 0, st,
-                           (const T*)a, (const T*)b, (T*)y, nvec);
-    else
-        hipLaunchKernelGGL((add_kernel<T, 1>), dim3((unsigned)blocks), dim3(kThreads), 0, st, (const T*)a, (const T*)b,
-                           (T*)y, nvec);
-    MRFP_LAUNCH_CHECK();
+    MRFP_LAUNCH_VEC(vec_ok, (add_kernel<T, FullVec<T>::value>), (add_kernel<T, 1>), dim3((unsigned)blocks), st, (const T*)a,
+                    (const T*)b, (T*)y, nvec);
     return 0;
 }
 
@@ -538,10 +519,10 @@ int mrfp_affine_fwd(const void* x, const void* res, void* y, int dtype, int64_t 
     MRFP_CHECK(x || S, "affine_fwd: neither x nor S given");
     MRFP_CHECK((tabH && tabW) || (Hs == Ho && Ws == Wo), "affine_fwd: resize geometry without index tables");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_F32) return launch_affine_fwd<float>(x, res, y, B, Ho, Wo, C, Hs, Ws, tabH, tabW, A, S, coef_per_image, relu, st);
-    if (dtype == MRFP_BF16) return launch_affine_fwd<bf16>(x, res, y, B, Ho, Wo, C, Hs, Ws, tabH, tabW, A, S, coef_per_image, relu, st);
-    if (dtype == MRFP_F16) return launch_affine_fwd<f16>(x, res, y, B, Ho, Wo, C, Hs, Ws, tabH, tabW, A, S, coef_per_image, relu, st);
-    MRFP_CHECK(false, "affine_fwd: unknown dtype %d", dtype);
+    return by_dtype(dtype, "affine_fwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_affine_fwd<T>(x, res, y, B, Ho, Wo, C, Hs, Ws, tabH, tabW, A, S, coef_per_image, relu, st);
+    });
 }
 
 int mrfp_affine_fwd_stats(const void* x, const void* res, void* y, int dtype, int64_t B, int64_t H, int64_t W, int64_t C,
@@ -551,22 +532,12 @@ int mrfp_affine_fwd_stats(const void* x, const void* res, void* y, int dtype, in
     RowGeom g{(int)B, (int)H, (int)W, (int)C, (int)H, (int)W, nullptr, nullptr};
     const int ly = lines_per_image(B, H);
     const bool al = aligned16(x) && aligned16(y) && (!res || aligned16(res)) && (!A || aligned16(A)) && (!S || aligned16(S));
-#define MRFP_AFS(TT)                                                                                                           \
-    do {                                                                                                                       \
-        if (pick_vec<TT>(C) > 1 && al)                                                                                         \
-            hipLaunchKernelGGL((affine_fwd_stats_kernel<TT, FullVec<TT>::value>), dim3((unsigned)(B * ly)), dim3(kThreads), 0, st, (const TT*)x,  \
-                               (const TT*)res, (TT*)y, g, ly, A, S, coef_per_image, relu, ws);                                   \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((affine_fwd_stats_kernel<TT, 1>), dim3((unsigned)(B * ly)), dim3(kThreads), 0, st, (const TT*)x,  \
-                               (const TT*)res, (TT*)y, g, ly, A, S, coef_per_image, relu, ws);                                   \
-    } while (0)
-    if (dtype == MRFP_F32) MRFP_AFS(float);
-    else if (dtype == MRFP_BF16) MRFP_AFS(bf16);
-    else if (dtype == MRFP_F16) MRFP_AFS(f16);
-    else MRFP_CHECK(false, "affine_fwd_stats: unknown dtype %d", dtype);
-#undef MRFP_AFS
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return by_dtype(dtype, "affine_fwd_stats", [&](auto t) {
+        using T = typename decltype(t)::type;
+        MRFP_DISPATCH_VEC(T, C, al, affine_fwd_stats_kernel, dim3((unsigned)(B * ly)), st, (const T*)x, (const T*)res, (T*)y, g, ly, A, S,
+                          coef_per_image, relu, ws);
+        return 0;
+    });
 }
 
 int mrfp_affine_bwd(const void* dy, const void* x, const void* y, void* dx, void* dres, int dtype, int64_t B,
@@ -578,28 +549,30 @@ int mrfp_affine_bwd(const void* dy, const void* x, const void* y, void* dx, void
     MRFP_CHECK((invH && invW) || (Hs == Ho && Ws == Wo), "affine_bwd: resize geometry without inverse tables");
     MRFP_CHECK(!dres || (!invH && !invW), "affine_bwd: dres is not supported behind a resize");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_F32) return launch_affine_bwd<float>(dy, x, y, dx, dres, B, Ho, Wo, C, Hs, Ws, invH, invW, P, Q, R, fA, fS, coef_per_image, st);
-    if (dtype == MRFP_BF16) return launch_affine_bwd<bf16>(dy, x, y, dx, dres, B, Ho, Wo, C, Hs, Ws, invH, invW, P, Q, R, fA, fS, coef_per_image, st);
-    if (dtype == MRFP_F16) return launch_affine_bwd<f16>(dy, x, y, dx, dres, B, Ho, Wo, C, Hs, Ws, invH, invW, P, Q, R, fA, fS, coef_per_image, st);
-    MRFP_CHECK(false, "affine_bwd: unknown dtype %d", dtype);
+    return by_dtype(dtype, "affine_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_affine_bwd<T>(dy, x, y, dx, dres, B, Ho, Wo, C, Hs, Ws, invH, invW, P, Q, R, fA, fS, coef_per_image, st);
+    });
 }
 
 int mrfp_affine_fwd_relu_mask(const void* x, const void* res, void* y, void* mask, int dtype, int64_t B, int64_t H, int64_t W,
                               int64_t C, const float* A, const float* S, int coef_per_image, void* stream) {
     MRFP_CHECK(x && y && mask && A && S && B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0, "affine_fwd_relu_mask: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_BF16) return launch_affine_fwd<bf16>(x, res, y, B, H, W, C, H, W, nullptr, nullptr, A, S, coef_per_image, 1, st, (uint8_t*)mask);
-    if (dtype == MRFP_F16) return launch_affine_fwd<f16>(x, res, y, B, H, W, C, H, W, nullptr, nullptr, A, S, coef_per_image, 1, st, (uint8_t*)mask);
-    MRFP_CHECK(false, "affine_fwd_relu_mask: 16-bit activations only (dtype %d)", dtype);
+    return by_dtype16(dtype, "affine_fwd_relu_mask", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_affine_fwd<T>(x, res, y, B, H, W, C, H, W, nullptr, nullptr, A, S, coef_per_image, 1, st, (uint8_t*)mask);
+    });
 }
 
 int mrfp_affine_bwd_mask(const void* dy, const void* x, const void* mask, void* dx, void* dres, int dtype, int64_t B, int64_t H,
                          int64_t W, int64_t C, const float* P, const float* Q, const float* R, int coef_per_image, void* stream) {
     MRFP_CHECK(dy && dx && mask && B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0, "affine_bwd_mask: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_BF16) return launch_affine_bwd<bf16>(dy, x, mask, dx, dres, B, H, W, C, H, W, nullptr, nullptr, P, Q, R, nullptr, nullptr, coef_per_image, st, true);
-    if (dtype == MRFP_F16) return launch_affine_bwd<f16>(dy, x, mask, dx, dres, B, H, W, C, H, W, nullptr, nullptr, P, Q, R, nullptr, nullptr, coef_per_image, st, true);
-    MRFP_CHECK(false, "affine_bwd_mask: 16-bit activations only (dtype %d)", dtype);
+    return by_dtype16(dtype, "affine_bwd_mask", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_affine_bwd<T>(dy, x, mask, dx, dres, B, H, W, C, H, W, nullptr, nullptr, P, Q, R, nullptr, nullptr, coef_per_image, st, true);
+    });
 }
 
 int mrfp_copy_channels(const void* src, void* dst, int dtype, int64_t npix, int64_t C, int64_t ld_src, int64_t c0_src,
@@ -607,19 +580,19 @@ int mrfp_copy_channels(const void* src, void* dst, int dtype, int64_t npix, int6
     MRFP_CHECK(src && dst && npix > 0 && C > 0 && c0_src >= 0 && c0_dst >= 0 && c0_src + C <= ld_src && c0_dst + C <= ld_dst,
                "copy_channels: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_F32) return launch_copy_channels<float>(src, dst, npix, C, ld_src, c0_src, ld_dst, c0_dst, st);
-    if (dtype == MRFP_BF16) return launch_copy_channels<bf16>(src, dst, npix, C, ld_src, c0_src, ld_dst, c0_dst, st);
-    if (dtype == MRFP_F16) return launch_copy_channels<f16>(src, dst, npix, C, ld_src, c0_src, ld_dst, c0_dst, st);
-    MRFP_CHECK(false, "copy_channels: unknown dtype %d", dtype);
+    return by_dtype(dtype, "copy_channels", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_copy_channels<T>(src, dst, npix, C, ld_src, c0_src, ld_dst, c0_dst, st);
+    });
 }
 
 int mrfp_add(const void* a, const void* b, void* y, int dtype, int64_t n, void* stream) {
     MRFP_CHECK(a && b && y && n > 0, "add: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_F32) return launch_add<float>(a, b, y, n, st);
-    if (dtype == MRFP_BF16) return launch_add<bf16>(a, b, y, n, st);
-    if (dtype == MRFP_F16) return launch_add<f16>(a, b, y, n, st);
-    MRFP_CHECK(false, "add: unknown dtype %d", dtype);
+    return by_dtype(dtype, "add", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_add<T>(a, b, y, n, st);
+    });
 }
 
 }  // extern "C"

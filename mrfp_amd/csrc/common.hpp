@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <stdlib.h>
+#include <type_traits>
 #include "../../include/mrfp_hip.h"
 
 namespace mrfp {
@@ -154,6 +155,41 @@ template <typename T> inline int pick_vec(int64_t C) {
     const int full = FullVec<T>::value;
     return (C % full == 0) ? full : 1;
 }
+
+// ---- host dispatch: element type, vector width ---------------------------------------------------------------------------
+// The element type of an entry point, from its run-time `dtype`.  by_dtype(dtype, "name", [&](auto t) { using T = typename
+// decltype(t)::type; return launch_x<T>(...); }) calls the body with one of Tag<float> / Tag<bf16> / Tag<f16> and returns its int;
+// any other dtype is refused as "name: unknown dtype %d" (-1).  The body is compiled for every type the helper can pass, so a
+// 16-bit-only entry point goes through by_dtype16 -- by_dtype would add its float kernels to the code object.
+template <typename T> struct Tag { using type = T; };
+template <int V> using Int = std::integral_constant<int, V>;      // a compile-time value chosen at run time, passed the same way
+
+inline bool dtype_known(int dtype) { return dtype == MRFP_F32 || dtype == MRFP_BF16 || dtype == MRFP_F16; }
+inline int dtype_bytes(int dtype) { return dtype == MRFP_F32 ? 4 : 2; }      // of a known dtype: check dtype_known first
+
+template <typename F> inline int by_dtype16(int dtype, const char* who, F&& f) {
+    if (dtype == MRFP_BF16) return f(Tag<bf16>{});
+    if (dtype == MRFP_F16) return f(Tag<f16>{});
+    MRFP_CHECK(false, "%s: 16-bit activations only (dtype %d)", who, dtype);
+}
+template <typename F> inline int by_dtype(int dtype, const char* who, F&& f) {
+    if (dtype == MRFP_F32) return f(Tag<float>{});
+    if (dtype == MRFP_BF16) return f(Tag<bf16>{});
+    if (dtype == MRFP_F16) return f(Tag<f16>{});
+    MRFP_CHECK(false, "%s: unknown dtype %d", who, dtype);
+}
+
+// The vector width of a launch: the full 16-byte instance KFULL when `vec`, else the scalar instance KONE (each a parenthesised
+// kernel instance), on kThreads threads; returns -2 from the caller when the launch fails.  MRFP_DISPATCH_VEC is the common case,
+// KERNEL<T, FullVec<T>::value> when the channel count makes whole vectors and `ok` (alignment, pitches) holds, else KERNEL<T, 1>.
+#define MRFP_LAUNCH_VEC(vec, KFULL, KONE, grid, st, ...)                                \
+    do {                                                                                \
+        if (vec) hipLaunchKernelGGL(KFULL, grid, dim3(kThreads), 0, st, __VA_ARGS__);   \
+        else hipLaunchKernelGGL(KONE, grid, dim3(kThreads), 0, st, __VA_ARGS__);        \
+        MRFP_LAUNCH_CHECK();                                                            \
+    } while (0)
+#define MRFP_DISPATCH_VEC(T, C, ok, KERNEL, grid, st, ...) \
+    MRFP_LAUNCH_VEC(pick_vec<T>(C) > 1 && (ok), (KERNEL<T, FullVec<T>::value>), (KERNEL<T, 1>), grid, st, __VA_ARGS__)
 
 inline int lines_per_image(int64_t B, int64_t Ho) {
     // ~1024 workgroups over the chip (4 per CU, 16 waves/CU, 4 independent 16-byte loads per lane in the

@@ -351,8 +351,8 @@ __global__ __launch_bounds__(kThreads) void mask_gate_kernel(const T* __restrict
 // ---- launchers -----------------------------------------------------------------------------------------------------------
 static bool dw_geom(int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp, int64_t C, int64_t Ho, int64_t Wo, int64_t stride,
                     int64_t dil, DwGeom& g) {
-    const int vec = dtype == MRFP_F32 ? 4 : 8;
-    if (dtype != MRFP_F32 && dtype != MRFP_BF16 && dtype != MRFP_F16) { set_error("dwconv: unsupported dtype %d", dtype); return false; }
+    if (!dtype_known(dtype)) { set_error("dwconv: unsupported dtype %d", dtype); return false; }
+    const int vec = 16 / dtype_bytes(dtype);
     if (B < 1 || H < 1 || W < 1 || C < 1 || Cp < C || Cp % vec != 0 || stride < 1 || stride > 2 || dil < 1) {
         set_error("dwconv: bad geometry B=%lld H=%lld W=%lld C=%lld Cp=%lld stride=%lld dil=%lld", (long long)B, (long long)H,
                   (long long)W, (long long)C, (long long)Cp, (long long)stride, (long long)dil);
@@ -369,7 +369,7 @@ static bool dw_geom(int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp, int6
     return true;
 }
 
-static int dw_nchunk(int dtype, int64_t Cp) { return dw_split((int)(Cp / (dtype == MRFP_F32 ? 4 : 8))).nchunk; }
+static int dw_nchunk(int dtype, int64_t Cp) { return dw_split((int)(Cp / (16 / dtype_bytes(dtype)))).nchunk; }
 
 template <typename T>
 static int launch_dw_fwd(const void* x, const float* w, const float* bias, void* y, const DwGeom& g, float* ws, hipStream_t st) {
@@ -451,9 +451,10 @@ int mrfp_dwconv_fwd(const void* x, const float* w, const float* bias, void* y, i
     DwGeom g;
     if (!dw_geom(dtype, B, H, W, Cp, C, Ho, Wo, stride, dil, g)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_BF16) return launch_dw_fwd<bf16>(x, w, bias, y, g, ws, st);
-    if (dtype == MRFP_F16) return launch_dw_fwd<f16>(x, w, bias, y, g, ws, st);
-    return launch_dw_fwd<float>(x, w, bias, y, g, ws, st);
+    return by_dtype(dtype, "dwconv", [&](auto t) {      // (dw_geom has refused an unknown dtype)
+        using T = typename decltype(t)::type;
+        return launch_dw_fwd<T>(x, w, bias, y, g, ws, st);
+    });
 }
 
 int mrfp_dwconv_fwd_act(const void* x, const float* w, const float* bias, void* y, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp,
@@ -465,11 +466,10 @@ int mrfp_dwconv_fwd_act(const void* x, const float* w, const float* bias, void* 
     DwGeom g;
     if (!dw_geom(dtype, B, H, W, Cp, C, Ho, Wo, stride, dil, g)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_BF16)
-        return act == 1 ? launch_dw_fwd_act<bf16, 1>(x, w, bias, y, g, st) : launch_dw_fwd_act<bf16, 2>(x, w, bias, y, g, st);
-    if (dtype == MRFP_F16)
-        return act == 1 ? launch_dw_fwd_act<f16, 1>(x, w, bias, y, g, st) : launch_dw_fwd_act<f16, 2>(x, w, bias, y, g, st);
-    return act == 1 ? launch_dw_fwd_act<float, 1>(x, w, bias, y, g, st) : launch_dw_fwd_act<float, 2>(x, w, bias, y, g, st);
+    return by_dtype(dtype, "dwconv", [&](auto t) {      // (dw_geom has refused an unknown dtype)
+        using T = typename decltype(t)::type;
+        return act == 1 ? launch_dw_fwd_act<T, 1>(x, w, bias, y, g, st) : launch_dw_fwd_act<T, 2>(x, w, bias, y, g, st);
+    });
 }
 
 int mrfp_dwconv_dgrad(const void* dy, const float* w, void* dx, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp, int64_t C,
@@ -479,9 +479,10 @@ int mrfp_dwconv_dgrad(const void* dy, const float* w, void* dx, int dtype, int64
     DwGeom g;
     if (!dw_geom(dtype, B, H, W, Cp, C, Ho, Wo, stride, dil, g)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_BF16) return launch_dw_dgrad<bf16>(dy, w, dx, g, st);
-    if (dtype == MRFP_F16) return launch_dw_dgrad<f16>(dy, w, dx, g, st);
-    return launch_dw_dgrad<float>(dy, w, dx, g, st);
+    return by_dtype(dtype, "dwconv", [&](auto t) {      // (dw_geom has refused an unknown dtype)
+        using T = typename decltype(t)::type;
+        return launch_dw_dgrad<T>(dy, w, dx, g, st);
+    });
 }
 
 int mrfp_dwconv_wgrad(const void* x, const void* dy, float* dw, void* ws, int dtype, int64_t B, int64_t H, int64_t W, int64_t Cp,
@@ -491,45 +492,39 @@ int mrfp_dwconv_wgrad(const void* x, const void* dy, float* dw, void* ws, int dt
     DwGeom g;
     if (!dw_geom(dtype, B, H, W, Cp, C, Ho, Wo, stride, dil, g)) return -1;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_BF16) return launch_dw_wgrad<bf16>(x, dy, dw, (float*)ws, g, st);
-    if (dtype == MRFP_F16) return launch_dw_wgrad<f16>(x, dy, dw, (float*)ws, g, st);
-    return launch_dw_wgrad<float>(x, dy, dw, (float*)ws, g, st);
+    return by_dtype(dtype, "dwconv", [&](auto t) {      // (dw_geom has refused an unknown dtype)
+        using T = typename decltype(t)::type;
+        return launch_dw_wgrad<T>(x, dy, dw, (float*)ws, g, st);
+    });
 }
 
 int mrfp_affine_fwd_relu6_mask(const void* x, void* y, void* mask, int dtype, int64_t npix, int64_t C, const float* A, const float* S,
                                void* stream) {
     MRFP_CHECK(x && y && mask && A && S && npix > 0 && C > 0, "affine_fwd_relu6_mask: bad arguments");
     MRFP_CHECK(aligned16(x) && aligned16(y), "affine_fwd_relu6_mask: tensors must be 16-byte aligned");
+    MRFP_CHECK(dtype_known(dtype), "affine_fwd_relu6_mask: unsupported dtype %d", dtype);
     const int64_t n = npix * C;
     hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = elem_blocks((n + 7) / 8);
-    if (dtype == MRFP_BF16)
-        hipLaunchKernelGGL(relu6_fwd_kernel<bf16>, dim3(blocks), dim3(kThreads), 0, st, (const bf16*)x, (bf16*)y, (uint8_t*)mask, n, (int)C, A, S);
-    else if (dtype == MRFP_F16)
-        hipLaunchKernelGGL(relu6_fwd_kernel<f16>, dim3(blocks), dim3(kThreads), 0, st, (const f16*)x, (f16*)y, (uint8_t*)mask, n, (int)C, A, S);
-    else if (dtype == MRFP_F32)
-        hipLaunchKernelGGL(relu6_fwd_kernel<float>, dim3(blocks), dim3(kThreads), 0, st, (const float*)x, (float*)y, (uint8_t*)mask, n, (int)C,
-                           A, S);
-    else
-        MRFP_CHECK(false, "affine_fwd_relu6_mask: unsupported dtype %d", dtype);
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return by_dtype(dtype, "affine_fwd_relu6_mask", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(relu6_fwd_kernel<T>, dim3(blocks), dim3(kThreads), 0, st, (const T*)x, (T*)y, (uint8_t*)mask, n, (int)C, A, S);
+        MRFP_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int mrfp_mask_gate(const void* dy, const void* mask, void* out, int dtype, int64_t n, void* stream) {
     MRFP_CHECK(dy && mask && out && n > 0, "mask_gate: bad arguments");
+    MRFP_CHECK(dtype_known(dtype), "mask_gate: unsupported dtype %d", dtype);
     hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = elem_blocks(n);
-    if (dtype == MRFP_BF16)
-        hipLaunchKernelGGL(mask_gate_kernel<bf16>, dim3(blocks), dim3(kThreads), 0, st, (const bf16*)dy, (const uint8_t*)mask, (bf16*)out, n);
-    else if (dtype == MRFP_F16)
-        hipLaunchKernelGGL(mask_gate_kernel<f16>, dim3(blocks), dim3(kThreads), 0, st, (const f16*)dy, (const uint8_t*)mask, (f16*)out, n);
-    else if (dtype == MRFP_F32)
-        hipLaunchKernelGGL(mask_gate_kernel<float>, dim3(blocks), dim3(kThreads), 0, st, (const float*)dy, (const uint8_t*)mask, (float*)out, n);
-    else
-        MRFP_CHECK(false, "mask_gate: unsupported dtype %d", dtype);
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return by_dtype(dtype, "mask_gate", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(mask_gate_kernel<T>, dim3(blocks), dim3(kThreads), 0, st, (const T*)dy, (const uint8_t*)mask, (T*)out, n);
+        MRFP_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 }  // extern "C"

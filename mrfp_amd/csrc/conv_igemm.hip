@@ -796,8 +796,8 @@ static int conv_params(ConvP& p, int dtype, int64_t B, int64_t H, int64_t W, int
                        const float* bias, const void* addend, const void* addend_mask, float* colstats, const unsigned char* rowweight) {
     MRFP_CHECK(B > 0 && H > 0 && W > 0 && C > 0 && N > 0 && R > 0 && S > 0 && Ho > 0 && Wo > 0, "conv_fwd: bad arguments");
     MRFP_CHECK(stride >= 1 && dil >= 1 && sstride >= 1 && ldy >= N, "conv_fwd: bad stride/dilation/pitch");
-    MRFP_CHECK(dtype == MRFP_F32 || dtype == MRFP_BF16 || dtype == MRFP_F16, "conv_fwd: unknown dtype %d", dtype);
-    const int esz = dtype == MRFP_F32 ? 4 : 2;
+    MRFP_CHECK(dtype_known(dtype), "conv_fwd: unknown dtype %d", dtype);
+    const int esz = dtype_bytes(dtype);
     MRFP_CHECK((C * esz) % 16 == 0, "conv_fwd: C=%lld must make 16-byte chunks (pad the channels)", (long long)C);
     MRFP_CHECK(B * Ho * Wo < (1LL << 31), "conv_fwd: tensor too large for 32-bit tile indices");
     p = ConvP{};
@@ -834,7 +834,7 @@ static int conv_fwd_impl(const void* x, const void* wpack, const float* bias, vo
                                 colstats, rowweight);
     if (bad) return bad;
     MRFP_CHECK(aligned16(x) && aligned16(wpack), "conv_fwd: x / wpack must be 16-byte aligned");
-    const int esz = dtype == MRFP_F32 ? 4 : 2;
+    const int esz = dtype_bytes(dtype);
     p.w = (const char*)wpack;
     // The plan is made from the whole batch BEFORE the class-major row order below changes M: that decision needs the tile height,
     // and M cannot change it -- class-major launches are strided dgrads, which only the generic tiles take, and the tile rules for
@@ -881,9 +881,7 @@ static int conv_fwd_impl(const void* x, const void* wpack, const float* bias, vo
         p.xbytes = (dbg_drop & 1) ? 0u : (unsigned)(bc * img);
         p.wbytes = (dbg_drop & 2) ? 0u : (unsigned)wb;
         if (chunked) plan = conv_plan(p, esz);       // a batch range is a launch of its own: a smaller M may take another kernel
-        rc = dtype == MRFP_F32 ? run_igemm_act<float>(p, plan, (hipStream_t)stream, act)
-             : dtype == MRFP_F16 ? run_igemm_act<f16>(p, plan, (hipStream_t)stream, act)
-                                 : run_igemm_act<bf16>(p, plan, (hipStream_t)stream, act);
+        rc = by_dtype(dtype, "conv_fwd", [&](auto t) { return run_igemm_act<typename decltype(t)::type>(p, plan, (hipStream_t)stream, act); });
     }
     if (rc || !colstats) return rc;
     if (plan.stats_blocks > kCompactAbove) {
@@ -962,7 +960,7 @@ int mrfp_conv_stats_layout(int dtype, int64_t B, int64_t H, int64_t W, int64_t C
     const int bad = conv_params(p, dtype, B, H, W, C, N, ldy, R, S, Ho, Wo, stride, pad_h, pad_w, dil, sstride, nullptr, nullptr,
                                 nullptr, &stats_present, wstats ? &rows_present : nullptr);
     if (bad) return bad;
-    const ConvPlan plan = conv_plan(p, dtype == MRFP_F32 ? 4 : 2);
+    const ConvPlan plan = conv_plan(p, dtype_bytes(dtype));
     const int64_t nblk = plan.stats_blocks;
     const bool compact = nblk > kCompactAbove;      // (conv_fwd_impl: the groups are appended behind the row blocks)
     out[0] = nblk;

@@ -213,11 +213,9 @@ static int launch_fold(const FoldJob* jobs, const int64_t* prefix, int njobs, in
     return 0;
 }
 static int run_fold(int dtype, const FoldJob* jobs, const int64_t* prefix, int njobs, int64_t total, const FoldJob& single, hipStream_t st) {
-    if (dtype == MRFP_F32) return launch_fold<float>(jobs, prefix, njobs, total, single, st);
-    if (dtype == MRFP_BF16) return launch_fold<bf16>(jobs, prefix, njobs, total, single, st);
-    if (dtype == MRFP_F16) return launch_fold<f16>(jobs, prefix, njobs, total, single, st);
-    set_error("pack_weight_folded: unknown dtype %d", dtype);
-    return -1;
+    return by_dtype(dtype, "pack_weight_folded", [&](auto t) {
+        return launch_fold<typename decltype(t)::type>(jobs, prefix, njobs, total, single, st);
+    });
 }
 
 // network input: NCHW fp32 [B,C,H,W] -> NHWC T [B,H,W,Cpad] (pad channels zero)
@@ -254,19 +252,13 @@ int mrfp_pack_weight(const float* w, void* wf, void* wd, int dtype, int64_t N, i
     const int64_t total = Npad * R * S * Cpad + C * R * S * Npad;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    if (dtype == MRFP_F32)
-        hipLaunchKernelGGL((pack_weight_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w,
-                           (float*)wf, (float*)wd, (int)N, (int)C, (int)R, (int)S, (int)Npad, (int)Cpad);
-    else if (dtype == MRFP_BF16)
-        hipLaunchKernelGGL((pack_weight_kernel<bf16>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w,
-                           (bf16*)wf, (bf16*)wd, (int)N, (int)C, (int)R, (int)S, (int)Npad, (int)Cpad);
-    else if (dtype == MRFP_F16)
-        hipLaunchKernelGGL((pack_weight_kernel<f16>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w,
-                           (f16*)wf, (f16*)wd, (int)N, (int)C, (int)R, (int)S, (int)Npad, (int)Cpad);
-    else
-        MRFP_CHECK(false, "pack_weight: unknown dtype %d", dtype);
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return by_dtype(dtype, "pack_weight", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((pack_weight_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, (T*)wf, (T*)wd, (int)N,
+                           (int)C, (int)R, (int)S, (int)Npad, (int)Cpad);
+        MRFP_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int mrfp_pack_weights_batched(const void* jobs, const int64_t* prefix, int64_t njobs, int64_t total, int dtype, void* stream) {
@@ -274,16 +266,13 @@ int mrfp_pack_weights_batched(const void* jobs, const int64_t* prefix, int64_t n
     const int64_t blocks = total;           // one workgroup per brick
     MRFP_CHECK(blocks < (1LL << 31), "pack_weights_batched: too many bricks");
     const mrfp::PackJob* jb = (const mrfp::PackJob*)jobs;
-    if (dtype == MRFP_F32)
-        hipLaunchKernelGGL((pack_weights_batched_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, jb, prefix, (int)njobs, total);
-    else if (dtype == MRFP_BF16)
-        hipLaunchKernelGGL((pack_weights_batched_kernel<bf16>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, jb, prefix, (int)njobs, total);
-    else if (dtype == MRFP_F16)
-        hipLaunchKernelGGL((pack_weights_batched_kernel<f16>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, jb, prefix, (int)njobs, total);
-    else
-        MRFP_CHECK(false, "pack_weights_batched: unknown dtype %d", dtype);
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return by_dtype(dtype, "pack_weights_batched", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((pack_weights_batched_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, jb, prefix, (int)njobs,
+                           total);
+        MRFP_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int mrfp_pack_weight_folded(const float* w, void* wf, const float* conv_bias, const float* bn_weight, const float* bn_bias,
@@ -308,19 +297,13 @@ int mrfp_nchw_to_nhwc_pad(const float* x, void* y, int dtype, int64_t B, int64_t
     MRFP_CHECK(x && y && B > 0 && C > 0 && H > 0 && W > 0 && Cpad >= C, "nchw_to_nhwc_pad: bad arguments");
     int64_t blocks = (B * H * W + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (dtype == MRFP_F32)
-        hipLaunchKernelGGL((nchw_to_nhwc_pad_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x,
-                           (float*)y, (int)B, (int)C, (int)H, (int)W, (int)Cpad);
-    else if (dtype == MRFP_BF16)
-        hipLaunchKernelGGL((nchw_to_nhwc_pad_kernel<bf16>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x,
-                           (bf16*)y, (int)B, (int)C, (int)H, (int)W, (int)Cpad);
-    else if (dtype == MRFP_F16)
-        hipLaunchKernelGGL((nchw_to_nhwc_pad_kernel<f16>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x,
-                           (f16*)y, (int)B, (int)C, (int)H, (int)W, (int)Cpad);
-    else
-        MRFP_CHECK(false, "nchw_to_nhwc_pad: unknown dtype %d", dtype);
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return by_dtype(dtype, "nchw_to_nhwc_pad", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((nchw_to_nhwc_pad_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (T*)y, (int)B, (int)C,
+                           (int)H, (int)W, (int)Cpad);
+        MRFP_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 }  // extern "C"

@@ -565,8 +565,8 @@ static int wgrad_call(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int
                       int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t count, WgradCall& c) {
     MRFP_CHECK(count > 0 && count <= kWgMaxGroup && B > 0 && H > 0 && W > 0 && C > 0 && N > 0 && R > 0 && S > 0 && Ho > 0 && Wo > 0,
                "conv_wgrad: bad arguments");
-    MRFP_CHECK(dtype == MRFP_F32 || dtype == MRFP_BF16 || dtype == MRFP_F16, "conv_wgrad: unknown dtype %d", dtype);
-    const int esz = dtype == MRFP_F32 ? 4 : 2;
+    MRFP_CHECK(dtype_known(dtype), "conv_wgrad: unknown dtype %d", dtype);
+    const int esz = dtype_bytes(dtype);
     MRFP_CHECK((C * esz) % 16 == 0 && (ldn * esz) % 16 == 0 && ldn >= N,
                "conv_wgrad: channel counts must make 16-byte chunks (C=%lld ldn=%lld)", (long long)C, (long long)ldn);
     MRFP_CHECK(B * Ho * Wo < (1LL << 31), "conv_wgrad: tensor too large");
@@ -649,9 +649,7 @@ static int wgrad_run(const void* const* xs, const void* const* dys, float* const
         int rc;
         if (pl.kind == WgradKernel::wg3) rc = wg3_run(xs, dys, (float*)ws, dtype == MRFP_F16, g, pl, p.xbytes, p.dybytes, st);
         else if (pl.kind == WgradKernel::wg1) rc = wg1_run(xs, dys, (float*)ws, dtype == MRFP_F16, g, pl, p.xbytes, p.dybytes, st);
-        else if (dtype == MRFP_F32) rc = launch_wgrad_tiles<float>(p, pl, st, &grp);
-        else if (dtype == MRFP_F16) rc = launch_wgrad_tiles<f16>(p, pl, st, &grp);
-        else rc = launch_wgrad_tiles<bf16>(p, pl, st, &grp);
+        else rc = by_dtype(dtype, "conv_wgrad", [&](auto t) { return launch_wgrad_tiles<typename decltype(t)::type>(p, pl, st, &grp); });
         if (rc) return rc;
         const int64_t total4 = N * (int64_t)p.Q / 4;          // Q = R*S*C and C*esz % 16 == 0  =>  Q % 4 == 0
         const int64_t blocks = (total4 + 63) / 64;

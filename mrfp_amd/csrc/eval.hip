@@ -210,22 +210,21 @@ int mrfp_prob_accum(const void* logits, int dtype, int64_t B, int64_t hs, int64_
     MRFP_CHECK(y0 >= 0 && x0 >= 0 && y0 + hd <= H && x0 + wd <= W,
                "prob_accum: rectangle (%lld,%lld,%lld,%lld) leaves the %lld x %lld accumulator", (long long)y0, (long long)x0,
                (long long)hd, (long long)wd, (long long)H, (long long)W);
-    MRFP_CHECK(dtype == MRFP_F32 || dtype == MRFP_BF16 || dtype == MRFP_F16, "prob_accum: unknown dtype %d", dtype);
+    MRFP_CHECK(dtype_known(dtype), "prob_accum: unknown dtype %d", dtype);
     MRFP_CHECK(aligned16(acc) && (reinterpret_cast<uintptr_t>(cnt) & 3) == 0, "prob_accum: acc must be 16-byte aligned");
     MRFP_CHECK(B < (1 << 24) && H < (1 << 24) && W < (1 << 24) && hs < (1 << 24) && ws < (1 << 24) && ld < (1 << 24),
                "prob_accum: sizes out of range");
     const int64_t nseg = (wd + kAccThreads - 1) / kAccThreads, seg = (wd + nseg - 1) / nseg;    // equal segments of <= 256 pixels
     const int64_t grid = B * hd * nseg;
     MRFP_CHECK(grid < (1LL << 31), "prob_accum: rectangle too large");
-    const int esz = dtype == MRFP_F32 ? 4 : 2;
-    const bool vsrc = (ld * esz) % 16 == 0 && aligned16(logits);
+    const bool vsrc = (ld * dtype_bytes(dtype)) % 16 == 0 && aligned16(logits);
     AccArgs a{logits, (int)ld, (int)hs, (int)ws, acc, cnt, (int)H, (int)W, (int)NC, (int)y0, (int)x0, (int)hd, (int)wd, (int)nseg,
               (int)seg, flip != 0, weight, (unsigned)grid, (hipStream_t)stream};
-    if (dtype == MRFP_F32) dispatch_acc<float>(a, vsrc);
-    else if (dtype == MRFP_BF16) dispatch_acc<bf16>(a, vsrc);
-    else dispatch_acc<f16>(a, vsrc);
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return by_dtype(dtype, "prob_accum", [&](auto t) {
+        dispatch_acc<typename decltype(t)::type>(a, vsrc);
+        MRFP_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int mrfp_acc_argmax_hist(const float* acc, const float* cnt, const int64_t* target, int64_t npix, int64_t NC, int64_t* hist,

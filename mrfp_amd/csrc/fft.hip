@@ -1141,10 +1141,10 @@ int mrfp_fourier_mix(const void* x, void* y, const int64_t* perm, void* S, void*
     p.radius2 = radius * radius; p.lam = lam; p.scale = 1.0f / (float)(H * W); p.high = high; p.load_ratio = load_ratio;
     p.Ws = stored_bins(H, W, radius, high);
     p.delta = p.Ws < p.Wh;
-    if (dtype == MRFP_F32) return run_mix<float>(p, (const float2*)twH, (const float2*)twW, (hipStream_t)stream);
-    if (dtype == MRFP_BF16) return run_mix<bf16>(p, (const float2*)twH, (const float2*)twW, (hipStream_t)stream);
-    if (dtype == MRFP_F16) return run_mix<f16>(p, (const float2*)twH, (const float2*)twW, (hipStream_t)stream);
-    MRFP_CHECK(false, "fourier_mix: unknown dtype %d", dtype);
+    return by_dtype(dtype, "fourier_mix", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return run_mix<T>(p, (const float2*)twH, (const float2*)twW, (hipStream_t)stream);
+    });
 }
 
 }  // extern "C"

@@ -129,18 +129,14 @@ int mrfp_ce_fwd(const void* logits, const int64_t* target, int dtype, int64_t np
     MRFP_CHECK(logits && target && ws && loss && npix > 0 && C > 0, "ce_fwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     const int nb = ce_blocks(npix);
-    if (dtype == MRFP_F32)
-        hipLaunchKernelGGL((ce_fwd_kernel<float>), dim3(nb), dim3(kCeThreads), 0, st, (const float*)logits, target, npix, (int)C, ignore_index, ws);
-    else if (dtype == MRFP_BF16)
-        hipLaunchKernelGGL((ce_fwd_kernel<bf16>), dim3(nb), dim3(kCeThreads), 0, st, (const bf16*)logits, target, npix, (int)C, ignore_index, ws);
-    else if (dtype == MRFP_F16)
-        hipLaunchKernelGGL((ce_fwd_kernel<f16>), dim3(nb), dim3(kCeThreads), 0, st, (const f16*)logits, target, npix, (int)C, ignore_index, ws);
-    else
-        MRFP_CHECK(false, "ce_fwd: unknown dtype %d", dtype);
-    MRFP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, ws, nb, loss);
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return by_dtype(dtype, "ce_fwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((ce_fwd_kernel<T>), dim3(nb), dim3(kCeThreads), 0, st, (const T*)logits, target, npix, (int)C, ignore_index, ws);
+        MRFP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, st, ws, nb, loss);
+        MRFP_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int mrfp_ce_bwd(const void* logits, const int64_t* target, const float* loss, const float* gscale, void* dlogits,
@@ -148,16 +144,13 @@ int mrfp_ce_bwd(const void* logits, const int64_t* target, const float* loss, co
     MRFP_CHECK(logits && target && loss && dlogits && npix > 0 && C > 0, "ce_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     const int nb = ce_blocks(npix);
-    if (dtype == MRFP_F32)
-        hipLaunchKernelGGL((ce_bwd_kernel<float>), dim3(nb), dim3(kCeThreads), 0, st, (const float*)logits, target, loss, gscale, (float*)dlogits, npix, (int)C, ignore_index);
-    else if (dtype == MRFP_BF16)
-        hipLaunchKernelGGL((ce_bwd_kernel<bf16>), dim3(nb), dim3(kCeThreads), 0, st, (const bf16*)logits, target, loss, gscale, (bf16*)dlogits, npix, (int)C, ignore_index);
-    else if (dtype == MRFP_F16)
-        hipLaunchKernelGGL((ce_bwd_kernel<f16>), dim3(nb), dim3(kCeThreads), 0, st, (const f16*)logits, target, loss, gscale, (f16*)dlogits, npix, (int)C, ignore_index);
-    else
-        MRFP_CHECK(false, "ce_bwd: unknown dtype %d", dtype);
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return by_dtype(dtype, "ce_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((ce_bwd_kernel<T>), dim3(nb), dim3(kCeThreads), 0, st, (const T*)logits, target, loss, gscale, (T*)dlogits, npix,
+                           (int)C, ignore_index);
+        MRFP_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int mrfp_argmax_hist(const void* logits, const int64_t* target, int dtype, int64_t npix, int64_t C, int64_t* hist,
@@ -166,16 +159,13 @@ int mrfp_argmax_hist(const void* logits, const int64_t* target, int dtype, int64
     MRFP_CHECK(!target || hist, "argmax_hist: target given without hist");
     hipStream_t st = (hipStream_t)stream;
     const int nb = ce_blocks(npix);
-    if (dtype == MRFP_F32)
-        hipLaunchKernelGGL((argmax_hist_kernel<float>), dim3(nb), dim3(kCeThreads), 0, st, (const float*)logits, target, npix, (int)C, (unsigned long long*)hist, pred);
-    else if (dtype == MRFP_BF16)
-        hipLaunchKernelGGL((argmax_hist_kernel<bf16>), dim3(nb), dim3(kCeThreads), 0, st, (const bf16*)logits, target, npix, (int)C, (unsigned long long*)hist, pred);
-    else if (dtype == MRFP_F16)
-        hipLaunchKernelGGL((argmax_hist_kernel<f16>), dim3(nb), dim3(kCeThreads), 0, st, (const f16*)logits, target, npix, (int)C, (unsigned long long*)hist, pred);
-    else
-        MRFP_CHECK(false, "argmax_hist: unknown dtype %d", dtype);
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return by_dtype(dtype, "argmax_hist", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((argmax_hist_kernel<T>), dim3(nb), dim3(kCeThreads), 0, st, (const T*)logits, target, npix, (int)C,
+                           (unsigned long long*)hist, pred);
+        MRFP_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 }  // extern "C"
@@ -340,21 +330,21 @@ int mrfp_upsample_ce_fwd(const void* P, int64_t ld, const int64_t* target, int d
                          int64_t H, int64_t W, int64_t C, int64_t ignore_index, float* ws, float* loss, void* stream) {
     MRFP_CHECK(P && target && ws && loss && B > 0 && Hi > 0 && Wi > 0 && H > 0 && W > 0 && C > 0 && C <= mrfp::kMaxClasses,
                "upsample_ce_fwd: bad arguments");
-    const int esz = dtype == MRFP_F32 ? 4 : 2, epc = 16 / esz;
-    MRFP_CHECK(dtype == MRFP_F32 || dtype == MRFP_BF16 || dtype == MRFP_F16, "upsample_ce_fwd: unknown dtype %d", dtype);
+    MRFP_CHECK(mrfp::dtype_known(dtype), "upsample_ce_fwd: unknown dtype %d", dtype);
+    const int epc = 16 / mrfp::dtype_bytes(dtype);
     MRFP_CHECK(ld % epc == 0 && ld >= (C + epc - 1) / epc * epc && mrfp::aligned16(P),
                "upsample_ce_fwd: the score buffer must be channel-padded to 16-byte chunks (ld=%lld)", (long long)ld);
     hipStream_t st = (hipStream_t)stream;
     const int nb = mrfp::ce_blocks(B * H * W);
     mrfp::UpCeArgs a{P, (int)ld, target, nullptr, nullptr, nullptr, 0, (int)B, (int)Hi, (int)Wi, (int)H, (int)W, (int)C,
                      ignore_index, ws, nb, st};
-    if (dtype == MRFP_F32) mrfp::dispatch_up_ce<float>(a, false);
-    else if (dtype == MRFP_F16) mrfp::dispatch_up_ce<mrfp::f16>(a, false);
-    else mrfp::dispatch_up_ce<mrfp::bf16>(a, false);
-    MRFP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mrfp::ce_finalize_kernel, dim3(1), dim3(256), 0, st, ws, nb, loss);
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return mrfp::by_dtype(dtype, "upsample_ce_fwd", [&](auto t) {
+        mrfp::dispatch_up_ce<typename decltype(t)::type>(a, false);
+        MRFP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(mrfp::ce_finalize_kernel, dim3(1), dim3(256), 0, st, ws, nb, loss);
+        MRFP_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int mrfp_upsample_ce_bwd(const void* P, int64_t ld, const int64_t* target, const float* loss, const float* gscale,
@@ -362,19 +352,19 @@ int mrfp_upsample_ce_bwd(const void* P, int64_t ld, const int64_t* target, const
                          int64_t C, int64_t ignore_index, void* stream) {
     MRFP_CHECK(P && target && loss && dlogits && B > 0 && Hi > 0 && Wi > 0 && H > 0 && W > 0 && C > 0 && C <= mrfp::kMaxClasses,
                "upsample_ce_bwd: bad arguments");
-    const int esz = dtype == MRFP_F32 ? 4 : 2, epc = 16 / esz;
-    MRFP_CHECK(dtype == MRFP_F32 || dtype == MRFP_BF16 || dtype == MRFP_F16, "upsample_ce_bwd: unknown dtype %d", dtype);
+    MRFP_CHECK(mrfp::dtype_known(dtype), "upsample_ce_bwd: unknown dtype %d", dtype);
+    const int epc = 16 / mrfp::dtype_bytes(dtype);
     MRFP_CHECK(ld % epc == 0 && Cd % epc == 0 && Cd >= C && ld >= Cd && mrfp::aligned16(P) && mrfp::aligned16(dlogits),
                "upsample_ce_bwd: channel pitches must be 16-byte multiples (ld=%lld Cd=%lld)", (long long)ld, (long long)Cd);
     hipStream_t st = (hipStream_t)stream;
     const int nb = mrfp::ce_blocks(B * H * W);
     mrfp::UpCeArgs a{P, (int)ld, target, loss, gscale, dlogits, (int)Cd, (int)B, (int)Hi, (int)Wi, (int)H, (int)W, (int)C,
                      ignore_index, nullptr, nb, st};
-    if (dtype == MRFP_F32) mrfp::dispatch_up_ce<float>(a, true);
-    else if (dtype == MRFP_F16) mrfp::dispatch_up_ce<mrfp::f16>(a, true);
-    else mrfp::dispatch_up_ce<mrfp::bf16>(a, true);
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    return mrfp::by_dtype(dtype, "upsample_ce_bwd", [&](auto t) {
+        mrfp::dispatch_up_ce<typename decltype(t)::type>(a, true);
+        MRFP_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 }  // extern "C"

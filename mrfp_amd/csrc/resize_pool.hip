@@ -464,15 +464,6 @@ __global__ __launch_bounds__(kThreads) void pool_norm_bwd_kernel(const T* __rest
     }
 }
 
-#define DISPATCH_VEC(T, C, ok, KERNEL, grid, st, ...)                                                      \
-    do {                                                                                                   \
-        if (pick_vec<T>(C) > 1 && (ok))                                                                    \
-            hipLaunchKernelGGL((KERNEL<T, FullVec<T>::value>), grid, dim3(kThreads), 0, st, __VA_ARGS__);  \
-        else                                                                                               \
-            hipLaunchKernelGGL((KERNEL<T, 1>), grid, dim3(kThreads), 0, st, __VA_ARGS__);                  \
-        MRFP_LAUNCH_CHECK();                                                                               \
-    } while (0)
-
 template <typename T>
 static int do_bilinear_fwd(const void* x, const void* addend, void* y, int64_t B, int64_t Hi, int64_t Wi, int64_t Ho,
                            int64_t Wo, int64_t C, int64_t ldi, hipStream_t st, int64_t ldo = 0) {
@@ -480,8 +471,8 @@ static int do_bilinear_fwd(const void* x, const void* addend, void* y, int64_t B
     if (ldo <= 0) ldo = C;
     const bool ok = aligned16(x) && aligned16(y) && (!addend || aligned16(addend)) && ldi % FullVec<T>::value == 0 &&
                     ldo % FullVec<T>::value == 0;
-    DISPATCH_VEC(T, C, ok, bilinear_fwd_kernel, dim3((unsigned)(B * ly)), st, (const T*)x, (const T*)addend, (T*)y,
-                 (int)B, (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)C, (int)ldi, ly, (int)ldo);
+    MRFP_DISPATCH_VEC(T, C, ok, bilinear_fwd_kernel, dim3((unsigned)(B * ly)), st, (const T*)x, (const T*)addend, (T*)y,
+                      (int)B, (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)C, (int)ldi, ly, (int)ldo);
     return 0;
 }
 template <typename T>
@@ -493,28 +484,20 @@ static int do_bilinear_bwd(const void* dy, void* dx, int64_t B, int64_t Hi, int6
     // destination columns per source column: ceil(2*(Wo-1)/(Wi-1)) + 2 (see ac_range)
     const int64_t kw = (Wi > 1 && Wo > 1) ? (2 * (Wo - 1) + (Wi - 1) - 1) / (Wi - 1) + 2 : (int64_t)1 << 30;
     const dim3 grid((unsigned)(B * ly));
-    const int full = FullVec<T>::value;
     const bool vec = ok && pick_vec<T>(C) > 1;
-#define MRFP_BWD_LAUNCH(VECV, KWV, ...)                                                                                     \
-    hipLaunchKernelGGL((bilinear_bwd_kernel<T, VECV, KWV, ##__VA_ARGS__>), grid, dim3(kThreads), 0, st, (const T*)dy, (T*)dx, (int)B, \
-                       (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)C, (int)ldi, ly, (int)ldd)
+    auto launch = [&](auto kwv, auto knv) {      // KW candidate columns, KN of them evaluated (0: all; the scalar kernel always takes all)
+        constexpr int KW = decltype(kwv)::value, KN = decltype(knv)::value;
+        MRFP_LAUNCH_VEC(vec, (bilinear_bwd_kernel<T, FullVec<T>::value, KW, KN>), (bilinear_bwd_kernel<T, 1, KW>), grid, st, (const T*)dy,
+                        (T*)dx, (int)B, (int)Hi, (int)Wi, (int)Ho, (int)Wo, (int)C, (int)ldi, ly, (int)ldd);
+        return 0;
+    };
     static const int win = env_switch("MRFP_BILINEAR_WINDOW", 1);      // =0: every candidate column evaluated (A/B runs, the bit-identity test)
-    if (vec) {
-        if (kw <= 4) MRFP_BWD_LAUNCH(full, 4);
-        else if (kw == 7 && win) MRFP_BWD_LAUNCH(full, 8, 5);          // 2x (the loss head, the class-score upsample): 5 of 8 slots
-        else if (kw <= 8) MRFP_BWD_LAUNCH(full, 8);
-        else if (kw == 11 && win) MRFP_BWD_LAUNCH(full, 12, 9);        // 4x (the decoder): 9 of 12
-        else if (kw <= 12) MRFP_BWD_LAUNCH(full, 12);
-        else MRFP_BWD_LAUNCH(full, 0);
-    } else {
-        if (kw <= 4) MRFP_BWD_LAUNCH(1, 4);
-        else if (kw <= 8) MRFP_BWD_LAUNCH(1, 8);
-        else if (kw <= 12) MRFP_BWD_LAUNCH(1, 12);
-        else MRFP_BWD_LAUNCH(1, 0);
-    }
-#undef MRFP_BWD_LAUNCH
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    if (kw <= 4) return launch(Int<4>{}, Int<0>{});
+    if (kw == 7 && win) return launch(Int<8>{}, Int<5>{});             // 2x (the loss head, the class-score upsample): 5 of 8 slots
+    if (kw <= 8) return launch(Int<8>{}, Int<0>{});
+    if (kw == 11 && win) return launch(Int<12>{}, Int<9>{});           // 4x (the decoder): 9 of 12
+    if (kw <= 12) return launch(Int<12>{}, Int<0>{});
+    return launch(Int<0>{}, Int<0>{});
 }
 template <typename T>
 static int do_maxpool_fwd(const void* x, void* y, uint8_t* idx, int64_t B, int64_t H, int64_t W, int64_t C,
@@ -524,8 +507,8 @@ static int do_maxpool_fwd(const void* x, void* y, uint8_t* idx, int64_t B, int64
     const int ly = lines_per_image(B, Ho);
     const bool ok = aligned16(x) && aligned16(y) && ((uintptr_t)idx % FullVec<T>::value) == 0 &&
                     (!A || (aligned16(A) && aligned16(S) && C % 4 == 0));
-    DISPATCH_VEC(T, C, ok, maxpool_fwd_kernel, dim3((unsigned)(B * ly)), st, (const T*)x, (T*)y, idx, (int)B, (int)H,
-                 (int)W, Ho, Wo, (int)C, ly, A, S, per_image, relu);
+    MRFP_DISPATCH_VEC(T, C, ok, maxpool_fwd_kernel, dim3((unsigned)(B * ly)), st, (const T*)x, (T*)y, idx, (int)B, (int)H,
+                      (int)W, Ho, Wo, (int)C, ly, A, S, per_image, relu);
     return 0;
 }
 template <typename T>
@@ -537,17 +520,14 @@ static int do_pool_norm_bwd(int pass, const void* dy, const uint8_t* idx, const 
     bool ok = aligned16(dy) && aligned16(x) && (!dx || aligned16(dx)) && ((uintptr_t)idx % FullVec<T>::value) == 0 && C % 4 == 0;
     for (const float* c : {mean, fA, fS, P, Q, R}) ok = ok && (!c || aligned16(c));
     const dim3 grid((unsigned)(B * ly));
-#define MRFP_PNB(VECV, PASSV)                                                                                                  \
-    hipLaunchKernelGGL((pool_norm_bwd_kernel<T, VECV, PASSV>), grid, dim3(kThreads), 0, st, (const T*)dy, idx, (const T*)x,   \
-                       (T*)dx, ws, (int)B, (int)H, (int)W, Ho, Wo, (int)C, ly, mean, fA, fS, P, Q, R, per_image, relu)
-    if (pick_vec<T>(C) > 1 && ok) {
-        if (pass == 0) MRFP_PNB(FullVec<T>::value, 0); else MRFP_PNB(FullVec<T>::value, 1);
-    } else {
-        if (pass == 0) MRFP_PNB(1, 0); else MRFP_PNB(1, 1);
-    }
-#undef MRFP_PNB
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    const bool vec = pick_vec<T>(C) > 1 && ok;
+    auto launch = [&](auto pv) {      // PASS: 0 statistics, 1 apply
+        constexpr int PASS = decltype(pv)::value;
+        MRFP_LAUNCH_VEC(vec, (pool_norm_bwd_kernel<T, FullVec<T>::value, PASS>), (pool_norm_bwd_kernel<T, 1, PASS>), grid, st, (const T*)dy,
+                        idx, (const T*)x, (T*)dx, ws, (int)B, (int)H, (int)W, Ho, Wo, (int)C, ly, mean, fA, fS, P, Q, R, per_image, relu);
+        return 0;
+    };
+    return pass == 0 ? launch(Int<0>{}) : launch(Int<1>{});
 }
 template <typename T>
 static int do_maxpool_bwd(const void* dy, const uint8_t* idx, void* dx, int64_t B, int64_t H, int64_t W, int64_t C,
@@ -555,8 +535,8 @@ static int do_maxpool_bwd(const void* dy, const uint8_t* idx, void* dx, int64_t 
     const int Ho = (int)((H + 2 - 3) / 2 + 1), Wo = (int)((W + 2 - 3) / 2 + 1);
     const int ly = lines_per_image(B, H);
     const bool ok = aligned16(dy) && aligned16(dx) && ((uintptr_t)idx % FullVec<T>::value) == 0;
-    DISPATCH_VEC(T, C, ok, maxpool_bwd_kernel, dim3((unsigned)(B * ly)), st, (const T*)dy, idx, (T*)dx, (int)B, (int)H,
-                 (int)W, Ho, Wo, (int)C, ly);
+    MRFP_DISPATCH_VEC(T, C, ok, maxpool_bwd_kernel, dim3((unsigned)(B * ly)), st, (const T*)dy, idx, (T*)dx, (int)B, (int)H,
+                      (int)W, Ho, Wo, (int)C, ly);
     return 0;
 }
 
@@ -569,18 +549,18 @@ extern "C" {
 int mrfp_bilinear_fwd(const void* x, const void* addend, void* y, int dtype, int64_t B, int64_t Hi, int64_t Wi,
                       int64_t Ho, int64_t Wo, int64_t C, int64_t ld_in, void* stream) {
     MRFP_CHECK(x && y && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && ld_in >= C, "bilinear_fwd: bad arguments");
-    if (dtype == MRFP_F32) return do_bilinear_fwd<float>(x, addend, y, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream);
-    if (dtype == MRFP_BF16) return do_bilinear_fwd<bf16>(x, addend, y, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream);
-    if (dtype == MRFP_F16) return do_bilinear_fwd<f16>(x, addend, y, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream);
-    MRFP_CHECK(false, "bilinear_fwd: unknown dtype %d", dtype);
+    return by_dtype(dtype, "bilinear_fwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return do_bilinear_fwd<T>(x, addend, y, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream);
+    });
 }
 int mrfp_bilinear_bwd(const void* dy, void* dx, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t Ho, int64_t Wo,
                       int64_t C, int64_t ld_in, void* stream) {
     MRFP_CHECK(dy && dx && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && ld_in >= C, "bilinear_bwd: bad arguments");
-    if (dtype == MRFP_F32) return do_bilinear_bwd<float>(dy, dx, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream);
-    if (dtype == MRFP_BF16) return do_bilinear_bwd<bf16>(dy, dx, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream);
-    if (dtype == MRFP_F16) return do_bilinear_bwd<f16>(dy, dx, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream);
-    MRFP_CHECK(false, "bilinear_bwd: unknown dtype %d", dtype);
+    return by_dtype(dtype, "bilinear_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return do_bilinear_bwd<T>(dy, dx, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream);
+    });
 }
 /* The same with the OUTPUT (forward) / the incoming gradient (backward) being a block of C channels inside a wider NHWC tensor
  * of ld_out channels per pixel (y / dy point at the block's first channel): Upsample() writing straight into its slot of a
@@ -588,68 +568,64 @@ int mrfp_bilinear_bwd(const void* dy, void* dx, int dtype, int64_t B, int64_t Hi
 int mrfp_bilinear_fwd_into(const void* x, void* y, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t Ho, int64_t Wo,
                            int64_t C, int64_t ld_in, int64_t ld_out, void* stream) {
     MRFP_CHECK(x && y && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && ld_in >= C && ld_out >= C, "bilinear_fwd_into: bad arguments");
-    if (dtype == MRFP_F32) return do_bilinear_fwd<float>(x, nullptr, y, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream, ld_out);
-    if (dtype == MRFP_BF16) return do_bilinear_fwd<bf16>(x, nullptr, y, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream, ld_out);
-    if (dtype == MRFP_F16) return do_bilinear_fwd<f16>(x, nullptr, y, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream, ld_out);
-    MRFP_CHECK(false, "bilinear_fwd_into: unknown dtype %d", dtype);
+    return by_dtype(dtype, "bilinear_fwd_into", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return do_bilinear_fwd<T>(x, nullptr, y, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream, ld_out);
+    });
 }
 int mrfp_bilinear_bwd_from(const void* dy, void* dx, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t Ho, int64_t Wo,
                            int64_t C, int64_t ld_in, int64_t ld_dy, void* stream) {
     MRFP_CHECK(dy && dx && B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && C > 0 && ld_in >= C && ld_dy >= C, "bilinear_bwd_from: bad arguments");
-    if (dtype == MRFP_F32) return do_bilinear_bwd<float>(dy, dx, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream, ld_dy);
-    if (dtype == MRFP_BF16) return do_bilinear_bwd<bf16>(dy, dx, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream, ld_dy);
-    if (dtype == MRFP_F16) return do_bilinear_bwd<f16>(dy, dx, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream, ld_dy);
-    MRFP_CHECK(false, "bilinear_bwd_from: unknown dtype %d", dtype);
+    return by_dtype(dtype, "bilinear_bwd_from", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return do_bilinear_bwd<T>(dy, dx, B, Hi, Wi, Ho, Wo, C, ld_in, (hipStream_t)stream, ld_dy);
+    });
 }
 int mrfp_maxpool_fwd(const void* x, void* y, uint8_t* idx, int dtype, int64_t B, int64_t H, int64_t W, int64_t C,
                      void* stream) {
     MRFP_CHECK(x && y && idx && B > 0 && H > 0 && W > 0 && C > 0, "maxpool_fwd: bad arguments");
-    if (dtype == MRFP_F32) return do_maxpool_fwd<float>(x, y, idx, B, H, W, C, (hipStream_t)stream);
-    if (dtype == MRFP_BF16) return do_maxpool_fwd<bf16>(x, y, idx, B, H, W, C, (hipStream_t)stream);
-    if (dtype == MRFP_F16) return do_maxpool_fwd<f16>(x, y, idx, B, H, W, C, (hipStream_t)stream);
-    MRFP_CHECK(false, "maxpool_fwd: unknown dtype %d", dtype);
+    return by_dtype(dtype, "maxpool_fwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return do_maxpool_fwd<T>(x, y, idx, B, H, W, C, (hipStream_t)stream);
+    });
 }
 int mrfp_maxpool_affine_fwd(const void* x, const float* A, const float* S, int coef_per_image, int relu, void* y, uint8_t* idx,
                             int dtype, int64_t B, int64_t H, int64_t W, int64_t C, void* stream) {
     MRFP_CHECK(x && A && S && y && idx && B > 0 && H > 0 && W > 0 && C > 0, "maxpool_affine_fwd: bad arguments");
-    if (dtype == MRFP_F32) return do_maxpool_fwd<float>(x, y, idx, B, H, W, C, (hipStream_t)stream, A, S, coef_per_image, relu);
-    if (dtype == MRFP_BF16) return do_maxpool_fwd<bf16>(x, y, idx, B, H, W, C, (hipStream_t)stream, A, S, coef_per_image, relu);
-    if (dtype == MRFP_F16) return do_maxpool_fwd<f16>(x, y, idx, B, H, W, C, (hipStream_t)stream, A, S, coef_per_image, relu);
-    MRFP_CHECK(false, "maxpool_affine_fwd: unknown dtype %d", dtype);
+    return by_dtype(dtype, "maxpool_affine_fwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return do_maxpool_fwd<T>(x, y, idx, B, H, W, C, (hipStream_t)stream, A, S, coef_per_image, relu);
+    });
 }
 int mrfp_pool_norm_bwd_stats(const void* dy, const uint8_t* idx, const void* x, const float* mean, const float* fA,
                              const float* fS, int coef_per_image, int relu, float* ws, int dtype, int64_t B, int64_t H,
                              int64_t W, int64_t C, void* stream) {
     MRFP_CHECK(dy && idx && x && mean && ws && (!relu || (fA && fS)) && B > 0 && H > 0 && W > 0 && C > 0,
                "pool_norm_bwd_stats: bad arguments");
-#define MRFP_PNS(TT) return do_pool_norm_bwd<TT>(0, dy, idx, x, nullptr, ws, B, H, W, C, mean, fA, fS, nullptr, nullptr, nullptr, \
-                                                 coef_per_image, relu, (hipStream_t)stream)
-    if (dtype == MRFP_F32) MRFP_PNS(float);
-    if (dtype == MRFP_BF16) MRFP_PNS(bf16);
-    if (dtype == MRFP_F16) MRFP_PNS(f16);
-#undef MRFP_PNS
-    MRFP_CHECK(false, "pool_norm_bwd_stats: unknown dtype %d", dtype);
+    return by_dtype(dtype, "pool_norm_bwd_stats", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return do_pool_norm_bwd<T>(0, dy, idx, x, nullptr, ws, B, H, W, C, mean, fA, fS, nullptr, nullptr, nullptr, coef_per_image, relu,
+                                   (hipStream_t)stream);
+    });
 }
 int mrfp_pool_norm_bwd_apply(const void* dy, const uint8_t* idx, const void* x, const float* P, const float* Q, const float* R,
                              const float* fA, const float* fS, int coef_per_image, int relu, void* dx, int dtype, int64_t B,
                              int64_t H, int64_t W, int64_t C, void* stream) {
     MRFP_CHECK(dy && idx && x && P && Q && R && dx && (!relu || (fA && fS)) && B > 0 && H > 0 && W > 0 && C > 0,
                "pool_norm_bwd_apply: bad arguments");
-#define MRFP_PNA(TT) return do_pool_norm_bwd<TT>(1, dy, idx, x, dx, nullptr, B, H, W, C, nullptr, fA, fS, P, Q, R, coef_per_image, \
-                                                 relu, (hipStream_t)stream)
-    if (dtype == MRFP_F32) MRFP_PNA(float);
-    if (dtype == MRFP_BF16) MRFP_PNA(bf16);
-    if (dtype == MRFP_F16) MRFP_PNA(f16);
-#undef MRFP_PNA
-    MRFP_CHECK(false, "pool_norm_bwd_apply: unknown dtype %d", dtype);
+    return by_dtype(dtype, "pool_norm_bwd_apply", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return do_pool_norm_bwd<T>(1, dy, idx, x, dx, nullptr, B, H, W, C, nullptr, fA, fS, P, Q, R, coef_per_image, relu,
+                                   (hipStream_t)stream);
+    });
 }
 int mrfp_maxpool_bwd(const void* dy, const uint8_t* idx, void* dx, int dtype, int64_t B, int64_t H, int64_t W,
                      int64_t C, void* stream) {
     MRFP_CHECK(dy && dx && idx && B > 0 && H > 0 && W > 0 && C > 0, "maxpool_bwd: bad arguments");
-    if (dtype == MRFP_F32) return do_maxpool_bwd<float>(dy, idx, dx, B, H, W, C, (hipStream_t)stream);
-    if (dtype == MRFP_BF16) return do_maxpool_bwd<bf16>(dy, idx, dx, B, H, W, C, (hipStream_t)stream);
-    if (dtype == MRFP_F16) return do_maxpool_bwd<f16>(dy, idx, dx, B, H, W, C, (hipStream_t)stream);
-    MRFP_CHECK(false, "maxpool_bwd: unknown dtype %d", dtype);
+    return by_dtype(dtype, "maxpool_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return do_maxpool_bwd<T>(dy, idx, dx, B, H, W, C, (hipStream_t)stream);
+    });
 }
 
 }  // extern "C"

@@ -163,14 +163,13 @@ static int launch_stats(const void* x, const void* dy, const void* y, const floa
             return -1;
         }
     }
-#define MRFP_STATS_LAUNCH(VECV, RS)                                                                                    \
-    hipLaunchKernelGGL((stats_kernel<T, VECV, MODE, RS>), grid, dim3(kThreads), 0, st, (const T*)x, (const T*)dy,      \
-                       (const T*)y, mean, fA, fS, per_image, g, ly, ws)
-    if (vec_ok) { if (resize) MRFP_STATS_LAUNCH(FullVec<T>::value, true); else MRFP_STATS_LAUNCH(FullVec<T>::value, false); }
-    else { if (resize) MRFP_STATS_LAUNCH(1, true); else MRFP_STATS_LAUNCH(1, false); }
-#undef MRFP_STATS_LAUNCH
-    MRFP_LAUNCH_CHECK();
-    return 0;
+    auto launch = [&](auto rs) {      // RS: through the index tables or not
+        constexpr bool RS = decltype(rs)::value != 0;
+        MRFP_LAUNCH_VEC(vec_ok, (stats_kernel<T, FullVec<T>::value, MODE, RS>), (stats_kernel<T, 1, MODE, RS>), grid, st, (const T*)x,
+                        (const T*)dy, (const T*)y, mean, fA, fS, per_image, g, ly, ws);
+        return 0;
+    };
+    return resize ? launch(Int<1>{}) : launch(Int<0>{});
 }
 
 // ------------------------------------------------------------------------------------------
@@ -509,10 +508,10 @@ int mrfp_stats_fwd(const void* x, int dtype, int64_t B, int64_t Ho, int64_t Wo, 
     MRFP_CHECK(x && ws && B > 0 && Ho > 0 && Wo > 0 && C > 0, "stats_fwd: bad arguments");
     MRFP_CHECK(C <= 65536 && B * Ho < (1LL << 31), "stats_fwd: shape out of range");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_F32) return launch_stats<float, 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, Ho, Wo, C, Hs, Ws, tabH, tabW, ws, st);
-    if (dtype == MRFP_BF16) return launch_stats<bf16, 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, Ho, Wo, C, Hs, Ws, tabH, tabW, ws, st);
-    if (dtype == MRFP_F16) return launch_stats<f16, 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, Ho, Wo, C, Hs, Ws, tabH, tabW, ws, st);
-    MRFP_CHECK(false, "stats_fwd: unknown dtype %d", dtype);
+    return by_dtype(dtype, "stats_fwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_stats<T, 0>(x, nullptr, nullptr, nullptr, nullptr, nullptr, 0, B, Ho, Wo, C, Hs, Ws, tabH, tabW, ws, st);
+    });
 }
 
 int mrfp_stats_bwd(const void* dy, const void* x, const void* y, const float* mean, const float* fA, const float* fS,
@@ -521,19 +520,20 @@ int mrfp_stats_bwd(const void* dy, const void* x, const void* y, const float* me
                    const int32_t* tabW, float* ws, void* stream) {
     MRFP_CHECK(dy && x && ws && B > 0 && Ho > 0 && Wo > 0 && C > 0, "stats_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_F32) return launch_stats<float, 1>(x, dy, y, mean, fA, fS, per_image, B, Ho, Wo, C, Hs, Ws, tabH, tabW, ws, st);
-    if (dtype == MRFP_BF16) return launch_stats<bf16, 1>(x, dy, y, mean, fA, fS, per_image, B, Ho, Wo, C, Hs, Ws, tabH, tabW, ws, st);
-    if (dtype == MRFP_F16) return launch_stats<f16, 1>(x, dy, y, mean, fA, fS, per_image, B, Ho, Wo, C, Hs, Ws, tabH, tabW, ws, st);
-    MRFP_CHECK(false, "stats_bwd: unknown dtype %d", dtype);
+    return by_dtype(dtype, "stats_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_stats<T, 1>(x, dy, y, mean, fA, fS, per_image, B, Ho, Wo, C, Hs, Ws, tabH, tabW, ws, st);
+    });
 }
 
 int mrfp_stats_bwd_mask(const void* dy, const void* x, const void* mask, const float* mean, int per_image, int dtype, int64_t B,
                         int64_t H, int64_t W, int64_t C, float* ws, void* stream) {
     MRFP_CHECK(dy && x && mask && ws && B > 0 && H > 0 && W > 0 && C > 0 && (C & 7) == 0, "stats_bwd_mask: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_BF16) return launch_stats<bf16, 1>(x, dy, mask, mean, nullptr, nullptr, per_image, B, H, W, C, H, W, nullptr, nullptr, ws, st, true);
-    if (dtype == MRFP_F16) return launch_stats<f16, 1>(x, dy, mask, mean, nullptr, nullptr, per_image, B, H, W, C, H, W, nullptr, nullptr, ws, st, true);
-    MRFP_CHECK(false, "stats_bwd_mask: 16-bit activations only (dtype %d)", dtype);
+    return by_dtype16(dtype, "stats_bwd_mask", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_stats<T, 1>(x, dy, mask, mean, nullptr, nullptr, per_image, B, H, W, C, H, W, nullptr, nullptr, ws, st, true);
+    });
 }
 
 int mrfp_bn_finalize(const float* ws, int64_t B, int64_t nslab, int64_t count, int64_t C, const float* weight,
@@ -615,22 +615,19 @@ int mrfp_mean_finalize(const float* ws, int64_t B, int64_t nslab, int64_t count,
                        int dtype, void* stream) {
     MRFP_CHECK(ws && out && tmp && C > 0 && B > 0 && B < 65536, "mean_finalize: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    float* dst = dtype == MRFP_F32 ? (float*)out : tmp;
-    hipLaunchKernelGGL(plane_sum_kernel, dim3((unsigned)((C + mrfp::kFC - 1) / mrfp::kFC), (unsigned)B), dim3(mrfp::kFC, mrfp::kFL), 0, st, ws, nslab,
-                       1.0 / (double)count, (int)C, dst);
-    MRFP_LAUNCH_CHECK();
-    if (dtype == MRFP_BF16) {
-        const int64_t n = B * C;
-        hipLaunchKernelGGL((cast_out_kernel<bf16>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tmp, (bf16*)out, n);
+    return by_dtype(dtype, "mean_finalize", [&](auto t) {      // (the dtype is refused before anything is enqueued)
+        using T = typename decltype(t)::type;
+        constexpr bool cast = !std::is_same<T, float>::value;      // the means are summed in fp32: into `out` itself, or `tmp` and cast
+        hipLaunchKernelGGL(plane_sum_kernel, dim3((unsigned)((C + mrfp::kFC - 1) / mrfp::kFC), (unsigned)B), dim3(mrfp::kFC, mrfp::kFL), 0, st, ws,
+                           nslab, 1.0 / (double)count, (int)C, cast ? tmp : (float*)out);
         MRFP_LAUNCH_CHECK();
-    } else if (dtype == MRFP_F16) {
-        const int64_t n = B * C;
-        hipLaunchKernelGGL((cast_out_kernel<f16>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tmp, (f16*)out, n);
-        MRFP_LAUNCH_CHECK();
-    } else {
-        MRFP_CHECK(dtype == MRFP_F32, "mean_finalize: unknown dtype %d", dtype);
-    }
-    return 0;
+        if constexpr (cast) {
+            const int64_t n = B * C;
+            hipLaunchKernelGGL((cast_out_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tmp, (T*)out, n);
+            MRFP_LAUNCH_CHECK();
+        }
+        return 0;
+    });
 }
 
 }  // extern "C"

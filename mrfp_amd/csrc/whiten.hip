@@ -485,10 +485,10 @@ int mrfp_group_moments(const void* a, const void* b, float* M, float* sum_a, voi
                (long long)B, (long long)HW, (long long)C);
     MRFP_CHECK(aligned16(a) && aligned16(b), "group_moments: activations must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_F32) return run_moments<float>(a, b, M, sum_a, (float*)ws, B, HW, C, st);
-    if (dtype == MRFP_BF16) return run_moments<bf16>(a, b, M, sum_a, (float*)ws, B, HW, C, st);
-    if (dtype == MRFP_F16) return run_moments<f16>(a, b, M, sum_a, (float*)ws, B, HW, C, st);
-    MRFP_CHECK(false, "group_moments: unknown dtype %d", dtype);
+    return by_dtype(dtype, "group_moments", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return run_moments<T>(a, b, M, sum_a, (float*)ws, B, HW, C, st);
+    });
 }
 
 int mrfp_group_apply(const void* x, const float* Wm, const void* z, const float* Vm, const float* shift, void* y, int dtype,
@@ -498,10 +498,10 @@ int mrfp_group_apply(const void* x, const float* Wm, const void* z, const float*
                (long long)B, (long long)HW, (long long)C);
     MRFP_CHECK(aligned16(x) && aligned16(y) && (!z || aligned16(z)), "group_apply: activations must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MRFP_F32) return run_apply<float>(x, Wm, z, Vm, shift, y, B, HW, C, st);
-    if (dtype == MRFP_BF16) return run_apply<bf16>(x, Wm, z, Vm, shift, y, B, HW, C, st);
-    if (dtype == MRFP_F16) return run_apply<f16>(x, Wm, z, Vm, shift, y, B, HW, C, st);
-    MRFP_CHECK(false, "group_apply: unknown dtype %d", dtype);
+    return by_dtype(dtype, "group_apply", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return run_apply<T>(x, Wm, z, Vm, shift, y, B, HW, C, st);
+    });
 }
 
 int mrfp_group_isqrt_fwd(const float* cov, float* wm, int64_t n, int T, void* stream) {

@@ -35,6 +35,54 @@ def test_host_only_entry_points(cdll):
     assert rc != 0 and b"add" in cdll.mrfp_last_error()
 
 
+def test_unknown_dtype_is_refused_before_any_launch(cdll):
+    """Every entry point takes its element type through one dispatch (csrc/common.hpp: by_dtype / by_dtype16 / dtype_known), which
+    refuses an unknown dtype on the host with the entry point's own message: one entry point per translation unit that dispatches on
+    the dtype, the 16-bit-only form included, with dtype 99 and otherwise valid arguments (pointers into a host buffer -- nothing is
+    launched, so this needs no GPU).  The texts are the ones the per-entry-point chains produced before the dispatch was shared.
+    mrfp_mean_finalize used to enqueue its reduction before it looked at the dtype; it now refuses first, with the dtype message."""
+    buf = ctypes.create_string_buffer(1 << 16)
+    p = (ctypes.addressof(buf) + 255) & ~255          # 16-byte aligned, like every tensor the library is given
+    BAD = 99
+    cases = [
+        # affine.hip
+        ("mrfp_add", (p, p, p, BAD, 64, None), b"add: unknown dtype 99"),
+        ("mrfp_affine_fwd_relu_mask", (p, None, p, p, BAD, 1, 4, 4, 8, p, p, 0, None),
+         b"affine_fwd_relu_mask: 16-bit activations only (dtype 99)"),
+        # resize_pool.hip
+        ("mrfp_maxpool_fwd", (p, p, p, BAD, 1, 4, 4, 8, None), b"maxpool_fwd: unknown dtype 99"),
+        ("mrfp_pool_norm_bwd_stats", (p, p, p, p, None, None, 0, 0, p, BAD, 1, 4, 4, 8, None), b"pool_norm_bwd_stats: unknown dtype 99"),
+        # loss.hip
+        ("mrfp_ce_fwd", (p, p, BAD, 16, 19, 255, p, p, None), b"ce_fwd: unknown dtype 99"),
+        ("mrfp_upsample_ce_fwd", (p, 24, p, BAD, 1, 2, 2, 4, 4, 19, 255, p, p, None), b"upsample_ce_fwd: unknown dtype 99"),
+        # conv_dw.hip
+        ("mrfp_dwconv_fwd", (p, p, None, p, BAD, 1, 4, 4, 8, 8, 4, 4, 1, 1, None, None), b"dwconv: unsupported dtype 99"),
+        ("mrfp_mask_gate", (p, p, p, BAD, 64, None), b"mask_gate: unsupported dtype 99"),
+        # stats.hip
+        ("mrfp_stats_fwd", (p, BAD, 1, 4, 4, 8, 4, 4, None, None, p, None), b"stats_fwd: unknown dtype 99"),
+        ("mrfp_stats_bwd_mask", (p, p, p, p, 0, BAD, 1, 4, 4, 8, p, None), b"stats_bwd_mask: 16-bit activations only (dtype 99)"),
+        ("mrfp_mean_finalize", (p, 1, 4, 16, 8, p, p, BAD, None), b"mean_finalize: unknown dtype 99"),
+        # conv_pack.hip
+        ("mrfp_pack_weight", (p, p, None, BAD, 8, 8, 3, 3, 8, 8, None), b"pack_weight: unknown dtype 99"),
+        ("mrfp_pack_weights_folded_batched", (p, p, 1, 64, BAD, None), b"pack_weight_folded: unknown dtype 99"),
+        # whiten.hip
+        ("mrfp_group_moments", (p, p, p, None, p, BAD, 1, 16, 16, None), b"group_moments: unknown dtype 99"),
+        # conv_igemm.hip
+        ("mrfp_conv_fwd", (p, p, None, p, BAD, 1, 4, 4, 8, 8, 8, 3, 3, 4, 4, 1, 1, 1, 1, 1, None, None, None),
+         b"conv_fwd: unknown dtype 99"),
+        # conv_wgrad.hip
+        ("mrfp_conv_wgrad", (p, p, p, p, BAD, 1, 4, 4, 8, 8, 8, 8, 3, 3, 4, 4, 1, 1, 1, 1, None), b"conv_wgrad: unknown dtype 99"),
+        # eval.hip
+        ("mrfp_prob_accum", (p, BAD, 1, 4, 4, 19, p, p, 4, 4, 19, 0, 0, 4, 4, 0, 1.0, None), b"prob_accum: unknown dtype 99"),
+        # fft.hip
+        ("mrfp_fourier_mix", (p, p, None, p, p, None, 0, p, p, BAD, 1, 8, 8, 16, 2.0, 0.5, 0, None), b"fourier_mix: unknown dtype 99"),
+    ]
+    for name, args, text in cases:
+        assert len(args) == len(_lib.ARG_NAMES[name]), name
+        rc = getattr(cdll, name)(*args)
+        assert rc == -1 and cdll.mrfp_last_error() == text, (name, rc, cdll.mrfp_last_error())
+
+
 def test_row_kernels_give_every_workgroup_the_same_number_of_lines(cdll):
     """mrfp_stats_nslab(B, Ho) = workgroups per image of the statistics / apply / pool kernels (workgroup j walks lines j, j + n, ...):
     at most the cap (2048 workgroups per launch), never more than the lines, and no workgroup with more than one line above another
