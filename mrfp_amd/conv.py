@@ -7,7 +7,10 @@ step, HRFP re-initialisation, load_state_dict).
 """
 from __future__ import annotations
 
+import collections
 import ctypes
+import os as _os
+import warnings
 import weakref
 from typing import Any, NamedTuple, Optional
 
@@ -16,9 +19,9 @@ import torch
 from . import _lib
 from ._lib import call, dt, ptr, stream
 from .ops import CL, GRAD_DEFERRED, _chk, channel_sums, empty_cl, grad_sink, notify_grad, wgrad_workspace, zeros_cl
+from .ops import _inside_autograd_engine as _in_backward
 
 _PACKS = {}      # id(weight Parameter) -> {key: _Pack}; entry dropped when the Parameter dies
-import os as _os
 FUSE_STATS = [_os.environ.get("MRFP_FUSE_STATS", "1") != "0"]   # conv epilogues emit BatchNorm partial statistics for bias-free convolutions
 
 
@@ -442,200 +445,189 @@ def _out_size(H, R, stride, pad, dil):
     return (H + 2 * pad - dil * (R - 1) - 1) // stride + 1
 
 
-# ---- second stream for the weight gradients ---------------------------------------------------------------------
+# ---- weight gradients: one launcher, one scheduler --------------------------------------------------------------------------------
+# The weight gradient feeds nothing but the optimizer, so it may run beside the dgrad chain and it may wait.
+# Second stream (MRFP_WGRAD_STREAM): with a gradient arena present (harness.FlatArena) the launches go to a side stream, concurrently
+# with the dgrad chain of the main stream (their workgroups fill the tails / small-kernel gaps of that chain).  Ordering: the side
+# stream waits for dy (an event on the main stream); the consumers of the arena (optimizer step, gradient all-reduce) wait for the
+# side stream (harness.Trainer / GradSync, join_wgrad_stream()).
+# Grouped, deferred launches (MRFP_WGRAD_GROUP): a ResNet stage is `blocks` Bottlenecks of ONE geometry (reference
+# network/Resnet.py:579-585 _make_layer; autograd of Resnet.py:202-216 yields their weight gradients one launch at a time).  At
+# M = 16*48*48 a single launch has 16-72 output tiles and needs 21-32 K' splits to fill 256 CUs -- 12 K' tiles per workgroup behind a
+# prologue, and fp32 slabs of 20-30x the size of dW written and read again.  So backward only QUEUES (x, dy, sink) per launch geometry
+# and a whole queue runs as one grouped launch + one slab reduction -- when a queue is full or complete, when backward leaves a stage
+# (wgrad_boundary), and when backward ends.  _WgradScheduler decides all of that; _launch_wgrads is the only launcher.
 USE_WGRAD_STREAM = [_os.environ.get("MRFP_WGRAD_STREAM", "1") != "0"]
-_WGRAD_STREAMS = {}
-_WGRAD_PENDING = [False]
-
-
-def wgrad_stream(device):
-    """The side stream weight gradients are computed on (None when disabled or while a hipGraph is being captured)."""
-    if not USE_WGRAD_STREAM[0] or device.type != "cuda" or torch.cuda.is_current_stream_capturing():
-        return None
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    st = _WGRAD_STREAMS.get(key)
-    if st is None:
-        st = _WGRAD_STREAMS[key] = torch.cuda.Stream(device=device)
-    return st
-
-
-_JOIN_QUEUED = [False]
-
-
-def _join_at_end_of_backward():
-    _JOIN_QUEUED[0] = False
-    flush_wgrads()
-    # what this pass produced is what the next pass OF THE SAME KIND is expected to produce.  Passes are told apart by the
-    # geometry of their first weight gradient (the head's convolution: input shape, batch, dtype and class count are in it), so
-    # two models / two input shapes alternating in one process each keep their own expectation (VERDICT r4 weak 8) instead of
-    # flushing late or early on the other one's counts.  (Grouping is a speed matter only: every flush is a correct launch.)
-    if _WG_PASS_KEY[0] is not None:
-        if len(_WG_EXPECT_ALL) >= 64 and _WG_PASS_KEY[0] not in _WG_EXPECT_ALL:
-            _WG_EXPECT_ALL.pop(next(iter(_WG_EXPECT_ALL)))
-        _WG_EXPECT_ALL[_WG_PASS_KEY[0]] = dict(_WG_SEEN)
-    _WG_PASS_KEY[0] = None
-    _WG_EXPECT.clear()
-    _WG_SEEN.clear()
-    join_wgrad_stream()
-
-
-def join_wgrad_stream(stream=None):
-    """Makes `stream` (default: the current one) wait for every weight gradient issued so far."""
-    if not _WGRAD_PENDING[0]:
-        return
-    tgt = stream if stream is not None else torch.cuda.current_stream()
-    for st in _WGRAD_STREAMS.values():
-        tgt.wait_stream(st)
-    if stream is None:
-        _WGRAD_PENDING[0] = False
-
-
-# ---- grouped, deferred weight gradients ----------------------------------------------------------------------------
-# A ResNet stage is `blocks` Bottlenecks of ONE geometry (reference network/Resnet.py:579-585 _make_layer; autograd of
-# Resnet.py:202-216 yields their weight gradients one launch at a time).  At M = 16*48*48 a single launch has 16-72 output tiles
-# and needs 21-32 K' splits to fill 256 CUs -- 12 K' tiles per workgroup behind a prologue, and fp32 slabs of 20-30x the size of
-# dW written and read again.  Weight gradients feed nothing but the optimizer, so they can wait: with a gradient arena present
-# (harness.FlatArena) backward only QUEUES (x, dy, sink) per launch geometry and mrfp_conv_wgrad_grouped runs a whole queue as one
-# launch + one slab reduction -- when a queue is full, when backward leaves a stage (wgrad_boundary), and when backward ends.
 GROUP_WGRAD = [_os.environ.get("MRFP_WGRAD_GROUP", "1") != "0"]
-_WG_QUEUE = {}              # launch geometry -> [(x, dy, sink, weight)]
-_WG_PENDING_BYTES = [0]
-# Activations (x, dy) the queues may keep alive beyond the point where an immediate launch would have released them.
-# MRFP_WGRAD_GROUP_GB fixes it; by default it is a quarter of the device memory that is free when the first gradient is queued,
-# at most 24 GB (the bench step on a 288 GB part: 24; a large-activation configuration -- configs[4] -- on a fuller device gets
-# less and flushes earlier instead of raising the peak).
-_WG_MAX_BYTES = [int(float(_os.environ["MRFP_WGRAD_GROUP_GB"]) * (1 << 30)) if "MRFP_WGRAD_GROUP_GB" in _os.environ else None]
-import collections as _collections
-WGRAD_GROUP_LAUNCHES = _collections.deque(maxlen=4096)   # sizes of the last grouped launches (tests / diagnostics; bounded)
-_GROUP_MAX = [None]
-# How many problems of a geometry one backward pass produces is learnt from the previous pass: a geometry that came ONCE is
-# launched at once from then on (nothing to group with -- and the last layers of backward, the stem, would otherwise leave as an
-# exposed tail behind the end of the dgrad chain), a repeated one leaves as soon as its expected count is complete.
-_WG_EXPECT = {}             # launch geometry -> problems seen in the last complete backward pass of THIS kind (see _WG_PASS_KEY)
-_WG_SEEN = {}               # ... in the running one
-_WG_PASS_KEY = [None]       # geometry of the first weight gradient of the running backward pass
-_WG_EXPECT_ALL = {}         # pass key -> {launch geometry -> problems} of the last complete pass that started with it
-
-
+WGRAD_GROUP_LAUNCHES = collections.deque(maxlen=4096)   # sizes of the last launches the scheduler issued (tests / diagnostics; bounded)
 _DEBUG_SKIP_WGRAD = _os.environ.get("MRFP_DEBUG_SKIP_WGRAD") == "1"     # timing diagnostics only: weight gradients are NOT computed
 
 
-def _issue_wgrads(sig, items):
-    """One mrfp_conv_wgrad(_grouped) launch for `items` (same geometry) on the weight-gradient stream (or the current one)."""
-    import ctypes
-    if _DEBUG_SKIP_WGRAD:
-        for _, _, _, weight in items:
-            GRAD_DEFERRED.discard(id(weight))
-            notify_grad(weight)
-        return
+def _launch_wgrads(sig, items, side):
+    """ONE launch for `items` = [(x, dy, out)] of launch geometry `sig`: mrfp_conv_wgrad for one problem, mrfp_conv_wgrad_grouped for
+    several.  side: None = on the current stream; else on that stream, behind everything the current one holds so far (the operands
+    are recorded on it, the scheduler is told that a join is due).  Who is notified, and when this is called, is the caller's
+    matter; no autograd callback is registered here (flush_wgrads() also runs outside a backward pass: harness.GradSync.finish)."""
     (dtype, B, H, W, Cphys, C, N, Nphys, R, S, Ho, Wo, stride, pad_h, pad_w, dil) = sig
-    x0 = items[0][0]
-    M, Q = B * Ho * Wo, R * S * Cphys
-    side = wgrad_stream(x0.device)
+    n = len(items)
 
     def run():
-        n = len(items)
+        ws = wgrad_workspace(B * Ho * Wo, N, R * S * Cphys, items[0][0].device, n)
         if n == 1:
-            x, dy, sink, _ = items[0]
-            ws = wgrad_workspace(M, N, Q, x.device)
-            call("mrfp_conv_wgrad", ptr(x), ptr(dy), ptr(sink), ptr(ws), _lib._DT[dtype], B, H, W, Cphys, C, N, Nphys, R, S,
+            x, dy, out = items[0]
+            call("mrfp_conv_wgrad", ptr(x), ptr(dy), ptr(out), ptr(ws), _lib._DT[dtype], B, H, W, Cphys, C, N, Nphys, R, S,
                  Ho, Wo, stride, pad_h, pad_w, dil, stream())
             return
-        ws = wgrad_workspace(M, N, Q, x0.device, n)
         arr = ctypes.c_void_p * n
         xs, dys, dws = arr(*[ptr(i[0]) for i in items]), arr(*[ptr(i[1]) for i in items]), arr(*[ptr(i[2]) for i in items])
         call("mrfp_conv_wgrad_grouped", xs, dys, dws, n, ptr(ws), _lib._DT[dtype], B, H, W, Cphys, C, N, Nphys, R, S,
              Ho, Wo, stride, pad_h, pad_w, dil, stream())
 
-    if side is not None:
-        main = torch.cuda.current_stream()
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            run()
-        for x, dy, _, _ in items:
-            dy.record_stream(side)
-            x.record_stream(side)
-        _WGRAD_PENDING[0] = True
-    else:
+    if side is None:
         run()
-    WGRAD_GROUP_LAUNCHES.append(len(items))
-    for _, _, _, weight in items:
-        GRAD_DEFERRED.discard(id(weight))
-        notify_grad(weight)
-
-
-def flush_wgrads(sig=None):
-    """Issues the queued weight gradients (of one launch geometry, or all of them in first-queued order)."""
-    keys = [sig] if sig is not None else list(_WG_QUEUE.keys())
-    for k in keys:
-        items = _WG_QUEUE.pop(k, None)
-        if not items:
-            continue
-        _WG_PENDING_BYTES[0] -= sum(i[0].numel() * i[0].element_size() + i[1].numel() * i[1].element_size() for i in items)
-        _issue_wgrads(k, items)
-
-
-def _queue_wgrad(sig, x, dy, sink, weight):
-    if _GROUP_MAX[0] is None:
-        _GROUP_MAX[0] = min(int(_lib.lib().mrfp_conv_wgrad_group_max()), int(_os.environ.get("MRFP_WGRAD_GROUP_MAX", "32")))
-    if not _JOIN_QUEUED[0]:       # when this backward pass ends: flush every queue, then the caller's stream waits for the side stream
-        _JOIN_QUEUED[0] = True
-        torch.autograd.Variable._execution_engine.queue_callback(_join_at_end_of_backward)
-    if _WG_PASS_KEY[0] is None:   # first weight gradient of this pass: pick up the expectation of the passes that started like it
-        _WG_PASS_KEY[0] = sig
-        _WG_EXPECT.clear()
-        _WG_EXPECT.update(_WG_EXPECT_ALL.get(sig, {}))
-        _WG_SEEN.clear()
-    if _WG_MAX_BYTES[0] is None:
-        free, _total = torch.cuda.mem_get_info(x.device)
-        _WG_MAX_BYTES[0] = min(24 << 30, max(1 << 30, free // 4))
-    seen = _WG_SEEN[sig] = _WG_SEEN.get(sig, 0) + 1
-    expect = _WG_EXPECT.get(sig, 0)
-    if expect == 1 and seen == 1 and sig not in _WG_QUEUE:
-        _issue_wgrads(sig, [(x, dy, sink, weight)])       # a geometry of its own: nothing to wait for
         return
-    q = _WG_QUEUE.setdefault(sig, [])
-    q.append((x, dy, sink, weight))
-    GRAD_DEFERRED.add(id(weight))
-    _WG_PENDING_BYTES[0] += x.numel() * x.element_size() + dy.numel() * dy.element_size()
-    if len(q) >= _GROUP_MAX[0] or (expect > 1 and seen % expect == 0):
-        flush_wgrads(sig)
-    elif _WG_PENDING_BYTES[0] > _WG_MAX_BYTES[0]:
-        flush_wgrads()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        run()
+    for x, dy, _ in items:
+        dy.record_stream(side)
+        x.record_stream(side)
+    _WGRADS.stream_pending = True
 
 
-def _in_backward():
-    """True while the autograd engine is executing a graph task on this thread (a forward convolution issued from inside a
-    backward pass -- activation checkpointing, recomputation in a custom backward -- is legitimate and must not be taken for
-    the sign of a dead pass)."""
-    f = getattr(torch._C, "_current_graph_task_id", None)
-    return f is not None and f() != -1
+class _WgradScheduler:
+    """When a weight gradient is launched, on which stream, and who is told (one instance: _WGRADS).
+    How many problems of a geometry one backward pass produces is learnt from the previous pass of the same kind: a geometry that
+    came ONCE is launched at once from then on (nothing to group with -- and the last layers of backward, the stem, would otherwise
+    leave as an exposed tail behind the end of the dgrad chain), a repeated one leaves as soon as its expected count is complete.
+    Passes are told apart by the geometry of their first weight gradient (the head's convolution: input shape, batch, dtype and
+    class count are in it), so two models / two input shapes alternating in one process each keep their own expectation instead of
+    flushing late or early on the other one's counts.  (Grouping is a speed matter only: every flush is a correct launch.)"""
+
+    def __init__(self):
+        self.queues = {}            # launch geometry -> [(x, dy, sink, weight)], in first-queued order
+        # Activations (x, dy) the queues keep alive beyond the point where an immediate launch would have released them, and their
+        # cap.  MRFP_WGRAD_GROUP_GB fixes it; by default it is a quarter of the device memory that is free when the first gradient
+        # is queued, at most 24 GB (the bench step on a 288 GB part: 24; a large-activation configuration -- configs[4] -- on a
+        # fuller device gets less and flushes earlier instead of raising the peak).
+        self.pending_bytes = 0
+        self.max_bytes = int(float(_os.environ["MRFP_WGRAD_GROUP_GB"]) * (1 << 30)) if "MRFP_WGRAD_GROUP_GB" in _os.environ else None
+        self.group_max = None       # problems per launch: min(mrfp_conv_wgrad_group_max(), MRFP_WGRAD_GROUP_MAX), taken at the first submit
+        self.expect_all = {}        # pass key -> {launch geometry -> problems} of the last complete pass that started with it (64 kinds)
+        self._reset_pass()
+        self.callback_queued = False    # end_of_backward is queued on the autograd engine for the running pass
+        self.streams = {}           # device index -> side stream
+        self.stream_pending = False     # a side stream holds launches that the current stream has not waited for
+
+    def _reset_pass(self, key=None):
+        """The running pass: its key (the geometry of its first weight gradient; None: no pass is running), the problems seen per
+        geometry so far, and those the last complete pass of this kind produced."""
+        self.pass_key, self.seen, self.expect = key, {}, dict(self.expect_all.get(key, ()))
+
+    def stream(self, device):
+        """The side stream weight gradients are computed on (None when disabled or while a hipGraph is being captured)."""
+        if not USE_WGRAD_STREAM[0] or device.type != "cuda" or torch.cuda.is_current_stream_capturing():
+            return None
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        st = self.streams.get(key)
+        if st is None:
+            st = self.streams[key] = torch.cuda.Stream(device=device)
+        return st
+
+    def ensure_callback(self):
+        """From inside a backward node: when this backward pass ends, every queue is flushed, then the caller's stream waits for
+        the side stream."""
+        if not self.callback_queued:
+            self.callback_queued = True
+            torch.autograd.Variable._execution_engine.queue_callback(self.end_of_backward)
+
+    def submit(self, sig, x, dy, sink, weight):
+        """Queues one weight gradient (from inside a backward node); launches what the rules above say is due."""
+        if self.group_max is None:
+            self.group_max = min(int(_lib.lib().mrfp_conv_wgrad_group_max()), int(_os.environ.get("MRFP_WGRAD_GROUP_MAX", "32")))
+        self.ensure_callback()
+        if self.pass_key is None:     # first weight gradient of this pass: pick up the expectation of the passes that started like it
+            self._reset_pass(sig)
+        if self.max_bytes is None:
+            free, _total = torch.cuda.mem_get_info(x.device)
+            self.max_bytes = min(24 << 30, max(1 << 30, free // 4))
+        seen = self.seen[sig] = self.seen.get(sig, 0) + 1
+        expect = self.expect.get(sig, 0)
+        if expect == 1 and seen == 1 and sig not in self.queues:
+            self.issue(sig, [(x, dy, sink, weight)])       # a geometry of its own: nothing to wait for
+            return
+        q = self.queues.setdefault(sig, [])
+        q.append((x, dy, sink, weight))
+        GRAD_DEFERRED.add(id(weight))
+        self.pending_bytes += x.numel() * x.element_size() + dy.numel() * dy.element_size()
+        if len(q) >= self.group_max or (expect > 1 and seen % expect == 0):
+            self.flush(sig)
+        elif self.pending_bytes > self.max_bytes:
+            self.flush()
+
+    def flush(self, sig=None):
+        """Issues the queued weight gradients (of one launch geometry, or all of them in first-queued order)."""
+        for k in [sig] if sig is not None else list(self.queues):
+            items = self.queues.pop(k, None)
+            if items:
+                self.pending_bytes -= sum(x.numel() * x.element_size() + dy.numel() * dy.element_size() for x, dy, _, _ in items)
+                self.issue(k, items)
+
+    def issue(self, sig, items):
+        """One launch for `items` (same geometry) on the side stream (or the current one); their weights are reported written."""
+        if not _DEBUG_SKIP_WGRAD:
+            _launch_wgrads(sig, [i[:3] for i in items], self.stream(items[0][0].device))
+            WGRAD_GROUP_LAUNCHES.append(len(items))
+        for _, _, _, weight in items:
+            GRAD_DEFERRED.discard(id(weight))
+            notify_grad(weight)
+
+    def end_of_backward(self):
+        self.callback_queued = False
+        self.flush()
+        # what this pass produced is what the next pass OF THE SAME KIND is expected to produce
+        if self.pass_key is not None:
+            if len(self.expect_all) >= 64 and self.pass_key not in self.expect_all:
+                self.expect_all.pop(next(iter(self.expect_all)))
+            self.expect_all[self.pass_key] = self.seen
+        self._reset_pass()
+        self.join()
+
+    def drop_stale(self, reason="a forward convolution found the end-of-backward callback of an earlier pass still pending"):
+        """The last backward pass died with an exception before the engine ran its callbacks (the harness calls this from the
+        `finally` of its forward/backward, conv2d() when it is called OUTSIDE any backward pass with the callback still marked as
+        queued).  Its queued weight gradients are forgotten -- their step is lost anyway -- so that the next backward registers its
+        own callback; dropping a non-empty queue is reported, never silent."""
+        dropped = sum(len(v) for v in self.queues.values())
+        self.callback_queued = False
+        self.queues.clear()
+        self.pending_bytes = 0
+        self._reset_pass()
+        GRAD_DEFERRED.clear()
+        if dropped:
+            warnings.warn("mrfp_amd.conv: %d queued weight gradients of a backward pass that did not finish were dropped (%s)"
+                          % (dropped, reason), RuntimeWarning, stacklevel=3)
+
+    def join(self, stream=None):
+        """Makes `stream` (default: the current one) wait for every weight gradient issued so far."""
+        if not self.stream_pending:
+            return
+        tgt = stream if stream is not None else torch.cuda.current_stream()
+        for st in self.streams.values():
+            tgt.wait_stream(st)
+        if stream is None:
+            self.stream_pending = False
 
 
-def _drop_stale_backward_state(reason="a forward convolution found the end-of-backward callback of an earlier pass still pending"):
-    """The last backward pass died with an exception before the engine ran its callbacks (the harness calls this from the
-    `finally` of its forward/backward, conv2d() when it is called OUTSIDE any backward pass with the callback still marked as
-    queued).  Its queued weight gradients are forgotten -- their step is lost anyway -- so that the next backward registers its
-    own callback; dropping a non-empty queue is reported, never silent."""
-    dropped = sum(len(v) for v in _WG_QUEUE.values())
-    _JOIN_QUEUED[0] = False
-    _WG_QUEUE.clear()
-    _WG_SEEN.clear()
-    _WG_EXPECT.clear()
-    _WG_PASS_KEY[0] = None
-    _WG_PENDING_BYTES[0] = 0
-    GRAD_DEFERRED.clear()
-    if dropped:
-        import warnings
-        warnings.warn("mrfp_amd.conv: %d queued weight gradients of a backward pass that did not finish were dropped (%s)"
-                      % (dropped, reason), RuntimeWarning, stacklevel=3)
+_WGRADS = _WgradScheduler()
+wgrad_stream, flush_wgrads, join_wgrad_stream = _WGRADS.stream, _WGRADS.flush, _WGRADS.join
 
 
 def backward_failed():
     """To be called when a backward pass raised (harness.Trainer does, from its `finally`): clears the deferred weight-gradient
     state at once instead of leaving it for the next forward convolution to find."""
-    if _JOIN_QUEUED[0] or _WG_QUEUE:
-        _drop_stale_backward_state("the backward pass raised")
+    if _WGRADS.callback_queued or _WGRADS.queues:
+        _WGRADS.drop_stale("the backward pass raised")
 
 
 def wgrad_boundary(t):
@@ -750,36 +742,19 @@ class _Conv2d(torch.autograd.Function):
                 call("mrfp_conv_fwd", ptr(dy), ptr(pk.wd), None, ptr(dx), dt(dy), B, Ho, Wo, Nphys, Cphys, Cphys, R, S, H, W,
                      1, dil * (R - 1) - pad_h, dil * (S - 1) - pad_w, dil, stride, ptr(dskip), None, stream())
         if ctx.needs_input_grad[1]:
-            M, Q = B * Ho * Wo, R * S * Cphys
+            sig = (x.dtype, B, H, W, Cphys, C, N, Nphys, R, S, Ho, Wo, stride, pad_h, pad_w, dil)
             sink = grad_sink(weight)      # the parameter's slot in the flat gradient arena, when the harness owns it
-            side = wgrad_stream(x.device) if sink is not None else None
+            side = _WGRADS.stream(x.device) if sink is not None else None
+            # one of three routes: queue it with the scheduler / launch it now on the side stream / ... on the current stream
             if sink is not None and GROUP_WGRAD[0] and L_single(B, H, W, Cphys, Ho, Wo, Nphys, x.element_size()):
-                _queue_wgrad((x.dtype, B, H, W, Cphys, C, N, Nphys, R, S, Ho, Wo, stride, pad_h, pad_w, dil), x, dy, sink, weight)
-                dw = None
+                _WGRADS.submit(sig, x, dy, sink, weight)
             elif side is not None:
-                # The weight gradient feeds nothing but the optimizer: it runs on a second HIP stream, concurrently with
-                # the dgrad chain of the main stream (its workgroups fill the tails / small-kernel gaps of that chain).
-                # Ordering: side waits for dy (an event on the main stream); the consumers of the arena (optimizer step,
-                # gradient all-reduce) wait for the side stream (harness.Trainer / GradSync, join_wgrad_stream()).
-                main = torch.cuda.current_stream()
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    ws = wgrad_workspace(M, N, Q, x.device)
-                    call("mrfp_conv_wgrad", ptr(x), ptr(dy), ptr(sink), ptr(ws), dt(x), B, H, W, Cphys, C, N, Nphys, R, S,
-                         Ho, Wo, stride, pad_h, pad_w, dil, stream())
-                dy.record_stream(side)
-                x.record_stream(side)
-                _WGRAD_PENDING[0] = True
-                if not _JOIN_QUEUED[0]:       # when this backward pass ends, the caller's stream waits for the side stream
-                    _JOIN_QUEUED[0] = True
-                    torch.autograd.Variable._execution_engine.queue_callback(_join_at_end_of_backward)
+                _WGRADS.ensure_callback()
+                _launch_wgrads(sig, [(x, dy, sink)], side)
                 notify_grad(weight)
-                dw = None
             else:
-                ws = wgrad_workspace(M, N, Q, x.device)
                 dw = sink if sink is not None else torch.empty((N, C, R, S), dtype=torch.float32, device=x.device)
-                call("mrfp_conv_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(ws), dt(x), B, H, W, Cphys, C, N, Nphys, R, S, Ho, Wo,
-                     stride, pad_h, pad_w, dil, stream())
+                _launch_wgrads(sig, [(x, dy, dw)], None)
                 if sink is not None:
                     notify_grad(weight)
                     dw = None
@@ -836,11 +811,8 @@ class _SharedConv1x1Pair(torch.autograd.Function):
                      None, None, stream())
             dxs.append(dx)
             if ctx.needs_input_grad[2]:
-                M = B * H * W
-                ws = wgrad_workspace(M, N, C, x.device)
                 dw = torch.empty((N, C, 1, 1), dtype=torch.float32, device=x.device)
-                call("mrfp_conv_wgrad", ptr(x), ptr(dy), ptr(dw), ptr(ws), dt(x), B, H, W, C, C, N, Nphys, 1, 1, H, W, 1, 0, 0, 1,
-                     stream())
+                _launch_wgrads((x.dtype, B, H, W, C, C, N, Nphys, 1, 1, H, W, 1, 0, 0, 1), [(x, dy, dw)], None)
                 dws.append(dw)
         if bias is not None and ctx.needs_input_grad[3] and dy2 is not None:
             db = channel_sums(_chk(dy2, "dy"), N).to(bias.dtype)
@@ -916,8 +888,8 @@ def conv2d(x, weight, bias, stride, padding, dilation, phys_out: Optional[int] =
             raise _lib.MrfpHipError("mrfp_conv_stats_layout failed (%d): %s" % (rc, L.mrfp_last_error().decode()))
         nblk, rb, rows, first, cnt = lay
         stats = torch.empty(rows * 2 * Nphys, dtype=torch.float32, device=x.device)
-    if _JOIN_QUEUED[0] and not _in_backward():
-        _drop_stale_backward_state()
+    if _WGRADS.callback_queued and not _in_backward():
+        _WGRADS.drop_stale()
     out = _Conv2d.apply(x, weight, bias, st, ph, pw, dl, Nphys, want_skip, stats, wtab)
     y, skip = out if want_skip else (out, None)
     if skip is not None:

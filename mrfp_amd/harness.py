@@ -183,7 +183,7 @@ class GradSync:
 
     def _make_autograd_hook(self, i, deferred):
         """autograd's post-accumulate hook: fires when the parameter's backward node has RUN -- also when that node returned None
-        because its kernel writes the arena directly, and also when it only QUEUED the weight-gradient launch (conv._queue_wgrad:
+        because its kernel writes the arena directly, and also when it only QUEUED the weight-gradient launch (conv._WGRADS.submit:
         grouped, deferred weight gradients).  A queued gradient has not been written: it is reported by ops.notify_grad when its
         launch has been issued, and ignored here."""
         inner = self._make_hook(i)

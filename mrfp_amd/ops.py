@@ -26,7 +26,7 @@ CL = torch.channels_last
 # (harness.FlatArena sets `_mrfp_direct`), backward kernels write the parameter gradient straight into that view
 # (no temporary, no autograd accumulate kernel) and report it through GRAD_NOTIFY (data-parallel bucket counting).
 GRAD_NOTIFY = [None]
-GRAD_DEFERRED = set()      # id(param) of weights whose gradient launch is queued (conv._queue_wgrad): not written yet -- autograd's
+GRAD_DEFERRED = set()      # id(param) of weights whose gradient launch is queued (conv._WGRADS.submit): not written yet -- autograd's
                            # post-accumulate hook fires for them all the same and must not count them as arrived (harness.GradSync)
 
 
@@ -1621,8 +1621,9 @@ def _saved_tensor_hooks_active():
 
 
 def _inside_autograd_engine():
-    """True while the autograd engine is executing a graph task on this thread (conv._in_backward, repeated here: ops does not
-    import conv)."""
+    """True while the autograd engine is executing a graph task on this thread (conv._in_backward is this function: a forward
+    convolution issued from inside a backward pass -- activation checkpointing, recomputation in a custom backward -- is legitimate
+    and must not be taken for the sign of a dead pass)."""
     f = getattr(torch._C, "_current_graph_task_id", None)
     return f is not None and f() != -1
 

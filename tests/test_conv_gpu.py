@@ -737,3 +737,48 @@ def test_batched_weight_pack_equals_the_per_layer_pack(dtype):
     for (case, (_, pk, _), (wf, wd)) in zip(cases, todo, ref):
         assert torch.equal(pk.wf, wf), ("wf", case)
         assert torch.equal(pk.wd, wd), ("wd", case)
+
+
+@pytest.mark.parametrize("case", [(torch.bfloat16, 64, 3, 1, 1), (torch.float32, 128, 1, 2, 0)], ids=["3x3_bf16", "1x1s2_f32"])
+def test_the_three_weight_gradient_routes_launch_the_same_problem(case):
+    """_Conv2d.backward takes one of three routes with its weight gradient: queue it with the scheduler (a sink and GROUP_WGRAD),
+    launch it now on the side stream (a sink, grouping off, USE_WGRAD_STREAM), launch it now on the current stream (both off -- or a
+    weight without a sink, whose gradient goes back through autograd).  With one problem per geometry each of the four ends in a
+    single mrfp_conv_wgrad launch of the same arguments: dW is bit-identical, dx too; only the scheduler records a launch
+    (WGRAD_GROUP_LAUNCHES == [1]), and no route leaves a queue, a deferred id or the callback flag behind."""
+    from mrfp_amd import conv
+    dtype, Cout, k, st, pad = case
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(2, 64, 16, 16, generator=g).to(DEV, dtype).contiguous(memory_format=torch.channels_last)
+    w0 = torch.randn(Cout, 64, k, k, generator=g) * 0.05
+    Ho = (16 + 2 * pad - k) // st + 1
+    gy = torch.randn(2, Cout, Ho, Ho, generator=g).to(DEV, dtype).contiguous(memory_format=torch.channels_last)
+
+    def run(group, side, sink):
+        conv.GROUP_WGRAD[0], conv.USE_WGRAD_STREAM[0] = group, side
+        conv.WGRAD_GROUP_LAUNCHES.clear()
+        w = w0.to(DEV).requires_grad_(True)
+        if sink:
+            w._mrfp_direct = True
+            w.grad = torch.full_like(w, float("nan"))         # (the launch writes every element)
+        xd = x.clone().requires_grad_(True)
+        conv.conv2d(xd, w, None, st, pad, 1).backward(gy)
+        conv.join_wgrad_stream()
+        torch.cuda.synchronize()
+        assert not conv._WGRADS.queues and not conv.GRAD_DEFERRED and not conv._WGRADS.callback_queued
+        assert w.grad.dtype == torch.float32 and bool(torch.isfinite(w.grad).all())
+        return w.grad.clone(), xd.grad.clone(), list(conv.WGRAD_GROUP_LAUNCHES)
+
+    was = conv.GROUP_WGRAD[0], conv.USE_WGRAD_STREAM[0]
+    try:
+        got = [run(True, True, True), run(False, True, True), run(False, False, True), run(True, True, False)]
+    finally:
+        conv.GROUP_WGRAD[0], conv.USE_WGRAD_STREAM[0] = was
+    assert [r[2] for r in got] == [[1], [], [], []]
+    for dw, dx, _ in got[1:]:
+        assert torch.equal(dw, got[0][0]) and torch.equal(dx, got[0][1])
+    # and it is the weight gradient (x and dy are already rounded: only the accumulation order differs; the bounds of
+    # test_conv_fwd_dgrad_wgrad)
+    wc = w0.clone().requires_grad_(True)
+    F.conv2d(x.float().cpu(), wc, None, st, pad).backward(gy.float().cpu())
+    assert relerr(got[0][0], wc.grad) < (1e-5 if dtype == torch.float32 else 2e-2)

@@ -325,7 +325,7 @@ def test_eight_rank_launch_rehearsal_on_cpu(tmp_path, capfd):
 
 def _worker_deferred(outdir):
     """One rank, MRFP_FORCE_SYNC=1 (the bucket machinery runs at world size 1): a backward node that only QUEUES its weight
-    gradient (what conv._queue_wgrad does for the grouped launches) must hold its bucket back until ops.notify_grad reports
+    gradient (what conv._WGRADS.submit does for the grouped launches) must hold its bucket back until ops.notify_grad reports
     the launch -- autograd's post-accumulate hook fires for the parameter as soon as the node has run."""
     sys.path.insert(0, ROOT)
     os.environ["MRFP_FORCE_SYNC"] = "1"

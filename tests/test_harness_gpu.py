@@ -333,7 +333,7 @@ def test_grouped_deferred_weight_gradients_equal_the_per_layer_launches():
             conv.WGRAD_GROUP_LAUNCHES.clear()
             loss = tr._fwd_bwd(x, y)
             torch.cuda.synchronize()
-            assert not conv._WG_QUEUE and not conv.GRAD_DEFERRED
+            assert not conv._WGRADS.queues and not conv.GRAD_DEFERRED
             grads.append((float(loss), tr.opt.flat_g.clone()))
             groups.append(list(conv.WGRAD_GROUP_LAUNCHES))
     finally:
@@ -355,7 +355,7 @@ def test_grouped_deferred_weight_gradients_equal_the_per_layer_launches():
 
 def test_two_trainers_and_two_input_shapes_interleaved_with_grouping_on():
     """the deferred weight-gradient queues learn how many problems of a geometry a backward pass produces from
-    the previous pass OF THE SAME KIND (conv._WG_EXPECT_ALL, keyed by the pass's first weight-gradient geometry).  Two Trainers
+    the previous pass OF THE SAME KIND (conv._WGRADS.expect_all, keyed by the pass's first weight-gradient geometry).  Two Trainers
     (two models) and two input shapes alternating in one process: every pass must reproduce, bit for bit, the gradients the same
     model / shape gives when it runs alone, leave no queue behind, and -- from its second occurrence on -- issue the same grouped
     launches as when it runs alone (no late or early flush on the other pass's counts)."""
@@ -381,7 +381,7 @@ def test_two_trainers_and_two_input_shapes_interleaved_with_grouping_on():
         conv.WGRAD_GROUP_LAUNCHES.clear()
         loss = tr._fwd_bwd(x, y)
         torch.cuda.synchronize()
-        assert not conv._WG_QUEUE and not conv.GRAD_DEFERRED and not conv._JOIN_QUEUED[0]
+        assert not conv._WGRADS.queues and not conv.GRAD_DEFERRED and not conv._WGRADS.callback_queued
         return float(loss), tr.opt.flat_g.clone(), sorted(conv.WGRAD_GROUP_LAUNCHES)
 
     # alone: each (trainer, shape) twice in a row -- the second pass is the steady state of that kind
@@ -397,7 +397,7 @@ def test_two_trainers_and_two_input_shapes_interleaved_with_grouping_on():
         ref = alone[(ti, si)]
         assert loss == ref[0] and torch.equal(g, ref[1]), (ti, si)
         assert groups == ref[2], (ti, si, groups, ref[2])       # the expectation of this kind of pass was learnt in the `alone` phase
-    assert len(conv._WG_EXPECT_ALL) <= 64
+    assert len(conv._WGRADS.expect_all) <= 64
 
 
 def test_a_backward_pass_that_raises_leaves_no_deferred_state_behind():
@@ -425,11 +425,11 @@ def test_a_backward_pass_that_raises_leaves_no_deferred_state_behind():
     def hook(_g):
         # a legitimate forward convolution from inside backward (activation recomputation) ...
         assert conv._in_backward()
-        q = sum(len(v) for v in conv._WG_QUEUE.values())
+        q = sum(len(v) for v in conv._WGRADS.queues.values())
         with torch.no_grad():
             conv.conv2d(torch.zeros(1, 64, 8, 8, device=DEV).contiguous(memory_format=torch.channels_last),
                         torch.zeros(64, 64, 1, 1, device=DEV), None, 1, 0, 1)
-        assert sum(len(v) for v in conv._WG_QUEUE.values()) == q        # ... did not drop the queues
+        assert sum(len(v) for v in conv._WGRADS.queues.values()) == q        # ... did not drop the queues
         fired.append(q)
         raise Boom("injected")
 
@@ -449,7 +449,7 @@ def test_a_backward_pass_that_raises_leaves_no_deferred_state_behind():
             warnings.simplefilter("always")
             with pytest.raises(Boom):
                 tr._fwd_bwd(x, y)
-        assert fired and not conv._WG_QUEUE and not conv.GRAD_DEFERRED and not conv._JOIN_QUEUED[0]
+        assert fired and not conv._WGRADS.queues and not conv.GRAD_DEFERRED and not conv._WGRADS.callback_queued
         if fired[0]:
             assert any("queued weight gradients" in str(i.message) for i in w)
     finally:
