@@ -435,6 +435,26 @@ int mrfp_u8hwc_to_f32chw(const void* src, float* dst, int64_t H, int64_t W, void
  * image, Convert.c rgb2hsv / hsv2rgb): op 0 brightness, 1 contrast (needs ws: 16 bytes, the L mean is reduced on the device),
  * 2 saturation, 3 hue (shift = uint8(hue_factor * 255), factor unused).  Byte-exact with PIL. */
 int mrfp_jitter_u8(const void* src, void* dst, int64_t npix, int op, float factor, int shift, void* ws, void* stream);
+/* The evaluation input path: label encoding and Mapillary's validation transform.
+ *   mrfp_label_lut_u8: dst[i] = lut[src[i]] over n >= 0 bytes (n == 0 launches nothing); lut: 256 bytes on the device.  Replaces
+ *     the per-class-id masked numpy passes over the label map of main.py:106-112 (encode_segmap, called at :96, :188, :290,
+ *     :383), :561-563 (Synthia) and :742-745 (Mapillary): the table is those passes replayed on arange(256)
+ *     (mrfp_amd/input_pipeline.py::LabelEncoder).  dst == src is allowed, any other overlap is refused; src and dst need no
+ *     alignment (bytes in front of the first 16-byte boundary and behind the last go one by one; pointers that differ modulo
+ *     16 take a byte path).
+ *   mrfp_label_encode_i64: dst_i64[i] = (int64)lut[src_u8[i]], lut == NULL: identity.  The label half of a ToTensor-only
+ *     validation sample (main.py:134-144 and the transform_val of every class but Mapillary; dataloaders.py:118-136 ToTensor)
+ *     with the encoding in the same pass.  src_u8 needs no alignment, dst_i64 that of an int64.
+ *   mrfp_eval_assemble: the assemble step of main.py:775-783 (dataloaders.py:354-394 CenterCropPad, :118-136 ToTensor).
+ *     Operands as mrfp_input_assemble (no flip, no uint8 output), except: the crop origin (x1, y1) may be negative and the crop
+ *     may leave the padded image -- such pixels are 0 in the image and 0 in the label, as Image.crop gives; pixels of the
+ *     ImageOps.expand border take the label `pad_label` (0..255; the image is 0 there); lut != NULL: 256 bytes, applied to
+ *     the label bytes as they are read (pad_label and the zeros are not looked up: the reference encodes before it pads). */
+int mrfp_label_lut_u8(const void* src, void* dst, int64_t n, const void* lut, void* stream);
+int mrfp_label_encode_i64(const void* src_u8, const void* lut, int64_t* dst_i64, int64_t n, void* stream);
+int mrfp_eval_assemble(const void* img, const void* lab, const int32_t* ytab, const int32_t* xtab, int64_t Hs, int64_t Ws,
+                       int64_t Hl, int64_t Wl, int pad_x, int pad_y, int x1, int y1, int64_t Hc, int64_t Wc, int pad_label,
+                       const void* lut, float* out_img, int64_t* out_lab, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Frequency filters of the input pipeline (reference dataloaders.py:24-45 HPF, 59-79 LPF, 47-57 PHOT: np.fft.fftn over the

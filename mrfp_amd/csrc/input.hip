@@ -182,6 +182,126 @@ __global__ __launch_bounds__(256) void jitter_u8_kernel(const uint8_t* __restric
     }
 }
 
+// ---- evaluation input path: label encoding and the validation assemble ------------------------------------------------------
+// The reference rewrites every label map on the host with one masked numpy pass per class id (main.py:106-112 encode_segmap,
+// :561-563 Synthia, :742-745 Mapillary); whatever order those passes run in, the result is a function of the source byte, i.e. a
+// 256-entry table (built on the host by replaying the passes on arange(256): mrfp_amd/input_pipeline.py::LabelEncoder).
+// One lane moves 16 bytes, one workgroup a chunk of kThreads * 16 bytes per step of its walk; the table sits in LDS.
+constexpr int kLutVec = 16;
+constexpr int kLutChunk = kThreads * kLutVec;        // bytes per workgroup and step
+
+__device__ __forceinline__ void load_label_table(uint8_t (&tab)[256], const uint8_t* __restrict__ lut) {
+    tab[threadIdx.x] = lut ? lut[threadIdx.x] : (uint8_t)threadIdx.x;       // kThreads == 256 entries; NULL: identity
+    __syncthreads();
+}
+__device__ __forceinline__ uint32_t lut4(const uint8_t (&tab)[256], uint32_t v) {
+    return (uint32_t)tab[v & 255] | ((uint32_t)tab[(v >> 8) & 255] << 8) | ((uint32_t)tab[(v >> 16) & 255] << 16) |
+           ((uint32_t)tab[v >> 24] << 24);
+}
+
+// dst[i] = lut[src[i]], dst == src allowed (no __restrict__: every lane reads its bytes before it writes them).  `head` bytes in
+// front of the first 16-byte boundary go one per lane (workgroup 0); VEC: src + head and dst + head are both 16-byte aligned and
+// a lane moves one uint4 (the last, partial one byte by byte); !VEC (the two pointers differ modulo 16): the same chunk walk with
+// one byte per lane and access, 16 accesses per step.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void label_lut_u8_kernel(const uint8_t* src, uint8_t* dst, int64_t n, int head,
+                                                                const uint8_t* __restrict__ lut) {
+    __shared__ uint8_t tab[256];
+    load_label_table(tab, lut);
+    if (blockIdx.x == 0 && (int)threadIdx.x < head) dst[threadIdx.x] = tab[src[threadIdx.x]];
+    src += head; dst += head; n -= head;
+    const int64_t nchunks = (n + kLutChunk - 1) / kLutChunk;
+    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        if constexpr (VEC) {
+            const int64_t o = c * kLutChunk + (int64_t)threadIdx.x * kLutVec;
+            if (o + kLutVec <= n) {
+                uint4 v = *reinterpret_cast<const uint4*>(src + o);
+                v.x = lut4(tab, v.x); v.y = lut4(tab, v.y); v.z = lut4(tab, v.z); v.w = lut4(tab, v.w);
+                *reinterpret_cast<uint4*>(dst + o) = v;
+            } else {
+                for (int64_t i = o; i < n; ++i) dst[i] = tab[src[i]];
+            }
+        } else {
+#pragma unroll 4
+            for (int j = 0; j < kLutVec; ++j) {
+                const int64_t i = c * kLutChunk + j * kThreads + threadIdx.x;
+                if (i < n) dst[i] = tab[src[i]];
+            }
+        }
+    }
+}
+
+// dst[i] = (int64)lut[src[i]]: 1 byte read, 8 written.  A lane reads 16 bytes at once (src + head is 16-byte aligned), the
+// looked-up bytes cross the wave through LDS so that every store instruction of a wave writes 64 consecutive int64 (512 bytes).
+__global__ __launch_bounds__(kThreads) void label_encode_i64_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ lut,
+                                                                    int64_t* __restrict__ dst, int64_t n, int head) {
+    __shared__ uint8_t tab[256];
+    __shared__ __attribute__((aligned(16))) uint8_t stage[kLutChunk];
+    load_label_table(tab, lut);
+    if (blockIdx.x == 0 && (int)threadIdx.x < head) dst[threadIdx.x] = (int64_t)tab[src[threadIdx.x]];
+    src += head; dst += head; n -= head;
+    const int64_t nchunks = (n + kLutChunk - 1) / kLutChunk;
+    const int wave0 = ((int)threadIdx.x >> 6) * 64 * kLutVec, lane = (int)threadIdx.x & 63;
+    for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {          // the same trip count for every lane of the workgroup
+        const int64_t base = c * kLutChunk;
+        const int64_t o = base + (int64_t)threadIdx.x * kLutVec;
+        if (o + kLutVec <= n) {
+            uint4 v = *reinterpret_cast<const uint4*>(src + o);
+            v.x = lut4(tab, v.x); v.y = lut4(tab, v.y); v.z = lut4(tab, v.z); v.w = lut4(tab, v.w);
+            *reinterpret_cast<uint4*>(stage + threadIdx.x * kLutVec) = v;
+        } else {
+            for (int64_t i = o; i < n; ++i) stage[i - base] = tab[src[i]];
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int j = 0; j < kLutVec; ++j) {
+            const int e = wave0 + j * 64 + lane;
+            if (base + e < n) dst[base + e] = (int64_t)stage[e];
+        }
+        __syncthreads();                                                  // the next step overwrites the stage
+    }
+}
+
+// The assemble step of the validation transform (main.py:775-783: dataloaders.py:354-394 CenterCropPad, then ToTensor).  As
+// input_assemble_kernel, with: a crop that may leave the padded image (such pixels are 0 in image and label, as Image.crop
+// gives); `pad_label` for the pixels of the ImageOps.expand border; the label bytes looked up in `lut` as they are read.
+__global__ __launch_bounds__(kThreads) void eval_assemble_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ lab,
+                                                                 const int32_t* __restrict__ ytab, const int32_t* __restrict__ xtab,
+                                                                 int Hs, int Ws, int Hl, int Wl, int pad_x, int pad_y, int x1, int y1,
+                                                                 int Hc, int Wc, int pad_label, const uint8_t* __restrict__ lut,
+                                                                 float* __restrict__ out_img, int64_t* __restrict__ out_lab) {
+    __shared__ uint8_t tab[256];
+    load_label_table(tab, lut);
+    const int64_t n = (int64_t)Hc * Wc;
+    const int Wp = Ws + 2 * pad_x, Hp = Hs + 2 * pad_y;                 // the padded image
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
+        const int ox = (int)(i % Wc), oy = (int)(i / Wc);
+        const int qx = x1 + ox, qy = y1 + oy;                           // position in the padded image
+        const int px = qx - pad_x, py = qy - pad_y;                     // position in the scaled image
+        uint8_t r = 0, g = 0, b = 0;
+        int64_t l = 0;                                                  // outside the padded image
+        if (px >= 0 && px < Ws && py >= 0 && py < Hs) {
+            const uint8_t* p = img + ((int64_t)py * Ws + px) * 3;
+            r = p[0]; g = p[1]; b = p[2];
+            const int sy = ytab[py], sx = xtab[px];
+            if (sy >= 0 && sy < Hl && sx >= 0 && sx < Wl) l = tab[lab[(int64_t)sy * Wl + sx]];
+        } else if (qx >= 0 && qx < Wp && qy >= 0 && qy < Hp) {
+            l = pad_label;
+        }
+        out_img[i] = (float)r;
+        out_img[n + i] = (float)g;
+        out_img[2 * n + i] = (float)b;
+        out_lab[i] = l;
+    }
+}
+
+// workgroups of a chunk walk: the cap of the row kernels (common.hpp: lines_per_image, MRFP_ROW_BLOCKS), every workgroup the
+// same number of chunks; at least one, which moves the head bytes
+inline unsigned lut_grid(int64_t nbytes) {
+    const int64_t nchunks = (nbytes + kLutChunk - 1) / kLutChunk;
+    return nchunks > 0 ? (unsigned)lines_per_image(1, nchunks) : 1u;
+}
+
 }  // namespace mrfp
 
 using namespace mrfp;
@@ -265,6 +385,61 @@ int mrfp_u8hwc_to_f32chw(const void* src, float* dst, int64_t H, int64_t W, void
     int64_t blocks = (n + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(u8hwc_to_f32chw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)src, dst, n);
+    MRFP_LAUNCH_CHECK();
+    return 0;
+}
+
+int mrfp_label_lut_u8(const void* src, void* dst, int64_t n, const void* lut, void* stream) {
+    MRFP_CHECK(src && dst && lut, "label_lut_u8: null argument");
+    MRFP_CHECK(n >= 0, "label_lut_u8: negative size %lld", (long long)n);
+    const uint8_t* s = (const uint8_t*)src;
+    uint8_t* d = (uint8_t*)dst;
+    const uintptr_t sa = reinterpret_cast<uintptr_t>(s), da = reinterpret_cast<uintptr_t>(d);
+    MRFP_CHECK(sa == da || (sa < da ? da - sa : sa - da) >= (uint64_t)n, "label_lut_u8: src and dst overlap (in place means dst == src)");
+    if (n == 0) return 0;
+    const bool vec = ((reinterpret_cast<uintptr_t>(s) ^ reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+    int64_t head = vec ? (int64_t)((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15) : 0;
+    if (head > n) head = n;
+    const dim3 grid(lut_grid(n - head));
+    if (vec) hipLaunchKernelGGL(label_lut_u8_kernel<true>, grid, dim3(kThreads), 0, (hipStream_t)stream, s, d, n, (int)head, (const uint8_t*)lut);
+    else hipLaunchKernelGGL(label_lut_u8_kernel<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, s, d, n, (int)head, (const uint8_t*)lut);
+    MRFP_LAUNCH_CHECK();
+    return 0;
+}
+
+int mrfp_label_encode_i64(const void* src_u8, const void* lut, int64_t* dst_i64, int64_t n, void* stream) {
+    MRFP_CHECK(src_u8 && dst_i64, "label_encode_i64: null argument");
+    MRFP_CHECK(n >= 0, "label_encode_i64: negative size %lld", (long long)n);
+    MRFP_CHECK((reinterpret_cast<uintptr_t>(dst_i64) & 7) == 0, "label_encode_i64: dst_i64 is not 8-byte aligned");
+    if (n == 0) return 0;
+    int64_t head = (int64_t)((16 - (reinterpret_cast<uintptr_t>(src_u8) & 15)) & 15);
+    if (head > n) head = n;
+    hipLaunchKernelGGL(label_encode_i64_kernel, dim3(lut_grid(n - head)), dim3(kThreads), 0, (hipStream_t)stream, (const uint8_t*)src_u8,
+                       (const uint8_t*)lut, dst_i64, n, (int)head);
+    MRFP_LAUNCH_CHECK();
+    return 0;
+}
+
+int mrfp_eval_assemble(const void* img, const void* lab, const int32_t* ytab, const int32_t* xtab, int64_t Hs, int64_t Ws, int64_t Hl,
+                       int64_t Wl, int pad_x, int pad_y, int x1, int y1, int64_t Hc, int64_t Wc, int pad_label, const void* lut,
+                       float* out_img, int64_t* out_lab, void* stream) {
+    MRFP_CHECK(img && lab && ytab && xtab && out_img && out_lab, "eval_assemble: null argument");
+    MRFP_CHECK(Hs > 0 && Ws > 0 && Hl > 0 && Wl > 0 && Hc > 0 && Wc > 0 && Hs < 65536 && Ws < 65536 && Hl < 65536 && Wl < 65536 &&
+               Hc < 65536 && Wc < 65536, "eval_assemble: bad sizes");
+    MRFP_CHECK(pad_x >= 0 && pad_y >= 0, "eval_assemble: negative padding (%d, %d)", pad_x, pad_y);
+    MRFP_CHECK(pad_label >= 0 && pad_label <= 255, "eval_assemble: pad_label %d is no uint8 value", pad_label);
+    // the kernel's 32-bit positions: the padded extent, the crop's far corner and the crop origin taken back by the padding
+    const int64_t lim = 2147483647ll;
+    MRFP_CHECK(Ws + 2 * (int64_t)pad_x <= lim && Hs + 2 * (int64_t)pad_y <= lim && (int64_t)x1 + Wc <= lim && (int64_t)y1 + Hc <= lim &&
+               (int64_t)x1 - pad_x >= -lim && (int64_t)y1 - pad_y >= -lim,
+               "eval_assemble: the crop [%d,%d)+%lldx%lld or the padding (%d, %d) overflows int32", x1, y1, (long long)Wc, (long long)Hc,
+               pad_x, pad_y);
+    const int64_t n = Hc * Wc;
+    int64_t blocks = (n + kThreads - 1) / kThreads;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(eval_assemble_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, (const uint8_t*)img,
+                       (const uint8_t*)lab, ytab, xtab, (int)Hs, (int)Ws, (int)Hl, (int)Wl, pad_x, pad_y, x1, y1, (int)Hc, (int)Wc, pad_label,
+                       (const uint8_t*)lut, out_img, out_lab);
     MRFP_LAUNCH_CHECK();
     return 0;
 }

@@ -472,6 +472,16 @@ def evaluate(model, batches, num_classes=19, fold=False):
     return h, (metrics.miou_from_hist(h) if h is not None else 0.0), dropped
 
 
+def eval_batches(samples, transform, encoder=None):
+    """(uint8 [H,W,3] image, uint8 [H,W] label map) device pairs -> the (img [1,3,h,w] float32, label [1,h,w] int64) batches that
+    evaluate / evaluate_tta consume, one sample at a time as the reference's batch-1 loop (main.py:887-913) sees them.
+    transform: input_pipeline.EvalTransform() or ResizeHeightCenterCropPad(eval_size); encoder: a LabelEncoder or None.
+    evaluate(model, eval_batches(samples, EvalTransform(), label_encoder("CityscapesSegmentation"))) is that loop."""
+    for img_u8, lab_u8 in samples:
+        img, lab = transform(img_u8, lab_u8, encoder)
+        yield img.unsqueeze(0), lab.unsqueeze(0)
+
+
 # ------------------------------------------------------------------------------------------
 # multi-scale / flipped / sliding-window evaluation (build-defined: the reference scores one forward per image)
 # ------------------------------------------------------------------------------------------

@@ -420,3 +420,197 @@ def phot(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
     call("mrfp_phot", ptr(x), ptr(out), ptr(ws), ptr(twH), ptr(twW), B, H, W, stream())
     return out
+
+
+# ---- evaluation input path: label encoding, ToTensor-only validation, Mapillary's validation transform ----------------------
+# Quirks of the reference that are kept as they are (DESIGN.md section 8 has the same list for users):
+#   * encode_segmap rewrites the map in place, class id by class id: ids named in neither list stay what they are (Cityscapes
+#     ids >= 34), and the -1 of the void lists never matches a uint8;
+#   * BDD100kSegmentation defines encode_segmap but never calls it (its label files hold train ids): its table is the identity;
+#   * Synthia starts from an all-255 map, Mapillary from a copy: unmapped ids are 255 there and unchanged here (ids >= 66);
+#   * CenterCropPad pads the FULL deficit on both sides, takes its crop origin from the width before padding (a narrow image is
+#     not centred, and the crop leaves the padded image on the left), and main.py:779 keeps its default ignore_index = 0:
+#     padded label pixels are class 0 (road), not 255.
+class LabelEncoder:
+    """A label encoding of the reference as one 256-entry table, applied on the device (csrc/input.hip: label_lut_u8,
+    label_encode_i64).  The reference rewrites the uint8 label map with one masked numpy pass per class id; the table is what
+    those passes, replayed in the reference's statement order on arange(256), leave behind -- so the quirks of the in-place
+    chain come out by construction instead of being restated.
+      LabelEncoder.from_lists(void_classes, valid_classes, ignore_index): encode_segmap (main.py:106-112): in place, the voids
+        first, then the valids in list order, valid_classes[i] -> i;
+      LabelEncoder.from_map({id: train_id}, default): the copy-based loops; default None leaves unmapped ids unchanged
+        (Mapillary, main.py:742-745), an int fills them (255 for Synthia, main.py:561-563)."""
+
+    def __init__(self, table):
+        table = np.asarray(table)
+        if table.shape != (256,) or table.min() < 0 or table.max() > 255:
+            raise ValueError("LabelEncoder: a table of 256 values in 0..255 expected")
+        self.table = np.ascontiguousarray(table.astype(np.uint8))
+        self.table.setflags(write=False)
+        self._dev_tables = {}
+
+    @classmethod
+    def from_lists(cls, void_classes, valid_classes, ignore_index: int = 255) -> "LabelEncoder":
+        t = np.arange(256, dtype=np.int64)           # wider than the map so that -1 compares as it does against a uint8: never equal
+        for c in void_classes:
+            t[t == c] = ignore_index
+        for i, c in enumerate(valid_classes):
+            t[t == c] = i
+        return cls(t)
+
+    @classmethod
+    def from_map(cls, class_map: dict, default: Optional[int] = None) -> "LabelEncoder":
+        src = np.arange(256, dtype=np.int64)
+        t = src.copy() if default is None else np.full(256, default, dtype=np.int64)
+        for k, v in class_map.items():
+            t[src == k] = v
+        return cls(t)
+
+    def device_table(self, dev) -> torch.Tensor:
+        return _cached(self._dev_tables, str(dev), lambda: _dev(dev, self.table.copy())[0])
+
+    def _arg(self, name: str, lab_u8: torch.Tensor) -> torch.Tensor:
+        if not (isinstance(lab_u8, torch.Tensor) and lab_u8.is_cuda and lab_u8.dtype == torch.uint8):
+            raise _lib.MrfpHipError("LabelEncoder%s: a uint8 CUDA tensor expected (there is no CPU path)" % name)
+        return lab_u8.contiguous()
+
+    def __call__(self, lab_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 label map of any shape -> the encoded uint8 map (out may be lab_u8 itself: in place)."""
+        lab_u8 = self._arg("", lab_u8)
+        out = _out_slot(out, tuple(lab_u8.shape), torch.uint8, lab_u8.device, "LabelEncoder: out")
+        if lab_u8.numel():                                   # (an empty tensor has no address to hand over)
+            call("mrfp_label_lut_u8", ptr(lab_u8), ptr(out), lab_u8.numel(), ptr(self.device_table(lab_u8.device)), stream())
+        return out
+
+    def to_int64(self, lab_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 label map -> the encoded map as int64 (what ToTensor hands the loss / the histogram), in one pass."""
+        lab_u8 = self._arg(".to_int64", lab_u8)
+        return _to_int64(lab_u8, self.device_table(lab_u8.device), out, "LabelEncoder.to_int64: out")
+
+
+def _to_int64(lab_u8: torch.Tensor, table: Optional[torch.Tensor], out: Optional[torch.Tensor], what: str) -> torch.Tensor:
+    out = _out_slot(out, tuple(lab_u8.shape), torch.int64, lab_u8.device, what)
+    if lab_u8.numel():
+        call("mrfp_label_encode_i64", ptr(lab_u8), ptr(table), ptr(out), lab_u8.numel(), stream())
+    return out
+
+
+# Label ids of the 19 evaluation classes, in train-id order (road, sidewalk, building, wall, fence, pole, traffic light, traffic
+# sign, vegetation, terrain, sky, person, rider, car, truck, bus, train, motorcycle, bicycle), per label set.
+_CITYSCAPES_IDS = (7, 8, 11, 12, 13, 17, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 31, 32, 33)      # Cityscapes labelIds; GTAV shares them
+_SYNTHIA_IDS = (3, 4, 2, 21, 5, 7, 15, 9, 6, 16, 1, 10, 17, 8, 18, 19, 20, 12, 11)               # SYNTHIA-RAND-CITYSCAPES
+_MAPILLARY_IDS = ((13, 24, 41), (2, 15), (17,), (6,), (3,), (45, 47), (48,), (50,), (30,), (29,), (27,), (19,), (20, 21, 22), (55,),
+                  (61,), (54,), (58,), (57,), (52,))                                              # Mapillary Vistas v1.2 (66 ids)
+
+
+def _preset_table(groups, nvoid: Optional[int], default: Optional[int] = None) -> np.ndarray:
+    """ids 0..nvoid-1 that belong to no class -> 255, every other unmapped id `default` (None: unchanged); groups[i] -> i."""
+    t = np.arange(256) if default is None else np.full(256, default)
+    if nvoid:
+        t[:nvoid] = 255
+    for i, g in enumerate(groups):
+        t[list(g) if isinstance(g, tuple) else g] = i
+    return t
+
+
+_PRESETS = {
+    # encode_segmap with the Cityscapes lists (main.py:69-70, 161-162, 257-258): labelIds 0..33; 34 and above are in neither list
+    "Cityscapes": lambda: _preset_table(_CITYSCAPES_IDS, 34),
+    "RainyCityscapes": lambda: _preset_table(_CITYSCAPES_IDS, 34),
+    "Foggy_Cityscapes": lambda: _preset_table(_CITYSCAPES_IDS, 34),
+    "GTAV": lambda: _preset_table(_CITYSCAPES_IDS, 35),                # main.py:358 adds 34 to the voids
+    # main.py:470-471: the *_train_id.png files go to the transform as they are; the encode_segmap of that class (whose valid
+    # list :448 differs, as the comment at :70 says) is never called
+    "BDD100k": lambda: _preset_table((), None),
+    "Synthia": lambda: _preset_table(_SYNTHIA_IDS, None, 255),         # main.py:561-563: an all-255 map, the 19 ids written in
+    "Mapillary": lambda: _preset_table(_MAPILLARY_IDS, 66),            # main.py:635-726, 742-745: 66 ids, a copy for the rest
+}
+
+
+def label_encoder(name: str) -> LabelEncoder:
+    """The label encoding of one dataset class of the reference's main.py, by the reference's class name
+    (CityscapesSegmentation, RainyCityscapesSegmentation, Foggy_CityscapesSegmentation, GTAVSegmentation, BDD100kSegmentation,
+    SynthiaSegmentation, MapillarySegmentation; the `Segmentation` suffix may be left out)."""
+    key = name[:-len("Segmentation")] if name.endswith("Segmentation") else name
+    if key not in _PRESETS:
+        raise KeyError("label_encoder: %r is none of %s" % (name, ", ".join(k + "Segmentation" for k in _PRESETS)))
+    return LabelEncoder(_PRESETS[key]())
+
+
+class EvalTransform:
+    """The ToTensor-only validation sample (main.py:134-144 and the transform_val of every dataset class but Mapillary;
+    dataloaders.py:118-136): uint8 [H,W,3] image and uint8 [H,W] label map on the GPU -> float32 [3,H,W] (0..255, no /255) and
+    int64 [H,W], the label encoded by `encoder` in the same pass (the reference encodes in __getitem__, before the transform)."""
+
+    def __call__(self, img_u8: torch.Tensor, lab_u8: torch.Tensor, encoder: Optional[LabelEncoder] = None,
+                 out_img: Optional[torch.Tensor] = None, out_lab: Optional[torch.Tensor] = None):
+        H, W, img_u8, lab_u8 = _check_pair("EvalTransform", img_u8, lab_u8)
+        dev = img_u8.device
+        out_img = _out_slot(out_img, (3, H, W), torch.float32, dev, "out_img")
+        call("mrfp_u8hwc_to_f32chw", ptr(img_u8), ptr(out_img), H, W, stream())
+        table = encoder.device_table(dev) if encoder is not None else None
+        return out_img, _to_int64(lab_u8, table, out_lab, "out_lab")
+
+
+class ResizeHeightCenterCropPad:
+    """Mapillary's validation composition (main.py:775-783): ResizeHeight(eval_size) -> CenterCropPad(eval_size) -> ToTensor
+    (dataloaders.py:339-394, 118-136) on the device, byte for byte what PIL gives, the reference's behaviour kept as it is:
+      * target_w = int(w / h * eval_size), in floating point as written; BICUBIC for the image, NEAREST for the label;
+      * a narrow result (target_w < eval_size) is padded by the FULL deficit on BOTH sides, and the crop origin
+        int(round((target_w - eval_size) / 2.)) (Python's round-half-even) is taken from the width BEFORE padding: it is then
+        negative, the crop leaves the padded image on the left (those pixels are 0 in image and label, as Image.crop gives) and
+        the content is not centred -- 12 wide at eval_size 16: 2 outside columns, 4 pad columns, the first 10 content columns;
+      * padded label pixels take `ignore_index`, whose default is 0 as CenterCropPad's is; main.py:779 does not override it, so
+        in the reference's Mapillary evaluation the padding counts as class 0 (road).  That is mirrored, not corrected: pass
+        ignore_index=255 for padding the loss and the histogram ignore.
+    Only the columns that survive the crop are resampled (a wide image loses target_w - eval_size columns before the horizontal
+    pass instead of after it).  `encoder`: the table is applied while the assemble kernel reads the label -- raw dataset ids in,
+    train ids out, no intermediate map.  Output: float32 [3,eval_size,eval_size] (0..255) and int64 [eval_size,eval_size]."""
+
+    def __init__(self, eval_size: int, ignore_index: int = 0):
+        self.eval_size, self.ignore_index = int(eval_size), int(ignore_index)
+        if self.eval_size <= 0 or not 0 <= self.ignore_index <= 255:
+            raise ValueError("ResizeHeightCenterCropPad: eval_size > 0 and ignore_index in 0..255 expected")
+        self._dev_tables = {}
+
+    def geometry(self, w: int, h: int):
+        """-> (target_w, pad_x, x1) of a w x h source: the scaled width, ImageOps.expand's border on each side and the crop
+        origin in the padded image (vertically the scaled image has eval_size rows: no padding, origin 0)."""
+        t = self.eval_size
+        tw = int(w / h * t)
+        if tw <= 0:
+            raise _lib.MrfpHipError("ResizeHeightCenterCropPad: a %dx%d image scales to width 0 (PIL refuses it too)" % (w, h))
+        return tw, (t - tw if tw < t else 0), int(round((tw - t) / 2.))
+
+    def _tables(self, dev, H: int, W: int):
+        def build():
+            t = self.eval_size
+            tw, pad_x, x1 = self.geometry(W, H)
+            c0, c1 = (x1, x1 + t) if tw >= t else (0, tw)          # the scaled columns the crop keeps (no padding when tw >= t)
+            bx, kx = _bicubic_tables(W, tw)
+            by, ky = _bicubic_tables(H, t)
+            tabs = _dev(dev, bx[c0:c1], kx[c0:c1], by, ky, _nearest_table(W, tw)[c0:c1], _nearest_table(H, t))
+            return tabs + (kx.shape[1], ky.shape[1], tw, c1 - c0, pad_x, x1 - c0 if tw >= t else x1)
+        return _cached(self._dev_tables, (str(dev), H, W), build)
+
+    def __call__(self, img_u8: torch.Tensor, lab_u8: torch.Tensor, encoder: Optional[LabelEncoder] = None,
+                 out_img: Optional[torch.Tensor] = None, out_lab: Optional[torch.Tensor] = None):
+        H, W, img_u8, lab_u8 = _check_pair("ResizeHeightCenterCropPad", img_u8, lab_u8)
+        dev, t = img_u8.device, self.eval_size
+        bx, kx, by, ky, tx, ty, ksx, ksy, tw, ncol, pad_x, x1 = self._tables(dev, H, W)
+        out_img = _out_slot(out_img, (3, t, t), torch.float32, dev, "out_img")
+        out_lab = _out_slot(out_lab, (t, t), torch.int64, dev, "out_lab")
+        cur = img_u8
+        if tw != W or ncol != W:    # horizontal pass over the kept columns only: their rows of Pillow's tables (at tw == W, where
+            # PIL returns a copy, the coefficients are exactly (0, 1, 0, 0): the pass then copies the kept columns)
+            tmp = torch.empty((H, ncol, 3), dtype=torch.uint8, device=dev)
+            call("mrfp_resample_u8", ptr(cur), ptr(tmp), H, W, H, ncol, 3, ptr(bx), ptr(kx), ksx, 0, 0, stream())
+            cur = tmp
+        if t != H:
+            tmp = torch.empty((t, ncol, 3), dtype=torch.uint8, device=dev)
+            call("mrfp_resample_u8", ptr(cur), ptr(tmp), H, ncol, t, ncol, 3, ptr(by), ptr(ky), ksy, 1, 0, stream())
+            cur = tmp
+        table = encoder.device_table(dev) if encoder is not None else None
+        call("mrfp_eval_assemble", ptr(cur), ptr(lab_u8), ptr(ty), ptr(tx), t, ncol, H, W, pad_x, 0, x1, 0, t, t, self.ignore_index,
+             ptr(table), ptr(out_img), ptr(out_lab), stream())
+        return out_img, out_lab
