@@ -435,6 +435,21 @@ int mrfp_u8hwc_to_f32chw(const void* src, float* dst, int64_t H, int64_t W, void
  * image, Convert.c rgb2hsv / hsv2rgb): op 0 brightness, 1 contrast (needs ws: 16 bytes, the L mean is reduced on the device),
  * 2 saturation, 3 hue (shift = uint8(hue_factor * 255), factor unused).  Byte-exact with PIL. */
 int mrfp_jitter_u8(const void* src, void* dst, int64_t npix, int op, float factor, int shift, void* ws, void* stream);
+/* RandomRotate (dataloaders.py:153-165: img.rotate(angle, BILINEAR), mask.rotate(angle, NEAREST)) for an image / label pair in
+ * one launch, byte-exact with Pillow's affine transform (Geometry.c).  img uint8 [H,W,3], lab uint8 [H,W] -> out_img, out_lab of the
+ * same shapes (no aliasing).  mode 0: the affine path with the matrix (m0..m5) that Image.rotate builds (host side:
+ * mrfp_amd/input_pipeline.py::rotate_plan): image by ImagingGenericTransform (double, bilinear, result truncated), label by
+ * affine_fixed (16.16 fixed point); pixels that map outside are 0 in both (the reference passes no fillcolor).  Refused when a
+ * corner of the image maps to 32768 or beyond (Pillow leaves the fixed-point path there; its double fallback is not built).
+ * mode 1 copy, 2 ROTATE_90, 3 ROTATE_180, 4 ROTATE_270: the exact transposes Image.rotate dispatches to (2 and 4: H == W; the
+ * matrix is ignored).  flip != 0 reads the source mirrored: RandomHorizontalFlip comes before RandomRotate. */
+int mrfp_affine_u8(const void* img, const void* lab, void* out_img, void* out_lab, int64_t H, int64_t W, int mode, int flip,
+                   double m0, double m1, double m2, double m3, double m4, double m5, void* stream);
+/* Normalize (dataloaders.py:95-115) fused into ToTensor (:118-136): src uint8 [H,W,3] -> dst float32 [3,H,W],
+ * v = float32(u8) / float32(255); v = float32(double(v) - mean[c]); v = float32(double(v) / std[c]) -- the precisions numpy
+ * evaluates `img /= 255.0; img -= mean; img /= std` in for a float32 array and tuples of Python floats.  Bit-equal to numpy. */
+int mrfp_u8hwc_to_f32chw_norm(const void* src, float* dst, int64_t H, int64_t W, double mean0, double mean1, double mean2,
+                              double std0, double std1, double std2, void* stream);
 /* The evaluation input path: label encoding and Mapillary's validation transform.
  *   mrfp_label_lut_u8: dst[i] = lut[src[i]] over n >= 0 bytes (n == 0 launches nothing); lut: 256 bytes on the device.  Replaces
  *     the per-class-id masked numpy passes over the label map of main.py:106-112 (encode_segmap, called at :96, :188, :290,

@@ -11,7 +11,10 @@
 //   box_blur3     one pass of ImageFilter.GaussianBlur's box-blur approximation (radius < 1: dataloaders.py:168-177)
 //   assemble      pad (ImageOps.expand: image 0, label ignore_index) + crop + ToTensor: float32 [3,Hc,Wc] in 0..255 and the
 //                 int64 label map, the label fetched through PIL's nearest-neighbour index tables from the ORIGINAL map
+//   affine_u8     Image.rotate of an image / label pair (dataloaders.py:153-165 RandomRotate): PIL's affine transform
+//   u8hwc_to_f32chw_norm   Normalize (dataloaders.py:95-115) fused into the ToTensor store
 #include "common.hpp"
+#include <cmath>
 
 namespace mrfp {
 
@@ -295,6 +298,97 @@ __global__ __launch_bounds__(kThreads) void eval_assemble_kernel(const uint8_t* 
     }
 }
 
+// ---- RandomRotate (dataloaders.py:153-165): Image.rotate(angle, BILINEAR) / mask.rotate(angle, NEAREST) -------------------
+// Pillow (Geometry.c) maps every OUTPUT pixel back into the source with the six-coefficient matrix Image.rotate builds
+// (mrfp_amd/input_pipeline.py::rotate_plan restates it).  The image takes ImagingGenericTransform: affine_transform in double at
+// the pixel centre, bilinear_filter32RGB (columns x, x + 1 and row y clamped, row y + 1 only when it is inside, else v2 = v1;
+// v = a + (b - a) * d in double, first along x, then along y; the result TRUNCATED to 8 bits).  The label takes affine_fixed:
+// 16.16 fixed point, xin = (a2 + a1 y + a0 x) >> 16.  Outside pixels are 0 in both (the reference passes no fillcolor: the
+// label's corners become class 0).  One lane per output pixel, image and label in one launch; `flip` reads the source mirrored
+// (the reference flips before it rotates).  mode 0: the affine path; 1 copy, 2 ROTATE_90, 3 ROTATE_180, 4 ROTATE_270: the exact
+// transposes Image.rotate dispatches to (90 / 270 on square images only).
+struct AffineCoefs {
+    double m[6];        // xin = m0 (x + .5) + m1 (y + .5) + m2, yin = m3 (x + .5) + m4 (y + .5) + m5
+    int32_t a[6];       // the same in 16.16, a2 / a5 at the pixel centre
+};
+
+__device__ __forceinline__ int pil_floor(double v) { return v < 0.0 ? (int)floor(v) : (int)v; }       // Geometry.c FLOOR
+__device__ __forceinline__ int pil_clip(int v, int n) { return v < 0 ? 0 : v < n ? v : n - 1; }          // XCLIP / YCLIP
+__device__ __forceinline__ uint8_t pil_bilinear(const uint8_t* __restrict__ r0, const uint8_t* __restrict__ r1, int x0, int x1, int c,
+                                                double dx, double dy) {
+    const double a = (double)r0[3 * x0 + c], b = (double)r0[3 * x1 + c];
+    const double v1 = a + (b - a) * dx;
+    double v2 = v1;
+    if (r1) {
+        const double e = (double)r1[3 * x0 + c], f = (double)r1[3 * x1 + c];
+        v2 = e + (f - e) * dx;
+    }
+    return (uint8_t)(int)(v1 + (v2 - v1) * dy);                  // (UINT8)v: truncation; 0 <= v <= 255
+}
+
+__global__ __launch_bounds__(kThreads) void affine_u8_kernel(const uint8_t* __restrict__ img, const uint8_t* __restrict__ lab,
+                                                             uint8_t* __restrict__ out_img, uint8_t* __restrict__ out_lab, int H, int W,
+                                                             int mode, int flip, AffineCoefs A) {
+    const int64_t n = (int64_t)H * W;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
+        const int x = (int)(i % W), y = (int)(i / W);
+        uint8_t r = 0, g = 0, b = 0, l = 0;
+        if (mode == 0) {
+            const double xc = (double)x + 0.5, yc = (double)y + 0.5;
+            double xin = A.m[0] * xc + A.m[1] * yc + A.m[2];
+            double yin = A.m[3] * xc + A.m[4] * yc + A.m[5];
+            if (!(xin < 0.0 || xin >= (double)W || yin < 0.0 || yin >= (double)H)) {
+                xin -= 0.5;
+                yin -= 0.5;
+                const int fx = pil_floor(xin), fy = pil_floor(yin);
+                const double dx = xin - (double)fx, dy = yin - (double)fy;
+                int x0 = pil_clip(fx, W), x1 = pil_clip(fx + 1, W);
+                if (flip) { x0 = W - 1 - x0; x1 = W - 1 - x1; }
+                const uint8_t* r0 = img + (int64_t)pil_clip(fy, H) * W * 3;
+                const uint8_t* r1 = (fy + 1 >= 0 && fy + 1 < H) ? img + (int64_t)(fy + 1) * W * 3 : nullptr;
+                r = pil_bilinear(r0, r1, x0, x1, 0, dx, dy);
+                g = pil_bilinear(r0, r1, x0, x1, 1, dx, dy);
+                b = pil_bilinear(r0, r1, x0, x1, 2, dx, dy);
+            }
+            // |every term| < 2^31 by the entry point's corner check; 64-bit sums keep the intermediate exact
+            const int64_t xx = (int64_t)A.a[2] + (int64_t)A.a[1] * y + (int64_t)A.a[0] * x;
+            const int64_t yy = (int64_t)A.a[5] + (int64_t)A.a[4] * y + (int64_t)A.a[3] * x;
+            const int64_t sx = xx >> 16, sy = yy >> 16;          // arithmetic shifts
+            if (sx >= 0 && sx < W && sy >= 0 && sy < H) l = lab[sy * W + (flip ? W - 1 - sx : sx)];
+        } else {
+            int sx, sy;                                          // Geometry.c ImagingRotate90 / 180 / 270 read backwards
+            if (mode == 1) { sx = x; sy = y; }
+            else if (mode == 2) { sx = W - 1 - y; sy = x; }
+            else if (mode == 3) { sx = W - 1 - x; sy = H - 1 - y; }
+            else { sx = y; sy = H - 1 - x; }
+            if (flip) sx = W - 1 - sx;
+            const uint8_t* p = img + ((int64_t)sy * W + sx) * 3;
+            r = p[0]; g = p[1]; b = p[2];
+            l = lab[(int64_t)sy * W + sx];
+        }
+        out_img[3 * i] = r; out_img[3 * i + 1] = g; out_img[3 * i + 2] = b;
+        out_lab[i] = l;
+    }
+}
+
+// Normalize (dataloaders.py:95-115) fused into the ToTensor store.  numpy evaluates `img /= 255.0` in float32 (a Python scalar
+// does not widen the array) and `img -= mean`, `img /= std` -- mean and std are tuples, i.e. float64 arrays -- in float64, each
+// rounded back to float32 when it is written into the float32 array.
+__global__ __launch_bounds__(kThreads) void u8hwc_to_f32chw_norm_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
+                                                                        int64_t npix, double m0, double m1, double m2, double s0,
+                                                                        double s1, double s2) {
+    const double mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < npix; i += (int64_t)gridDim.x * kThreads) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float v = (float)src[3 * i + c] / 255.0f;
+            v = (float)((double)v - mean[c]);
+            v = (float)((double)v / sd[c]);
+            dst[c * npix + i] = v;
+        }
+    }
+}
+
 // workgroups of a chunk walk: the cap of the row kernels (common.hpp: lines_per_image, MRFP_ROW_BLOCKS), every workgroup the
 // same number of chunks; at least one, which moves the head bytes
 inline unsigned lut_grid(int64_t nbytes) {
@@ -440,6 +534,57 @@ int mrfp_eval_assemble(const void* img, const void* lab, const int32_t* ytab, co
     hipLaunchKernelGGL(eval_assemble_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, (const uint8_t*)img,
                        (const uint8_t*)lab, ytab, xtab, (int)Hs, (int)Ws, (int)Hl, (int)Wl, pad_x, pad_y, x1, y1, (int)Hc, (int)Wc, pad_label,
                        (const uint8_t*)lut, out_img, out_lab);
+    MRFP_LAUNCH_CHECK();
+    return 0;
+}
+
+int mrfp_affine_u8(const void* img, const void* lab, void* out_img, void* out_lab, int64_t H, int64_t W, int mode, int flip,
+                   double m0, double m1, double m2, double m3, double m4, double m5, void* stream) {
+    MRFP_CHECK(img && lab && out_img && out_lab && img != out_img && lab != out_lab, "affine_u8: null or aliased argument");
+    MRFP_CHECK(H > 0 && W > 0 && H < 65536 && W < 65536, "affine_u8: bad sizes %lldx%lld", (long long)H, (long long)W);
+    MRFP_CHECK(mode >= 0 && mode <= 4, "affine_u8: mode %d (0 affine, 1 copy, 2 / 3 / 4 the 90 / 180 / 270 degree transposes)", mode);
+    MRFP_CHECK(!(mode == 2 || mode == 4) || H == W, "affine_u8: the 90 / 270 degree transposes keep the size of square images only (%lldx%lld)",
+               (long long)H, (long long)W);
+    AffineCoefs A{};
+    if (mode == 0) {
+        const double m[6] = {m0, m1, m2, m3, m4, m5};
+        // Geometry.c ImagingTransformAffine: the fixed-point path holds while all four corners stay below 32768
+        const double w = (double)W, h = (double)H;
+        const double cx[4] = {0.0, w, 0.0, w}, cy[4] = {0.0, h, h, 0.0};
+        for (int k = 0; k < 4; ++k) {
+            const double px = cx[k] * m[0] + cy[k] * m[1] + m[2], py = cx[k] * m[3] + cy[k] * m[4] + m[5];
+            MRFP_CHECK(std::isfinite(px) && std::isfinite(py) && fabs(px) < 32768.0 && fabs(py) < 32768.0,
+                       "affine_u8: a corner of the %lldx%lld image maps to (%g, %g): outside the 16.16 fixed-point range (< 32768)",
+                       (long long)W, (long long)H, px, py);
+        }
+        const double c[6] = {m[0], m[1], m[2] + m[0] * 0.5 + m[1] * 0.5, m[3], m[4], m[5] + m[3] * 0.5 + m[4] * 0.5};
+        for (int k = 0; k < 6; ++k) {
+            const double f = floor(c[k] * 65536.0 + 0.5);        // FIX(v): FLOOR(v * 65536 + 0.5)
+            MRFP_CHECK(fabs(f) < 2147483648.0, "affine_u8: coefficient %g does not fit 16.16 fixed point", c[k]);
+            A.m[k] = m[k];
+            A.a[k] = (int32_t)f;
+        }
+    }
+    const int64_t n = H * W;
+    int64_t blocks = (n + kThreads - 1) / kThreads;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(affine_u8_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, (const uint8_t*)img,
+                       (const uint8_t*)lab, (uint8_t*)out_img, (uint8_t*)out_lab, (int)H, (int)W, mode, flip != 0, A);
+    MRFP_LAUNCH_CHECK();
+    return 0;
+}
+
+int mrfp_u8hwc_to_f32chw_norm(const void* src, float* dst, int64_t H, int64_t W, double mean0, double mean1, double mean2,
+                              double std0, double std1, double std2, void* stream) {
+    MRFP_CHECK(src && dst && H > 0 && W > 0, "u8hwc_to_f32chw_norm: bad arguments");
+    MRFP_CHECK(std::isfinite(mean0) && std::isfinite(mean1) && std::isfinite(mean2) && std::isfinite(std0) && std::isfinite(std1) &&
+               std::isfinite(std2) && std0 != 0.0 && std1 != 0.0 && std2 != 0.0,
+               "u8hwc_to_f32chw_norm: finite means and finite non-zero standard deviations expected");
+    const int64_t n = H * W;
+    int64_t blocks = (n + kThreads - 1) / kThreads;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(u8hwc_to_f32chw_norm_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, (hipStream_t)stream, (const uint8_t*)src, dst, n,
+                       mean0, mean1, mean2, std0, std1, std2);
     MRFP_LAUNCH_CHECK();
     return 0;
 }

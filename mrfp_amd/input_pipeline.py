@@ -4,6 +4,9 @@ sets) on the GPU, bit-exact with their PIL calls, and its frequency filters HPF 
 ResizeTransform (main.py:319-330, 499-507, 592-603) and CropTransform (main.py:764-773) reuse the kernels below: Pillow's BILINEAR
 tables for the resampler, the assemble kernel with no padding, and the same flip, jitter and blur steps as TrainTransform.
 hpf / lpf / phot (csrc/freq.hip) take the ToTensor layout float32 [3,H,W] or [B,3,H,W].
+rotate / contrast, ScaleCropTransform, FixScaleCropTransform and CropTransform.p2 are the classes main.py keeps commented or never
+composes (RandomRotate, RandomScaleCrop, RandomCrop_p2, FixScaleCrop, Contrast, Normalize): Image.rotate is csrc/input.hip's
+affine_u8, Normalize is fused into the ToTensor store, the rest reuses the kernels below.
 
 Reference: main.py:409-419 `transform_tr` = RandomHorizontalFlip -> ColorJitter -> RandomSizeAndCrop(crop_size,
 crop_nopad=False, ignore_index=255) -> Resize(crop_size) -> RandomGaussianBlur -> ToTensor (dataloaders.py).  This module
@@ -338,6 +341,12 @@ class CropTransform:
         self.base_size, self.crop_size = int(base_size), int(crop_size)
         self._dev_tables = {}
 
+    @classmethod
+    def p2(cls, crop_w: int, crop_h: int) -> "CropTransform":
+        """The same composition around RandomCrop_p2(crop_sizew, crop_sizeh) (dataloaders.py:236-255): RandomCrop_p with the
+        width named first -- x0 = randint(0, w - crop_w), then y0 = randint(0, h - crop_h).  Output [3,crop_h,crop_w]."""
+        return cls(crop_h, crop_w)
+
     def draw(self, w: int, h: int, rng=_random, np_rng=np.random) -> Draw:
         """python's `random`: flip, jitter gate, randint x0, randint y0, blur gate (+ radius); numpy's stream as
         ColorJitter.get_params when its gate fires."""
@@ -366,6 +375,263 @@ class CropTransform:
         cur = _resample(cur, H, W, H, W, (bx, kx, kx.shape[1]), None, d.flip)
         return _assemble(cur, lab_u8, ty, tx, H, W, Draw(d.flip, d.jitter, (W, H), (0, 0), (x0, y0), d.blur), self.base_size,
                          self.crop_size, 255, out_img, out_lab)
+
+
+# ---- RandomRotate, RandomScaleCrop, FixScaleCrop, Contrast, Normalize (dataloaders.py:83-115, 153-165, 180-214, 439-465) -------
+# Quirks of the reference that are kept as they are:
+#   * RandomRotate passes no fillcolor: the corners a rotation uncovers are 0 in the image AND in the label -- class 0 (road),
+#     not the ignore index;
+#   * RandomScaleCrop pads on the right and at the bottom only (the content stays in the top-left corner), and only when
+#     short_size < crop_size; the label padding is `fill`, whose default is 0;
+#   * the reference never puts these classes into one Compose: the ORDER of ScaleCropTransform is this build's (the classic
+#     DeepLab train composition dataloaders.py descends from), every step equals its class.
+ROT_AFFINE, ROT_COPY, ROT_90, ROT_180, ROT_270 = 0, 1, 2, 3, 4        # the `mode` of mrfp_affine_u8
+
+
+def rotate_plan(w: int, h: int, degrees: float):
+    """Image.rotate(degrees) of a w x h image without expand / center / translate -> (mode, (m0..m5)): Pillow's dispatch to a copy
+    or an exact transpose, else the matrix of its affine transform, with the same IEEE operations in the same order
+    (Image.py: angle % 360.0, -math.radians, cos / sin rounded to 15 places, the centre (w / 2, h / 2) taken through the matrix and
+    added back).  Raises MrfpHipError when a corner of the image maps to 32768 or beyond: Pillow's NEAREST transform then leaves
+    the 16.16 fixed-point path (Geometry.c ImagingTransformAffine), and its double fallback is not built."""
+    angle = degrees % 360.0
+    if angle == 0:
+        return ROT_COPY, (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+    if angle == 180:
+        return ROT_180, (-1.0, 0.0, float(w), 0.0, -1.0, float(h))
+    if angle in (90, 270) and w == h:
+        return (ROT_90 if angle == 90 else ROT_270), (0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+    cx, cy = w / 2, h / 2
+    a = -math.radians(angle)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    x, y = -cx - 0, -cy - 0
+    m[2], m[5] = m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+    m[2] += cx
+    m[5] += cy
+    for px, py in ((0, 0), (w, h), (0, h), (w, 0)):
+        if not (abs(px * m[0] + py * m[1] + m[2]) < 32768.0 and abs(px * m[3] + py * m[4] + m[5]) < 32768.0):
+            raise _lib.MrfpHipError("rotate: a corner of the %dx%d image leaves the 16.16 fixed-point range of Pillow's NEAREST "
+                                    "transform (|coordinate| < 32768) at %r degrees" % (w, h, degrees))
+    return ROT_AFFINE, tuple(m)
+
+
+def _rotate(name: str, img_u8: torch.Tensor, lab_u8: torch.Tensor, degrees: float, flip: bool):
+    """(flip, then) rotate: contiguous uint8 [H,W,3] / [H,W] on the device -> new tensors of the same shapes."""
+    H, W = lab_u8.shape
+    mode, m = rotate_plan(W, H, degrees)
+    if mode == ROT_COPY and not flip:
+        return img_u8, lab_u8                                # nothing downstream writes into its input
+    out_img, out_lab = torch.empty_like(img_u8), torch.empty_like(lab_u8)
+    call("mrfp_affine_u8", ptr(img_u8), ptr(lab_u8), ptr(out_img), ptr(out_lab), H, W, mode, int(flip), *m, stream())
+    return out_img, out_lab
+
+
+def rotate(img_u8: torch.Tensor, lab_u8: torch.Tensor, degrees: float):
+    """RandomRotate's two calls (dataloaders.py:161-162): img.rotate(degrees, BILINEAR), mask.rotate(degrees, NEAREST), byte for
+    byte.  uint8 [H,W,3] and [H,W] on the GPU -> the rotated pair (same shapes; uncovered corners are 0 in both)."""
+    H, W, img_u8, lab_u8 = _check_pair("rotate", img_u8, lab_u8)
+    out_img, out_lab = _rotate("rotate", img_u8, lab_u8, float(degrees), False)
+    if out_img is img_u8:
+        out_img, out_lab = img_u8.clone(), lab_u8.clone()    # Image.copy()
+    return out_img, out_lab
+
+
+def contrast(img_u8: torch.Tensor, factor: float = 2.0) -> torch.Tensor:
+    """Contrast (dataloaders.py:83-93): ImageEnhance.Contrast(img).enhance(2.0), byte for byte -- the blend of every byte with
+    the rounded mean of the L image, clipped (the contrast op of mrfp_jitter_u8).  uint8 [H,W,3] on the GPU -> the same."""
+    if not (isinstance(img_u8, torch.Tensor) and img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.dim() == 3
+            and img_u8.shape[2] == 3 and img_u8.numel() > 0):
+        raise _lib.MrfpHipError("contrast: a uint8 CUDA tensor [H,W,3] expected (there is no CPU path)")
+    return _jitter(img_u8.contiguous(), [("contrast", float(factor))])
+
+
+def _normalize_arg(name: str, normalize):
+    """normalize=(mean, std), three numbers each (the arguments of Normalize) -> six Python floats, or None."""
+    if normalize is None:
+        return None
+    try:
+        mean, std = normalize
+        six = tuple(float(v) for v in mean) + tuple(float(v) for v in std)
+    except (TypeError, ValueError):
+        six = ()
+    if len(six) != 6 or not all(math.isfinite(v) for v in six) or 0.0 in six[3:]:
+        raise ValueError("%s: normalize=(mean, std) with three finite numbers each and no zero std expected" % name)
+    return six
+
+
+def _to_tensor(crop_u8: torch.Tensor, out_img: torch.Tensor, normalize):
+    """(Normalize ->) ToTensor of a uint8 [Hc,Wc,3] image into out_img float32 [3,Hc,Wc]."""
+    Hc, Wc = crop_u8.shape[0], crop_u8.shape[1]
+    if normalize is None:
+        call("mrfp_u8hwc_to_f32chw", ptr(crop_u8), ptr(out_img), Hc, Wc, stream())
+    else:
+        call("mrfp_u8hwc_to_f32chw_norm", ptr(crop_u8), ptr(out_img), Hc, Wc, *normalize, stream())
+
+
+def _assemble_post(cur: torch.Tensor, lab_u8: torch.Tensor, ty, tx, sh: int, sw: int, flip: bool, pad, crop, Hc: int, Wc: int,
+                   fill: int, blur, contrast_on: bool, normalize, out_img, out_lab):
+    """Pad on the right / at the bottom + crop of the scaled image `cur` [sh,sw,3], then RandomGaussianBlur, Contrast, Normalize,
+    ToTensor as asked.  mrfp_input_assemble pads both sides by (pad_x, pad_y): with the crop origin moved by the same amount its
+    left / top border is never read, which leaves the one-sided padding of RandomScaleCrop."""
+    H, W = lab_u8.shape
+    dev = cur.device
+    out_img = _out_slot(out_img, (3, Hc, Wc), torch.float32, dev, "out_img")
+    out_lab = _out_slot(out_lab, (Hc, Wc), torch.int64, dev, "out_lab")
+    blur_on = blur is not None and blur != 0.0               # PIL returns a copy for radius 0
+    staged = blur_on or contrast_on or normalize is not None
+    crop_u8 = torch.empty((Hc, Wc, 3), dtype=torch.uint8, device=dev) if staged else None
+    call("mrfp_input_assemble", ptr(cur), ptr(lab_u8), ptr(ty), ptr(tx), sh, sw, H, W, int(flip), pad[0], pad[1],
+         crop[0] + pad[0], crop[1] + pad[1], Hc, Wc, int(fill), ptr(out_img), ptr(crop_u8), ptr(out_lab), stream())
+    if not staged:
+        return out_img, out_lab
+    if blur_on:                                              # RandomGaussianBlur (dataloaders.py:168-177)
+        ww, fw = _blur_weights(blur)
+        a, b = crop_u8, torch.empty_like(crop_u8)
+        for vertical in (0, 0, 0, 1, 1, 1):
+            call("mrfp_box_blur3_u8", ptr(a), ptr(b), Hc, Wc, 3, ww, fw, vertical, stream())
+            a, b = b, a
+        crop_u8 = a
+    if contrast_on:                                          # Contrast (dataloaders.py:83-93)
+        crop_u8 = _jitter(crop_u8, [("contrast", 2.0)])
+    _to_tensor(crop_u8, out_img, normalize)
+    return out_img, out_lab
+
+
+@dataclass
+class ScaleCropDraw:
+    flip: bool
+    jitter: Optional[list]             # ColorJitter: [(op, factor), ...] when asked and its gate fired, else None
+    degrees: Optional[float]           # RandomRotate's angle, None without rotation
+    scaled: Tuple[int, int]            # (ow, oh) of RandomScaleCrop's resize
+    pad: Tuple[int, int]               # (padw, padh): right and bottom only
+    crop: Tuple[int, int]              # (x1, y1) in the padded image
+    blur: Optional[float]              # GaussianBlur radius when its gate fired
+
+
+class ScaleCropTransform:
+    """The classic DeepLab train composition from the classes of dataloaders.py, on the device:
+    RandomHorizontalFlip (:139-150) -> ColorJitter (:596-660, when jitter=True, with the constants of the other compositions) ->
+    RandomRotate(rotate_degree) (:153-165, when given) -> RandomScaleCrop(base_size, crop_size, fill) (:180-214) ->
+    RandomGaussianBlur (:168-177) -> Contrast (:83-93, when contrast=True) -> Normalize(*normalize) (:95-115, when given) ->
+    ToTensor (:118-136).  The reference never composes these itself: this ORDER is build-defined; every step is byte for byte
+    (Normalize: bit for bit) what its class computes.
+    RandomScaleCrop: short_size = randint(int(base_size * 0.5), int(base_size * 2.0)) becomes the short edge, the long one is
+    int(1.0 * long * short_size / short); BILINEAR for the image, NEAREST for the label; when short_size < crop_size the result is
+    padded on the RIGHT and at the BOTTOM only (image 0, label `fill`, default 0 as the class has it); then a crop_size square at
+    x1 = randint(0, w - crop_size), y1 = randint(0, h - crop_size).  RandomRotate leaves uncovered corners 0 in image and label
+    (class 0: the reference passes no fillcolor).  Output: float32 [3,crop_size,crop_size] (0..255 without normalize) and int64
+    [crop_size,crop_size]."""
+
+    JITTER = TrainTransform.JITTER
+
+    def __init__(self, base_size: int, crop_size: int, fill: int = 0, rotate_degree: Optional[float] = None, jitter: bool = False,
+                 contrast: bool = False, normalize=None):
+        self.base_size, self.crop_size, self.fill = int(base_size), int(crop_size), int(fill)
+        if self.crop_size <= 0 or int(self.base_size * 0.5) <= 0 or not 0 <= self.fill <= 255:
+            raise ValueError("ScaleCropTransform: base_size >= 2, crop_size > 0 and fill in 0..255 expected")
+        self.rotate_degree, self.jitter, self.contrast = rotate_degree, bool(jitter), bool(contrast)
+        self.normalize = _normalize_arg("ScaleCropTransform", normalize)
+        self._dev_tables = {}
+
+    def draw(self, w: int, h: int, rng=_random, np_rng=np.random) -> ScaleCropDraw:
+        """Consumes python's `random` in the order of the composition: flip gate (:145); with jitter=True the ColorJitter gate
+        (:655) and, when it fires, numpy's stream as get_params does; with a rotate_degree uniform(-degree, degree) (:160);
+        randint for short_size (:190), x1, y1 (:208-209); the blur gate and its radius (:172-174)."""
+        flip = rng.random() < 0.5
+        jitter = _draw_jitter(rng, np_rng, self.JITTER) if self.jitter else None
+        degrees = rng.uniform(-1 * self.rotate_degree, self.rotate_degree) if self.rotate_degree is not None else None
+        short_size = rng.randint(int(self.base_size * 0.5), int(self.base_size * 2.0))
+        if h > w:
+            ow = short_size
+            oh = int(1.0 * h * ow / w)
+        else:
+            oh = short_size
+            ow = int(1.0 * w * oh / h)
+        padw = padh = 0
+        t = self.crop_size
+        if short_size < t:
+            padh = t - oh if oh < t else 0
+            padw = t - ow if ow < t else 0
+        x1 = rng.randint(0, ow + padw - t)
+        y1 = rng.randint(0, oh + padh - t)
+        blur = _draw_blur(rng)
+        return ScaleCropDraw(flip, jitter, degrees, (ow, oh), (padw, padh), (x1, y1), blur)
+
+    def __call__(self, img_u8: torch.Tensor, lab_u8: torch.Tensor, d: ScaleCropDraw, out_img: Optional[torch.Tensor] = None,
+                 out_lab: Optional[torch.Tensor] = None):
+        """img_u8: uint8 [H,W,3], lab_u8: uint8 [H,W], both on the GPU -> (float32 [3,T,T], int64 [T,T]); out_img / out_lab: slots
+        to write into.  The rotated label is materialised as uint8 and read through the nearest-neighbour tables."""
+        H, W, img_u8, lab_u8 = _check_pair("ScaleCropTransform", img_u8, lab_u8)
+        t = self.crop_size
+        (sw, sh), (padw, padh), (x1, y1) = d.scaled, d.pad, d.crop
+        if not (sw > 0 and sh > 0 and padw >= 0 and padh >= 0 and 0 <= x1 <= sw + padw - t and 0 <= y1 <= sh + padh - t):
+            raise _lib.MrfpHipError("ScaleCropTransform: a %d crop at (%d, %d) leaves the %dx%d image padded by (%d, %d)" % (
+                t, x1, y1, sw, sh, padw, padh))
+        dev = img_u8.device
+        bx, kx, by, ky, tx, ty = _cached(self._dev_tables, (str(dev), H, W, sh, sw), lambda: _dev(
+            dev, *_bilinear_tables(W, sw), *_bilinear_tables(H, sh), _nearest_table(W, sw), _nearest_table(H, sh)))
+        cur = _jitter(img_u8, d.jitter)                      # per pixel: commutes with the flip
+        flip = d.flip
+        if d.degrees is not None:                            # the rotation reads the source mirrored: the flip is done with it
+            cur, lab_u8 = _rotate("ScaleCropTransform", cur, lab_u8, d.degrees, flip)
+            flip = False
+        cur = _resample(cur, H, W, sh, sw, (bx, kx, kx.shape[1]), (by, ky, ky.shape[1]), flip)
+        return _assemble_post(cur, lab_u8, ty, tx, sh, sw, flip, (padw, padh), (x1, y1), t, t, self.fill, d.blur, self.contrast,
+                              self.normalize, out_img, out_lab)
+
+
+class FixScaleCropTransform:
+    """The evaluation composition FixScaleCrop(crop_size) -> Contrast (when contrast=True) -> Normalize(*normalize) (when given)
+    -> ToTensor (dataloaders.py:439-465, 83-115, 118-136; the lines commented in every transform_val of main.py) on the device.
+    FixScaleCrop: the short edge goes to crop_size (w > h: oh = crop_size, ow = int(1.0 * w * oh / h); else the other way round),
+    BILINEAR for the image and NEAREST for the label; the centre crop starts at int(round((ow - crop_size) / 2.)),
+    int(round((oh - crop_size) / 2.)) -- Python's round-half-even.  Only the columns and rows the crop keeps are resampled.
+    Called as the other evaluation transforms (harness.eval_batches): `encoder` encodes the label first, as the reference's
+    __getitem__ does.  Output: float32 [3,crop_size,crop_size] and int64 [crop_size,crop_size]."""
+
+    def __init__(self, crop_size: int, contrast: bool = False, normalize=None):
+        self.crop_size, self.contrast = int(crop_size), bool(contrast)
+        if self.crop_size <= 0:
+            raise ValueError("FixScaleCropTransform: crop_size > 0 expected")
+        self.normalize = _normalize_arg("FixScaleCropTransform", normalize)
+        self._dev_tables = {}
+
+    def geometry(self, w: int, h: int):
+        """-> (ow, oh, x1, y1) of a w x h source: the scaled size and the crop origin in it."""
+        t = self.crop_size
+        if w > h:
+            oh = t
+            ow = int(1.0 * w * oh / h)
+        else:
+            ow = t
+            oh = int(1.0 * h * ow / w)
+        return ow, oh, int(round((ow - t) / 2.)), int(round((oh - t) / 2.))
+
+    def __call__(self, img_u8: torch.Tensor, lab_u8: torch.Tensor, encoder: Optional[LabelEncoder] = None,
+                 out_img: Optional[torch.Tensor] = None, out_lab: Optional[torch.Tensor] = None):
+        H, W, img_u8, lab_u8 = _check_pair("FixScaleCropTransform", img_u8, lab_u8)
+        dev, t = img_u8.device, self.crop_size
+
+        def build():
+            ow, oh, x1, y1 = self.geometry(W, H)
+            bx, kx = _bilinear_tables(W, ow)
+            by, ky = _bilinear_tables(H, oh)
+            return _dev(dev, bx[x1:x1 + t], kx[x1:x1 + t], by[y1:y1 + t], ky[y1:y1 + t], _nearest_table(W, ow)[x1:x1 + t],
+                        _nearest_table(H, oh)[y1:y1 + t]) + (ow, oh)
+        bx, kx, by, ky, tx, ty, ow, oh = _cached(self._dev_tables, (str(dev), H, W), build)
+        cur = img_u8
+        if ow != W or t != W:       # the kept columns' rows of Pillow's tables (at ow == W PIL copies: the coefficients are (0, 1, 0))
+            tmp = torch.empty((H, t, 3), dtype=torch.uint8, device=dev)
+            call("mrfp_resample_u8", ptr(cur), ptr(tmp), H, W, H, t, 3, ptr(bx), ptr(kx), kx.shape[1], 0, 0, stream())
+            cur = tmp
+        if oh != H or t != H:
+            tmp = torch.empty((t, t, 3), dtype=torch.uint8, device=dev)
+            call("mrfp_resample_u8", ptr(cur), ptr(tmp), H, t, t, t, 3, ptr(by), ptr(ky), ky.shape[1], 1, 0, stream())
+            cur = tmp
+        if encoder is not None:
+            lab_u8 = encoder(lab_u8)
+        return _assemble_post(cur, lab_u8, ty, tx, t, t, False, (0, 0), (0, 0), t, t, 0, None, self.contrast, self.normalize,
+                              out_img, out_lab)
 
 
 # ---- frequency filters (dataloaders.py:24-79; csrc/freq.hip) --------------------------------------------------------------
