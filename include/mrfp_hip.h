@@ -219,6 +219,47 @@ int mrfp_upsample_ce_bwd(const void* P, int64_t ld, const int64_t* target, const
                          void* dlogits, int64_t Cd, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
                          int64_t C, int64_t ignore_index, void* stream);
 
+/* Weighted / label-smoothed / per-image forms of the two losses above: the criteria a caller hands to the reference's
+ * DeepV3Plus (network/deepv3.py:111 `criterion`, `criterion_aux`; main.py:822 builds the plain one).
+ * weight: fp32 class weights, row b at weight + b*wstride: wstride == 0 one row [C] for all images, wstride == C one row per
+ * image [B][C]; NULL = all ones.  smoothing: 0 <= eps < 1.  For a valid pixel i of image b (label t in [0,C) and != ignore_index),
+ * lp = log_softmax(logits_i), w = its weight row:
+ *     num_i = (1-eps) * w[t] * (-lp[t]) + (eps/C) * sum_c w[c] * (-lp[c]),      den_i = w[t]
+ *     MRFP_CE_MEAN        sum_i num_i / sum_i den_i   over the batch (torch's reduction='mean'; 0/0 -> NaN)
+ *     MRFP_CE_SUM         sum_i num_i
+ *     MRFP_CE_IMAGE_MEAN  sum_b ( sum_{i in b} num_i / sum_{i in b} den_i )     (an all-ignored image -> NaN)
+ * ws: float [2 * mrfp_ce_w_nblocks(B, HW)] (one (num, den) pair per workgroup; a workgroup stays inside one image).
+ * loss: float [mrfp_ce_w_loss_floats(B, mode)]: loss[0] the loss, then the denominators the backward divides by -- loss[1] the
+ * batch denominator (MEAN, SUM), loss[1 + b] the one of image b (IMAGE_MEAN).  Partial sums are reduced in double in a fixed
+ * order: two runs are bit-identical.
+ * bwd: dlogits_c = k * ( p_c * ((1-eps) w[t] + (eps/C) sum_j w[j]) - (1-eps) w[t] [c == t] - (eps/C) w[c] ),
+ * k = gscale[0] / den (MEAN), gscale[0] (SUM), gscale[0] / den_b (IMAGE_MEAN); ignored pixels and pad channels are zeros.
+ * The upsample form takes 1 <= C <= 64 and writes d(logits)[B,H,W,Cd] for mrfp_bilinear_bwd exactly as mrfp_upsample_ce_bwd. */
+typedef enum { MRFP_CE_MEAN = 0, MRFP_CE_SUM = 1, MRFP_CE_IMAGE_MEAN = 2 } mrfp_ce_mode;
+int64_t mrfp_ce_w_nblocks(int64_t B, int64_t HW);
+int64_t mrfp_ce_w_loss_floats(int64_t B, int mode);
+int mrfp_ce_w_fwd(const void* logits, const int64_t* target, int dtype, int64_t B, int64_t HW, int64_t C,
+                  int64_t ignore_index, const float* weight, int64_t wstride, float smoothing, int mode, float* ws,
+                  float* loss, void* stream);
+int mrfp_ce_w_bwd(const void* logits, const int64_t* target, const float* loss, const float* gscale, void* dlogits,
+                  int dtype, int64_t B, int64_t HW, int64_t C, int64_t ignore_index, const float* weight, int64_t wstride,
+                  float smoothing, int mode, void* stream);
+int mrfp_upsample_ce_w_fwd(const void* P, int64_t ld, const int64_t* target, int dtype, int64_t B, int64_t Hi, int64_t Wi,
+                           int64_t H, int64_t W, int64_t C, int64_t ignore_index, const float* weight, int64_t wstride,
+                           float smoothing, int mode, float* ws, float* loss, void* stream);
+int mrfp_upsample_ce_w_bwd(const void* P, int64_t ld, const int64_t* target, const float* loss, const float* gscale,
+                           void* dlogits, int64_t Cd, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
+                           int64_t C, int64_t ignore_index, const float* weight, int64_t wstride, float smoothing, int mode,
+                           void* stream);
+
+/* Per-image class weights from the label map, on the device (the rule of the per-image class-weighted criterion the DeepLabV3+
+ * baseline was trained with; build-defined here).  n_c = number of labels equal to c in [0,C) of one image
+ * (batch != 0: of all images, one output row), f_c = n_c / sum_c n_c:
+ *     norm == 0:  w_c = 1 + upper_bound * (1 - f_c)        norm != 0:  w_c = 1 + upper_bound / f_c        n_c == 0:  w_c = 1
+ * in double, rounded once to float.  counts_ws: int64 [B*C] scratch (cleared here); weight_out: float [B][C] ([C] if batch). */
+int mrfp_label_class_weights(const int64_t* target, int64_t B, int64_t HW, int64_t C, double upper_bound, int norm,
+                             int batch, int64_t* counts_ws, float* weight_out, void* stream);
+
 /* Eval: argmax over classes + 19x19 confusion histogram on the device (reference main.py:898-909,
  * metrics.py:122-126): hist[num_classes*gt + pred] += 1 for gt in [0,num_classes).  hist: int64
  * [C*C], accumulated (not cleared).  pred (optional, uint8 [npix]) receives the arg-max. */

@@ -22,6 +22,7 @@ from torch import nn
 from . import ops
 from .config import cfg
 from .conv import wgrad_boundary
+from .loss import fused_ce_kwargs, fused_loss
 from .network import Resnet
 from .network.mynn import (HipBatchNorm2d, HipConv2d, HipInstanceNorm2d, Norm2d, Upsample, conv_norm, initialize_weights,
                            initialize_weights_kaimingnormal_forOC)
@@ -286,15 +287,11 @@ class _DeepLabBase(nn.Module):
         d = conv_norm(self.final1[0], self.final1[1], d, relu=True)
         return conv_norm(self.final1[3], self.final1[4], d, relu=True)
 
-    def _plain_ce(self):
-        c = self.criterion
-        return isinstance(c, nn.CrossEntropyLoss) and c.weight is None and c.reduction == "mean" and c.label_smoothing == 0.0
-
     def _head(self, dec1, size, gts, training, low_res=False):
         """final2 (1x1 conv + bias) -> bilinear upsample to the input size -> loss or logits (reference
         deepv3.py:360-367).  The low-resolution class scores live in a 32-channel padded buffer so the conv stays
-        chunk-aligned; in training with the plain CE criterion the upsample and the loss are one kernel and the
-        full-resolution logits are never written.  low_res (eval only): return that padded low-resolution buffer
+        chunk-aligned; in training with a criterion the fused kernels compute (loss.fused_loss) the upsample and the loss are
+        one kernel and the full-resolution logits are never written.  low_res (eval only): return that padded low-resolution buffer
         [B,32,h/4,w/4] itself, in the activation dtype -- harness.evaluate_tta resizes it inside ops.prob_accum."""
         f2 = self.final2[0]
         nc = f2.out_channels
@@ -304,8 +301,8 @@ class _DeepLabBase(nn.Module):
             if training:
                 raise ValueError("low_res is an eval-path option (training=False)")
             return dec2
-        if training and cfg.MODEL.FUSE_UPSAMPLE_CE and self._plain_ce():
-            return ops.upsample_cross_entropy(dec2, gts, size, nc, self.criterion.ignore_index)
+        if training and cfg.MODEL.FUSE_UPSAMPLE_CE and fused_ce_kwargs(self.criterion) is not None:
+            return fused_loss(self.criterion, dec2, gts, size, nc)
         main_out = ops.upsample_bilinear(dec2, size, channels=nc)
         if training:
             return self._loss(main_out, gts)
@@ -322,17 +319,18 @@ class _DeepLabBase(nn.Module):
         pitch = (nc + 31) // 32 * 32
         p_low, p_half = conv.shared_conv1x1_pair(dec1, oc_dec, f2.weight, f2.bias, pitch)
         dec2 = ops.upsample_bilinear(p_low, (oc_dec.shape[2], oc_dec.shape[3]), addend=p_half)
-        if training and cfg.MODEL.FUSE_UPSAMPLE_CE and self._plain_ce():
-            return ops.upsample_cross_entropy(dec2, gts, size, nc, self.criterion.ignore_index)
+        if training and cfg.MODEL.FUSE_UPSAMPLE_CE and fused_ce_kwargs(self.criterion) is not None:
+            return fused_loss(self.criterion, dec2, gts, size, nc)
         main_out = ops.upsample_bilinear(dec2, size, channels=nc)
         if training:
             return self._loss(main_out, gts)
         return main_out.float()
 
     def _loss(self, main_out, gts):
-        if self._plain_ce():
-            return ops.cross_entropy(main_out, gts, self.criterion.ignore_index)
-        return self.criterion(main_out.float(), gts)
+        loss = fused_loss(self.criterion, main_out, gts)
+        if loss is None:          # reduction='none', a foreign module: the one stock path, on the full-resolution fp32 logits
+            loss = self.criterion(main_out.float(), gts)
+        return loss
 
 
 class MRFPPlus(_DeepLabBase):

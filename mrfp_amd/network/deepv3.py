@@ -23,6 +23,7 @@ from .. import ops
 from ..config import cfg
 from ..conv import wgrad_boundary
 from ..deepv3 import _AtrousSpatialPyramidPoolingModule, _ConvBnRelu, _DeepLabBase
+from ..loss import fused_loss
 from . import Mobilenet, Resnet
 from .mynn import HipConv2d, Norm2d, freeze_weights, initialize_weights, unfreeze_weights  # noqa: F401
 from .wider_resnet import HipDropout2d
@@ -170,10 +171,10 @@ class DeepV3Plus(_DeepLabBase):
         th = torch.as_tensor(ops._nearest_table(Hs, h, None), dtype=torch.long, device=aux_gts.device)
         tw = torch.as_tensor(ops._nearest_table(Ws, w, None), dtype=torch.long, device=aux_gts.device)
         aux_gts = aux_gts.long().index_select(1, th).index_select(2, tw).contiguous()
-        c = self.criterion_aux
-        if isinstance(c, nn.CrossEntropyLoss) and c.weight is None and c.reduction == "mean" and c.label_smoothing == 0.0:
-            return ops.cross_entropy(aux_out, aux_gts, c.ignore_index)
-        return c(aux_out.float(), aux_gts)
+        loss = fused_loss(self.criterion_aux, aux_out, aux_gts)
+        if loss is None:
+            loss = self.criterion_aux(aux_out.float(), aux_gts)
+        return loss
 
     def forward(self, x, gts=None, aux_gts=None, img_gt=None, visualize=False, cal_covstat=False, apply_wtloss=True,
                 training=None, low_res=False):

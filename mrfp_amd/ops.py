@@ -986,8 +986,81 @@ class _CrossEntropy(torch.autograd.Function):
         return d, None, None
 
 
-def cross_entropy(logits, target, ignore_index=255):
-    return _CrossEntropy.apply(logits, target, ignore_index)
+# ---- class weights / label smoothing / sum / per-image mean: the criteria a caller hands to the reference's DeepV3Plus
+# (network/deepv3.py:111 `criterion`, `criterion_aux`) instead of the plain one of main.py:822 -- csrc/loss.hip, mrfp_ce_w_* ----
+CE_MEAN, CE_SUM, CE_IMAGE_MEAN = 0, 1, 2
+
+
+def _ce_general(weight, label_smoothing, reduction, per_image, _general):
+    """True when the call needs the weighted entries; with the four keywords at their defaults the plain kernels run untouched."""
+    return _general or weight is not None or float(label_smoothing) != 0.0 or reduction != "mean" or bool(per_image)
+
+
+def _ce_options(who, weight, label_smoothing, reduction, per_image, B, C, device):
+    """-> (weight fp32 [C] / [B,C] or None, wstride, eps, mode), validated without touching the device."""
+    if reduction not in ("mean", "sum"):
+        raise _lib.MrfpHipError("%s: reduction must be 'mean' or 'sum' (got %r; 'none' stays the caller's business)" % (who, reduction))
+    if per_image and reduction != "mean":
+        raise _lib.MrfpHipError("%s: per_image sums the per-image weighted means: reduction must be 'mean'" % who)
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise _lib.MrfpHipError("%s: label_smoothing must be in [0, 1) (got %r)" % (who, label_smoothing))
+    wstride = 0
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or weight.device != device \
+                or tuple(weight.shape) not in ((C,), (B, C)):
+            raise _lib.MrfpHipError("%s: weight must be a float32 tensor of shape [C] or [B, C] on %s (C=%d, B=%d; got %s)" % (
+                who, device, C, B, (weight.dtype, tuple(weight.shape), weight.device) if isinstance(weight, torch.Tensor) else type(weight)))
+        weight = weight.detach().contiguous()
+        wstride = C if weight.dim() == 2 else 0
+    mode = CE_IMAGE_MEAN if per_image else (CE_MEAN if reduction == "mean" else CE_SUM)
+    return weight, wstride, eps, mode
+
+
+def _ce_buffers(B, HW, mode, device):
+    L = _lib.lib()
+    ws = torch.empty(2 * int(L.mrfp_ce_w_nblocks(B, HW)), dtype=torch.float32, device=device)
+    loss = torch.empty(int(L.mrfp_ce_w_loss_floats(B, mode)), dtype=torch.float32, device=device)
+    return ws, loss
+
+
+class _CrossEntropyW(torch.autograd.Function):
+    """nn.CrossEntropyLoss(weight, ignore_index, label_smoothing, reduction 'mean' / 'sum') and the per-image weighted mean."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, weight, label_smoothing, reduction, per_image):
+        logits = _chk(logits, "logits")
+        B, C, H, W = logits.shape
+        target = target.contiguous()
+        if target.dtype != torch.int64 or tuple(target.shape) != (B, H, W):
+            raise _lib.MrfpHipError("cross_entropy: target must be int64 [B,H,W]")
+        weight, wstride, eps, mode = _ce_options("cross_entropy", weight, label_smoothing, reduction, per_image, B, C, logits.device)
+        ws, loss = _ce_buffers(B, H * W, mode, logits.device)
+        call("mrfp_ce_w_fwd", ptr(logits), ptr(target), dt(logits), B, H * W, C, int(ignore_index), ptr(weight), wstride, eps, mode,
+             ptr(ws), ptr(loss), stream())
+        ctx.save_for_backward(logits, target, loss, weight)
+        ctx.cfg = (int(ignore_index), wstride, eps, mode)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, loss, weight = ctx.saved_tensors
+        ignore, wstride, eps, mode = ctx.cfg
+        B, C, H, W = logits.shape
+        gs = g.detach().float().reshape(1).contiguous()
+        d = torch.empty_like(logits, memory_format=CL)
+        call("mrfp_ce_w_bwd", ptr(logits), ptr(target), ptr(loss), ptr(gs), ptr(d), dt(logits), B, H * W, C, ignore, ptr(weight),
+             wstride, eps, mode, stream())
+        return d, None, None, None, None, None, None
+
+
+def cross_entropy(logits, target, ignore_index=255, *, weight=None, label_smoothing=0.0, reduction="mean", per_image=False,
+                  _general=False):
+    """weight: float32 [C] (shared) or [B, C] (one row per image) on the device; reduction 'mean' (sum of weighted losses over the
+    sum of the target weights, as torch) or 'sum'; per_image: the sum over images of each image's weighted mean."""
+    if not _ce_general(weight, label_smoothing, reduction, per_image, _general):
+        return _CrossEntropy.apply(logits, target, ignore_index)
+    return _CrossEntropyW.apply(logits, target, ignore_index, weight, label_smoothing, reduction, per_image)
 
 
 class _UpsampleCrossEntropy(torch.autograd.Function):
@@ -1029,9 +1102,67 @@ class _UpsampleCrossEntropy(torch.autograd.Function):
         return dP, None, None, None, None, None
 
 
-def upsample_cross_entropy(P, target, size, channels, ignore_index=255):
-    """P: channel-padded low-resolution class scores [B,ld,Hi,Wi] (ld a multiple of the 16-byte chunk)."""
-    return _UpsampleCrossEntropy.apply(P, target, int(size[0]), int(size[1]), int(channels), ignore_index)
+class _UpsampleCrossEntropyW(torch.autograd.Function):
+    """_UpsampleCrossEntropy with class weights / label smoothing / sum / per-image mean (mrfp_upsample_ce_w_*)."""
+
+    @staticmethod
+    def forward(ctx, P, target, H, W, C, ignore_index, weight, label_smoothing, reduction, per_image):
+        P = _chk(P, "P")
+        B, ld, Hi, Wi = P.shape
+        target = target.contiguous()
+        if target.dtype != torch.int64 or tuple(target.shape) != (B, H, W):
+            raise _lib.MrfpHipError("upsample_cross_entropy: target must be int64 [B,H,W]")
+        weight, wstride, eps, mode = _ce_options("upsample_cross_entropy", weight, label_smoothing, reduction, per_image, B, C, P.device)
+        ws, loss = _ce_buffers(B, H * W, mode, P.device)
+        call("mrfp_upsample_ce_w_fwd", ptr(P), ld, ptr(target), dt(P), B, Hi, Wi, H, W, C, int(ignore_index), ptr(weight), wstride,
+             eps, mode, ptr(ws), ptr(loss), stream())
+        ctx.save_for_backward(P, target, loss, weight)
+        ctx.cfg = (H, W, C, int(ignore_index), wstride, eps, mode)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        P, target, loss, weight = ctx.saved_tensors
+        H, W, C, ignore, wstride, eps, mode = ctx.cfg
+        B, ld, Hi, Wi = P.shape
+        epc = 16 // P.element_size()
+        Cd = (C + epc - 1) // epc * epc
+        gs = g.detach().float().reshape(1).contiguous()
+        dP = empty_cl(B, ld, Hi, Wi, P.dtype, P.device)
+        dlog = empty_cl(B, Cd, H, W, P.dtype, P.device)
+        call("mrfp_upsample_ce_w_bwd", ptr(P), ld, ptr(target), ptr(loss), ptr(gs), ptr(dlog), Cd, dt(P), B, Hi, Wi, H, W, C,
+             ignore, ptr(weight), wstride, eps, mode, stream())
+        if ld != Cd:
+            dP.zero_()
+        call("mrfp_bilinear_bwd", ptr(dlog), ptr(dP), dt(P), B, Hi, Wi, H, W, Cd, ld, stream())
+        return dP, None, None, None, None, None, None, None, None, None
+
+
+def upsample_cross_entropy(P, target, size, channels, ignore_index=255, *, weight=None, label_smoothing=0.0, reduction="mean",
+                           per_image=False, _general=False):
+    """P: channel-padded low-resolution class scores [B,ld,Hi,Wi] (ld a multiple of the 16-byte chunk).  Keywords as cross_entropy."""
+    if not _ce_general(weight, label_smoothing, reduction, per_image, _general):
+        return _UpsampleCrossEntropy.apply(P, target, int(size[0]), int(size[1]), int(channels), ignore_index)
+    return _UpsampleCrossEntropyW.apply(P, target, int(size[0]), int(size[1]), int(channels), ignore_index, weight, label_smoothing,
+                                        reduction, per_image)
+
+
+def label_class_weights(target, num_classes, upper_bound=1.0, norm=False, batch=False):
+    """Per-image class weights from the label map, on the device (csrc/loss.hip, mrfp_label_class_weights):
+    with n_c the count of label c in [0, num_classes) and f_c = n_c / sum n_c, w_c = 1 + upper_bound * (1 - f_c) (norm: 1 +
+    upper_bound / f_c) where n_c > 0, else 1.  -> float32 [B, C], or [1, C] from the pooled counts of all images (batch)."""
+    if not isinstance(target, torch.Tensor) or not target.is_cuda:
+        raise _lib.MrfpHipError("label_class_weights: target must be a GPU tensor: the HIP path has no CPU fallback")
+    if target.dtype != torch.int64 or target.dim() != 3:
+        raise _lib.MrfpHipError("label_class_weights: target must be int64 [B,H,W] (got %s %s)" % (target.dtype, tuple(target.shape)))
+    target = target.contiguous()
+    B, H, W = target.shape
+    C, rows = int(num_classes), (1 if batch else B)
+    counts = torch.empty(rows * C, dtype=torch.int64, device=target.device)
+    out = torch.empty(rows, C, dtype=torch.float32, device=target.device)
+    call("mrfp_label_class_weights", ptr(target), B, H * W, C, float(upper_bound), int(bool(norm)), int(bool(batch)), ptr(counts),
+         ptr(out), stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------
