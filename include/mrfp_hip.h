@@ -405,6 +405,45 @@ int mrfp_sgd_step(float* p, const float* g, float* m, int64_t n, float lr, float
                   float weight_decay, float gscale, int first, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Checked step: dynamic loss scale, skip on a non-finite gradient and gradient-norm clipping decided ON THE DEVICE -- the
+ * semantics of torch.amp.GradScaler (unscale_ / step / update, i.e. torch._amp_update_scale_) and
+ * torch.nn.utils.clip_grad_norm_ around the update rule of mrfp_sgd_step, without the host read of the overflow flag.
+ * The reference trains in fp32 only (main.py:857-864), so this is build-defined.
+ *
+ * state: the device step state, eight 32-bit words (32 bytes), 16-byte aligned:
+ *   word 0  float scale           the loss scale S; the cross-entropy backward kernels read it as their `gscale` pointer
+ *   word 1  int   growth_tracker  consecutive taken steps since the scale last changed
+ *   word 2  int   found_inf       1 if the last checked gradient held an inf / NaN
+ *   word 3  float grad_norm       || G * gscale / S ||_2 of the last check (inf / NaN possible when found_inf)
+ *   word 4  float gmul            the factor the last step applied to the raw arena gradient (0 when found_inf)
+ *   word 5  int   taken           steps applied so far
+ *   word 6  int   skipped         steps skipped so far
+ *   word 7  reserved (0)
+ *
+ * mrfp_grad_check (two launches: partial sums, then a one-workgroup finalize) looks at the raw arena G = g[0..n), S = state.scale
+ * and gscale (the 1/world of the data-parallel average):
+ *   found_inf = any(!finite(G)), tested on the exponent bits of each element -- a large finite gradient is not an overflow;
+ *   grad_norm = || G * gscale / S ||_2, accumulated in double in a fixed order (two runs are bit-identical);
+ *   found_inf:  skipped += 1; dynamic: S <- S * backoff, growth_tracker <- 0;
+ *   otherwise:  c = min(1, max_norm / (grad_norm + 1e-6)) (max_norm = +inf: no clipping), gmul = gscale / S * c, taken += 1;
+ *               dynamic: growth_tracker += 1, and when it reaches growth_interval: S <- S * growth (kept if that is not finite),
+ *               growth_tracker <- 0.
+ * gmul carries the OLD scale to the step that follows; the next backward reads the new one (stream order).
+ * ws: 16 * mrfp_grad_check_nblocks(n) bytes, 16-byte aligned (one {double, flag} per workgroup; no atomics).
+ * Refused before any launch: null pointers, n % 4 != 0, misaligned g / ws / state, growth <= 1, backoff outside (0, 1),
+ * growth_interval < 1, max_norm <= 0.
+ *
+ * mrfp_sgd_step_checked: found_inf set -> writes nothing (p and m stay bit for bit); else g' = g*gmul + wd*p,
+ * m = momentum*m + g', p -= lr*m.  No first-step flag: m must be zero wherever no momentum exists yet (then m = g', the copy
+ * torch.optim.SGD's first step makes).
+ * ------------------------------------------------------------------------------------------- */
+int64_t mrfp_grad_check_nblocks(int64_t n);
+int mrfp_grad_check(const float* g, int64_t n, float gscale, void* ws, void* state, int dynamic, float growth,
+                    float backoff, int growth_interval, float max_norm, void* stream);
+int mrfp_sgd_step_checked(float* p, const float* g, float* m, int64_t n, float lr, float momentum,
+                          float weight_decay, const void* state, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Group whitening passes (groups of 16 channels; reference network/sync_switchwhiten.py:20-26, 161-170:
  * in_data.mean(-1), bmm(in_data, in_data^T) per group; :217 bmm(wm, in_data); network/instance_whitening.py):
  *   mrfp_group_moments: M[b,g,i,j] = sum_p a[b,p,16g+i] * b[b,p,16g+j]  (fp32 [B,C/16,16,16]) and, when sum_a != NULL,

@@ -29,6 +29,81 @@ def poly_lr_factor(it: int, max_iter: int = 40000, power: float = 0.9) -> float:
     return math.pow(1 - it / max_iter, power)
 
 
+class LossScaler:
+    """The loss scale of a half-precision run as DEVICE state: torch.amp.GradScaler's rule (scale *= backoff_factor after a step
+    whose gradient held an inf / NaN, scale *= growth_factor after growth_interval clean steps in a row) applied by
+    mrfp_grad_check's finalize kernel, so no step waits for the host.  dynamic=False keeps the scale fixed and still skips a step
+    with a non-finite gradient.  The state is the eight 32-bit words of include/mrfp_hip.h (scale, growth_tracker, found_inf,
+    grad_norm, gmul, taken, skipped, reserved); `scale_tensor` is the 0-dim fp32 view of word 0 that backward is seeded with.
+    Build-defined: the reference trains in fp32."""
+
+    FIELDS = ("scale", "growth_tracker", "found_inf", "grad_norm", "gmul", "taken", "skipped")
+    _FLOAT = (0, 3, 4)            # words that hold a float
+
+    def __init__(self, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, dynamic=True,
+                 device=None):
+        init_scale, growth_factor, backoff_factor = float(init_scale), float(growth_factor), float(backoff_factor)
+        if not (init_scale > 0.0) or math.isinf(init_scale):
+            raise ValueError("init_scale must be positive and finite, got %r" % (init_scale,))
+        if not (growth_factor > 1.0) or math.isinf(growth_factor):
+            raise ValueError("growth_factor must be > 1, got %r" % (growth_factor,))
+        if not (0.0 < backoff_factor < 1.0):
+            raise ValueError("backoff_factor must be in (0, 1), got %r" % (backoff_factor,))
+        if int(growth_interval) != growth_interval or int(growth_interval) < 1:
+            raise ValueError("growth_interval must be an integer >= 1, got %r" % (growth_interval,))
+        self.growth_factor, self.backoff_factor = growth_factor, backoff_factor
+        self.growth_interval, self.dynamic = int(growth_interval), bool(dynamic)
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"      # (on the CPU: state_dict / info only)
+        self._set_state(torch.device(device), init_scale, 0)
+
+    def _set_state(self, device, scale, tracker, taken=0, skipped=0):
+        words = torch.zeros(8, dtype=torch.int32)
+        words.view(torch.float32)[0] = scale
+        words[1], words[5], words[6] = int(tracker), int(taken), int(skipped)
+        self.state = words.to(device)
+        self.scale_tensor = self.state.view(torch.float32)[0]            # 0-dim view: the CE backward kernels read this address
+
+    def to(self, device):
+        if self.state.device != torch.device(device):
+            i = self.info()
+            self._set_state(torch.device(device), i["scale"], i["growth_tracker"], i["taken"], i["skipped"])
+        return self
+
+    def info(self):
+        """The seven fields of the device state as python numbers.  This is the one host wait of the feature, and it happens only
+        when somebody asks."""
+        w = self.state.cpu()
+        f = w.view(torch.float32)
+        return {k: (float(f[i]) if i in self._FLOAT else int(w[i])) for i, k in enumerate(self.FIELDS)}
+
+    # the key layout of torch.amp.GradScaler.state_dict(): either side loads the other's dict
+    def state_dict(self):
+        i = self.info()
+        return {"scale": i["scale"], "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor,
+                "growth_interval": self.growth_interval, "_growth_tracker": i["growth_tracker"]}
+
+    def load_state_dict(self, sd):
+        new = LossScaler(sd["scale"], sd["growth_factor"], sd["backoff_factor"], sd["growth_interval"], self.dynamic, "cpu")
+        tracker = int(sd["_growth_tracker"])
+        if tracker < 0:
+            raise ValueError("_growth_tracker must be >= 0, got %r" % (tracker,))
+        self.growth_factor, self.backoff_factor, self.growth_interval = new.growth_factor, new.backoff_factor, new.growth_interval
+        i = self.info()
+        words = new.state.clone()
+        words[1], words[5], words[6] = tracker, i["taken"], i["skipped"]
+        self.state.copy_(words)                  # in place: captured graphs and scale_tensor keep pointing at this block
+
+
+def _check_max_grad_norm(max_grad_norm):
+    if max_grad_norm is None:
+        return None
+    max_grad_norm = float(max_grad_norm)
+    if not (max_grad_norm > 0.0):
+        raise ValueError("max_grad_norm must be > 0, got %r" % (max_grad_norm,))
+    return max_grad_norm
+
+
 class FlatArena:
     """Trainable parameters and their gradients as views into two flat fp32 buffers (every tensor starts
     16-byte aligned).  Device-agnostic host logic: the data-parallel buckets are ranges of `flat_g`."""
@@ -74,6 +149,8 @@ class FlatSGD(FlatArena):
         self.max_iter, self.power = max_iter, power
         self.it = 0
         self.has_momentum = False        # torch.optim.SGD: the first step copies the gradient into the momentum buffer
+        self._scaler = None              # the LossScaler of the checked steps so far: its `taken` count says whether one was applied
+        self._check_ws = None
 
     @property
     def lr(self):
@@ -87,6 +164,8 @@ class FlatSGD(FlatArena):
         `mrfp_iteration` carries the scheduler position, which the reference does not save (its resume restarts the
         poly schedule); loading a plain torch state dict recovers it from lr / initial_lr."""
         state = {}
+        if not self.has_momentum and self._scaler is not None:       # checked steps decide on the device: ask (a host copy, like the rest)
+            self.has_momentum = self._scaler.info()["taken"] > 0
         if self.has_momentum:
             for i, p, o in zip(self.all_index, self.params, self.offsets):
                 state[i] = {"momentum_buffer": self.flat_m[o:o + p.numel()].view(p.shape).detach().clone().cpu()}
@@ -125,12 +204,37 @@ class FlatSGD(FlatArena):
         self.missing_state = len(self.params) - n if n else 0
         self.has_momentum = n > 0
 
-    def step(self, gscale: float = 1.0):
+    def step(self, gscale: float = 1.0, scaler: Optional[LossScaler] = None, max_grad_norm: Optional[float] = None):
+        """One optimiser step + scheduler step.  Without `scaler`: mrfp_sgd_step with the host-side factor `gscale`.
+        With a LossScaler: mrfp_grad_check (partial sums, finalize) and mrfp_sgd_step_checked on the current stream -- the device
+        decides whether the step is applied (no inf / NaN in the arena), by which factor (gscale / scale, times the
+        clip_grad_norm_ coefficient of `max_grad_norm`), and what the next loss scale is; nothing waits for the host.  The
+        schedule position `it` advances on a skipped step too, as the reference's unconditional scheduler.step() does
+        (main.py:864)."""
         if self.flat_p.device.type != "cuda":
             raise _lib.MrfpHipError("FlatSGD.step needs the arenas on the GPU: the HIP path has no CPU fallback")
-        call("mrfp_sgd_step", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), self.n, float(self.lr),
-             float(self.momentum), float(self.weight_decay), float(gscale), int(not self.has_momentum), stream())
-        self.has_momentum = True
+        max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        if scaler is None:
+            if max_grad_norm is not None:
+                raise ValueError("max_grad_norm needs a LossScaler (LossScaler(init_scale=1.0, dynamic=False) for a plain run)")
+            # (after a checked step the momentum arena obeys "zero where no momentum exists": mu*0 + g' is the first-step copy)
+            first = not self.has_momentum and self._scaler is None
+            call("mrfp_sgd_step", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), self.n, float(self.lr),
+                 float(self.momentum), float(self.weight_decay), float(gscale), int(first), stream())
+            self.has_momentum = True
+        else:
+            if scaler.state.device != self.flat_p.device:
+                raise _lib.MrfpHipError("LossScaler state on %s, arenas on %s: scaler.to(device) first"
+                                        % (scaler.state.device, self.flat_p.device))
+            if self._check_ws is None:
+                nblk = int(_lib.lib().mrfp_grad_check_nblocks(self.n))
+                self._check_ws = torch.empty(4 * nblk, dtype=torch.float32, device=self.flat_p.device)
+            call("mrfp_grad_check", ptr(self.flat_g), self.n, float(gscale), ptr(self._check_ws), ptr(scaler.state),
+                 int(scaler.dynamic), scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval,
+                 math.inf if max_grad_norm is None else max_grad_norm, stream())
+            call("mrfp_sgd_step_checked", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), self.n, float(self.lr),
+                 float(self.momentum), float(self.weight_decay), ptr(scaler.state), stream())
+            self._scaler = scaler
         # the fused kernel wrote the arena behind autograd's version counters: invalidate the derived
         # weight packs explicitly (mrfp_amd/conv.py rebuilds them on next use)
         from . import conv
@@ -295,12 +399,31 @@ class Trainer:
     """zero_grad -> forward -> backward (+ overlapped all-reduce) -> fused SGD step -> LR step."""
 
     def __init__(self, model, lr=1e-2, momentum=0.9, weight_decay=5e-4, max_iter=40000, bucket_mb=32.0,
-                 loss_scale=None):
-        """loss_scale: static scale of the backward pass for float16 activations (the per-pixel CE gradient is
-        1/#pixels ~ 1e-7, below float16's normal range); default 65536 when cfg.MODEL.ACT_DTYPE is float16, else 1.
-        The scale enters through the gradient of the loss (the CE backward kernel multiplies by it) and leaves in the
-        fused SGD kernel's gradient scale, so parameters see exactly the unscaled step."""
+                 loss_scale=None, max_grad_norm=None):
+        """loss_scale: scale of the backward pass for float16 activations (the per-pixel CE gradient is 1/#pixels ~ 1e-7, below
+        float16's normal range).
+          None / a float, no max_grad_norm: a STATIC host-side scale, default 65536 when cfg.MODEL.ACT_DTYPE is float16, else 1.
+            It enters through the gradient of the loss (the CE backward kernel multiplies by it) and leaves in the fused SGD
+            kernel's gradient scale, so parameters see exactly the unscaled step.  Nothing looks at the gradient: an overflow
+            reaches the parameters.
+          "dynamic": a default LossScaler -- the scale lives on the device, a step whose gradient arena holds an inf / NaN is
+            skipped (parameters and momentum untouched, scale halved), 2000 clean steps in a row double the scale.
+          a LossScaler: that one (LossScaler(init_scale=s, dynamic=False): fixed scale, still skips non-finite steps -- what a
+            float together with max_grad_norm builds; use it for bf16 / fp32 runs).
+        max_grad_norm: clip_grad_norm_(parameters, max_grad_norm) of the unscaled, averaged gradient, folded into the step.
+        With a scaler no host value enters backward (it is seeded with scaler.scale_tensor) and no step waits for the host;
+        step_info() reads the device state back on request.  The poly schedule advances on skipped steps too, and the BatchNorm
+        running statistics of a skipped step are kept, as with stock AMP."""
         from .config import cfg
+        max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        if isinstance(loss_scale, str):
+            if loss_scale != "dynamic":
+                raise ValueError("loss_scale must be None, a number, 'dynamic' or a LossScaler, got %r" % (loss_scale,))
+        elif loss_scale is not None and not isinstance(loss_scale, LossScaler):
+            if isinstance(loss_scale, bool) or not isinstance(loss_scale, (int, float)):
+                raise ValueError("loss_scale must be None, a number, 'dynamic' or a LossScaler, got %r" % (loss_scale,))
+            if not (float(loss_scale) > 0.0) or math.isinf(float(loss_scale)):
+                raise ValueError("loss_scale must be positive and finite, got %r" % (loss_scale,))
         self.model = model
         self.opt = FlatSGD(model, lr, momentum, weight_decay, max_iter)
         self.sync = GradSync(self.opt, bucket_mb)
@@ -308,9 +431,19 @@ class Trainer:
         #  torch seeds -- also runs at world size 1: the rehearsal of every collective of the multi-GPU path on one GPU over RCCL)
         if dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get("MRFP_FORCE_SYNC") == "1"):
             sync_replicas(model, self.opt)
-        if loss_scale is None:
-            loss_scale = 65536.0 if cfg.MODEL.ACT_DTYPE == torch.float16 else 1.0
-        self.loss_scale = float(loss_scale)
+        self.scaler, self.max_grad_norm = None, max_grad_norm
+        dev = self.opt.flat_p.device
+        if isinstance(loss_scale, LossScaler):
+            self.scaler = loss_scale.to(dev)
+        elif loss_scale == "dynamic":
+            self.scaler = LossScaler(device=dev)
+        if loss_scale is None or self.scaler is not None:
+            static = 65536.0 if cfg.MODEL.ACT_DTYPE == torch.float16 else 1.0
+        else:
+            static = float(loss_scale)
+        if self.scaler is None and max_grad_norm is not None:
+            self.scaler = LossScaler(init_scale=static, dynamic=False, device=dev)
+        self.loss_scale = static if self.scaler is None else None        # the host-side scale of the unchecked path
         self.graph = False
 
     def _fwd_bwd(self, img, label):
@@ -320,7 +453,9 @@ class Trainer:
         ok = False
         try:
             loss = self.model(img, label, training=True)
-            if self.loss_scale != 1.0:
+            if self.scaler is not None:
+                loss.backward(self.scaler.scale_tensor)      # a device address: a replayed graph reads the scale of its own step
+            elif self.loss_scale != 1.0:
                 loss.backward(torch.full_like(loss, self.loss_scale))
             else:
                 loss.backward()
@@ -330,6 +465,21 @@ class Trainer:
                 conv.backward_failed()
         return loss
 
+    def _opt_step(self, gscale):
+        """After GradSync.finish(): every rank holds the same all-reduced arena, so with a scaler every rank's check decides from
+        identical bits and the loss scales stay in lockstep without a collective."""
+        if self.scaler is None:
+            self.opt.step(gscale / self.loss_scale)
+        else:
+            self.opt.step(gscale, scaler=self.scaler, max_grad_norm=self.max_grad_norm)
+
+    def step_info(self):
+        """LossScaler.info() of this trainer's scaler (scale, growth_tracker, found_inf, grad_norm, gmul, taken, skipped): one
+        device -> host copy, on request only."""
+        if self.scaler is None:
+            raise _lib.MrfpHipError("step_info: this Trainer has no LossScaler (loss_scale='dynamic' or a LossScaler)")
+        return self.scaler.info()
+
     def step(self, img, label):
         if self.graph:
             return self._graph_step(img, label)
@@ -337,7 +487,7 @@ class Trainer:
         gscale = self.sync.finish()
         from . import conv, ops
         conv.join_wgrad_stream()                       # weight gradients are computed on a second stream
-        self.opt.step(gscale / self.loss_scale)
+        self._opt_step(gscale)
         if ops._SYNC_BN_FLAG:                          # cfg.MODEL.SYNC_BN over several ranks: the device-side count check (no host wait)
             ops.sync_bn_poll()
         return loss
@@ -386,7 +536,7 @@ class Trainer:
                 torch.cuda.current_stream().wait_stream(side)
                 from . import conv
                 conv.join_wgrad_stream()
-                self.opt.step(1.0 / self.loss_scale)
+                self._opt_step(1.0)
                 conv.prebuild_repack_tables()            # (job tables of the batched re-packs: no host -> device copy inside the capture)
                 # capture on the warm-up's stream, with the warm-up's autograd graph gone (.detach() above): a gradient
                 # accumulator that remembers another stream makes autograd fork / join the capture once per parameter, and
@@ -413,7 +563,7 @@ class Trainer:
         for m in self._bns:
             if m.training and m.num_batches_tracked is not None:
                 m._nbt_pending += 1
-        self.opt.step(1.0 / self.loss_scale)
+        self._opt_step(1.0)
         return static_loss
 
 
@@ -625,13 +775,16 @@ def save_checkpoint(path, model, epoch, optimizer=None):
     if optimizer is not None:
         opt = getattr(optimizer, "opt", optimizer)                  # Trainer -> its FlatSGD
         ck["optimizer"] = opt.state_dict() if hasattr(opt, "state_dict") else opt
+        if getattr(optimizer, "scaler", None) is not None:          # a Trainer with a LossScaler: GradScaler's dict of plain numbers
+            ck["scaler"] = optimizer.scaler.state_dict()
     torch.save(ck, path)
 
 
 def load_checkpoint(path_or_dict, model, strict=True, optimizer=None, trust_pickle=False):
     """Loads a reference checkpoint (keys with or without the `module.` prefix) into the HIP model and, when
     `optimizer` (FlatSGD / Trainer) is given and the checkpoint has an 'optimizer' entry, the momentum buffers and the
-    schedule position (reference main.py:884-886 + the 'optimizer' entry of main.py:867).  The reference's format
+    schedule position (reference main.py:884-886 + the 'optimizer' entry of main.py:867); a 'scaler' entry is restored when
+    `optimizer` is a Trainer with a LossScaler, and files without one load as before.  The reference's format
     ({'epoch', 'state_dict', 'optimizer'} of tensors, numbers, lists and dicts) loads under torch's safe unpickler;
     `trust_pickle=True` opts into arbitrary pickles for files of known origin only."""
     ck = (torch.load(path_or_dict, map_location="cpu", weights_only=not trust_pickle)
@@ -644,4 +797,6 @@ def load_checkpoint(path_or_dict, model, strict=True, optimizer=None, trust_pick
     conv.invalidate_packs()
     if optimizer is not None and isinstance(ck, dict) and ck.get("optimizer") is not None:
         getattr(optimizer, "opt", optimizer).load_state_dict(ck["optimizer"])
+    if getattr(optimizer, "scaler", None) is not None and isinstance(ck, dict) and ck.get("scaler") is not None:
+        optimizer.scaler.load_state_dict(ck["scaler"])
     return ck.get("epoch", None) if isinstance(ck, dict) else None, missing
