@@ -16,8 +16,9 @@ test_cross_entropy_and_hist / test_fused_upsample_cross_entropy), all relative t
 
 ReLU gates.  A float64 reference and an fp32 kernel may disagree about the sign of a pre-activation that lies within fp32 rounding
 of zero; one such element moves its input gradient and its channel's weight gradient by percents.  Like a tie inside a max-pool
-window this is a property of the input, not of the kernel: settle() moves the (few per million) input values whose float64
-pre-activation is closer to the gate than BAND x the magnitude of its terms, and the tests assert that none is left.
+window this is a property of the input, not of the kernel: settle() (tests/rounding_model_common.py, shared with
+test_ops_16bit_gpu.py) moves the (few per million) input values whose float64 pre-activation is closer to the gate than BAND x the
+magnitude of its terms, and the tests assert that none is left.
 
 Second assertion where an output line does not depend on which workgroup wrote it (bilinear, max pool, add / ReLU, the apply pass
 of an eval-mode BatchNorm): the batched call is BIT-IDENTICAL to the same tensor run image by image -- at B = 1 every shape here
@@ -26,8 +27,6 @@ gives one line per workgroup.
 Bounds that were measured instead of inherited: BILINEAR_F32_Y below (the fp32 bilinear resize along lines of 700 pixels), nothing
 else.
 """
-import math
-
 import numpy as np
 import pytest
 import torch
@@ -35,6 +34,7 @@ import torch.nn.functional as F
 
 import eval_tta_common as etc
 import launch_geometry_common as lg
+from rounding_model_common import no_tie_planes, norm_pre, settle, window_max_count
 from oracle import mrfp_oracle as orc
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(lg.row_blocks_overridden(), reason=lg.SKIP_REASON)]
@@ -42,7 +42,6 @@ DEV = "cuda:0"
 CL = torch.channels_last
 F32, BF16, F16 = lg.F32, lg.BF16, lg.F16
 EPS = 1e-5
-BAND = 4e-6          # 16 x the fp32 error of x*A + S (+ res) with rounded coefficients (4 roundings of 2^-24 each), relative to its terms
 
 
 def ops():
@@ -82,37 +81,6 @@ def leaf64(*ts):
 
 def dname(dtype):
     return str(dtype).replace("torch.", "")
-
-
-def settle(x, dtype, pre, tries=16):
-    """x with no ReLU pre-activation within BAND of its gate.  pre(x float64) -> [(distance to the gate, magnitude of the terms)]."""
-    for _ in range(tries):
-        near = None
-        for z, mag in pre(x.double()):
-            n = z.abs() <= BAND * mag
-            near = n if near is None else (near | n)
-        if not bool(near.any()):
-            return x
-        x = torch.where(near, x + x.abs().clamp_min(1.0) * 2.0 ** -5, x).to(dtype).float()
-    raise AssertionError("could not move the inputs away from the ReLU gate")
-
-
-def norm_pre(w, b, res, dims, gates=(0.0,), stats=None):
-    """The pre-activation (x - m) * w / sqrt(v + eps) + b + res of a normalisation over `dims` as the kernels evaluate it, x*A + S
-    + res with A = w / sqrt(v + eps), S = b - m*A: (distance to each gate, |x*A| + |m*A| + |b| + |res| + |gate|)."""
-    def pre(x):
-        if stats is None:
-            m, v = x.mean(dims, keepdim=True), x.var(dims, unbiased=False, keepdim=True)
-        else:
-            m, v = (s.double().view(1, -1, 1, 1) for s in stats)
-        wv = w.double().view(1, -1, 1, 1) if w is not None else 1.0
-        bv = b.double().view(1, -1, 1, 1) if b is not None else torch.zeros(())
-        a = wv / (v + EPS).sqrt()
-        r = res.double() if res is not None else torch.zeros(())
-        z = (x - m) * a + bv + r
-        mag = (x * a).abs() + (m * a).abs() + bv.abs() + r.abs()
-        return [(z - g, mag + abs(g)) for g in gates]
-    return pre
 
 
 def hooked(fn):
@@ -467,26 +435,6 @@ def test_bilinear_many_lines(name, dtype):
             for u, v in zip(*outs):
                 assert torch.equal(u, v)
             assert relerr(outs[0][0][:, 16:], y64) < t
-
-
-def no_tie_planes(shape, seed):
-    """Max-pool inputs without ties inside any 3x3 window, exactly representable in bf16 / fp16 / fp32: pixel (h, w) of a plane
-    holds 16 * P[(h % 3, w % 3)] + n - 72 with P a per-plane permutation of 0..8 and n a random integer of 0..15 -- a window holds
-    every residue class at most once, classes differ by at least 16 > n, and all values are integers of magnitude < 128."""
-    B, C, H, W = shape
-    g = torch.Generator().manual_seed(seed)
-    perm = torch.rand(B, C, 9, generator=g).argsort(-1)
-    cls = (torch.arange(H).view(H, 1) % 3) * 3 + (torch.arange(W).view(1, W) % 3)
-    base = torch.gather(perm, 2, cls.flatten().expand(B, C, H * W)).view(B, C, H, W)
-    return (16 * base + torch.randint(0, 16, (B, C, H, W), generator=g) - 72).float()
-
-
-def window_max_count(z):
-    """How often each 3x3 / stride 2 / pad 1 window of z attains its maximum -> (count, maximum)."""
-    zp = F.pad(z, (1, 1, 1, 1), value=-math.inf)
-    win = zp.unfold(2, 3, 2).unfold(3, 3, 2)                      # [B, C, Ho, Wo, 3, 3]
-    mx = win.amax((-1, -2))
-    return (win == mx[..., None, None]).sum((-1, -2)), mx
 
 
 POOL_CASES = [(n, d) for n in lg.POOL_SHAPES for d in (F32, BF16)] + [("c8", F16)]
