@@ -260,6 +260,61 @@ int mrfp_upsample_ce_w_bwd(const void* P, int64_t ld, const int64_t* target, con
 int mrfp_label_class_weights(const int64_t* target, int64_t B, int64_t HW, int64_t C, double upper_bound, int norm,
                              int batch, int64_t* counts_ws, float* weight_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Boundary label relaxation and the joint-weighted soft-NLL loss (csrc/relax.hip).  Replaces the reference's
+ * transforms/transforms.py:75-124 RelaxedBoundaryLossToTensor (config.py:56-64 BATCH_WEIGHTING, BORDER_WINDOW,
+ * STRICTBORDERCLASS; utils/misc.py:51 `jointwtborder`) and the criterion that consumes its output, handed to DeepV3Plus as
+ * `criterion` / `criterion_aux` (network/deepv3.py:111; its source is not in the reference tree).  Build-defined, DESIGN.md
+ * section 8:
+ *
+ * C = number of classes, 1 <= C <= 31.  A label is a class if it lies in [0, C); every other value (255, -1, C, ...) is ignore.
+ * Relaxed target R[b,y,x] (32-bit word, stored as int32) for border r, 0 <= r <= 8: the OR over the window |dy| <= r, |dx| <= r of
+ * 1 << t(y+dy, x+dx), t = the label if it is a class, else C; positions outside the image give 1 << C (the reference's
+ * cval = num_classes).  Bit c: class c occurs in the window; bit C: ignore / outside the image occurs.
+ * strict_mask (STRICTBORDERCLASS as a bit mask): a pixel whose own label is a class in the mask gets 1 << label only.
+ * The reference's scipy.ndimage.shift at integer offsets is read as a pure translation with constant fill
+ * (tests/test_relaxed_cpu.py pins it); its REDUCE_BORDER_ITER branch is not built (a caller passes border / 2).
+ *
+ * counts (optional, int64 [B][C+1], cleared by the entry): n[b][c] = number of pixels of image b with bit c set, exact.
+ * Class weights: f_c = n_c / sum_{c=0..C} n_c (the ignore plane counts in the total);
+ *     norm == 0:  w_c = 1 + upper_bound * (1 - f_c)        norm != 0:  w_c = 1 + upper_bound / f_c        n_c == 0:  w_c = 1
+ * in double, rounded once to float; batch != 0 pools the images into one row.  weight_out: float [B][C] ([C] if batch).
+ *
+ * Loss: S_i = R_i & ((1 << C) - 1); pixel i of image b is valid iff S_i is not empty; k_i = popcount(S_i), W_i = sum_{c in S_i} w_b[c]
+ * (weight rows as mrfp_ce_w_fwd: wstride 0 or C, NULL = ones), lse_A(z) = log sum_{c in A} exp(z_c):
+ *     l_i = (W_i / k_i) * (lse_all(z_i) - lse_{S_i}(z_i))          ( = -(W_i / k_i) log sum_{c in S_i} softmax(z_i)_c, the published
+ *     L   = sum_b ( sum_{i in b, valid} l_i ) / (valid_b + 1)         per-class term log max(p_c, q_i) being log q_i on the set )
+ * computed from the two log-sum-exps, each around its own maximum: a confident wrong pixel gives a finite loss and gradient.  The
+ * + 1 is the published denominator: an all-ignored image contributes 0.
+ * ws: float [2 * mrfp_soft_nll_nblocks(B, HW)]; loss: float [mrfp_soft_nll_loss_floats(B)]: loss[0] = L, loss[1 + b] = valid_b + 1.
+ * Partials are per workgroup and reduced in double in a fixed order: two runs are bit-identical.
+ * bwd: dz_c = gscale[0] * (W_i / k_i) / (valid_b + 1) * ( softmax(z_i)_c - [c in S_i] exp(z_c - lse_{S_i}) ); ignored pixels and pad
+ * channels are zeros.  The upsample form works on the channel-padded low-resolution scores P[B,Hi,Wi,ld] and writes
+ * d(logits)[B,H,W,Cd] (Cd = C rounded up to a 16-byte chunk) for mrfp_bilinear_bwd, exactly as mrfp_upsample_ce_w_bwd.
+ * ------------------------------------------------------------------------------------------- */
+int64_t mrfp_relax_nblocks(int64_t B, int64_t H, int64_t W);       /* workgroups of mrfp_relax_labels: one per 32 x 64 tile, capped */
+int mrfp_relax_labels(const int64_t* target, int64_t B, int64_t H, int64_t W, int64_t C, int64_t border, int strict_mask,
+                      int32_t* words, int64_t* counts, void* stream);
+/* multihot: uint8 [B][C+1][HW], what the reference's transform emits; any non-zero byte is a set bit. */
+int mrfp_multihot_pack(const uint8_t* multihot, int64_t B, int64_t HW, int64_t C, int32_t* words, int64_t* counts,
+                       void* stream);
+/* the counts of words that exist already */
+int mrfp_relax_word_counts(const int32_t* words, int64_t B, int64_t HW, int64_t C, int64_t* counts, void* stream);
+int mrfp_relax_class_weights(const int64_t* counts, int64_t B, int64_t C, double upper_bound, int norm, int batch,
+                             float* weight_out, void* stream);
+int64_t mrfp_soft_nll_nblocks(int64_t B, int64_t HW);
+int64_t mrfp_soft_nll_loss_floats(int64_t B);
+int mrfp_soft_nll_fwd(const void* logits, const int32_t* words, int dtype, int64_t B, int64_t HW, int64_t C,
+                      const float* weight, int64_t wstride, float* ws, float* loss, void* stream);
+int mrfp_soft_nll_bwd(const void* logits, const int32_t* words, const float* loss, const float* gscale, void* dlogits,
+                      int dtype, int64_t B, int64_t HW, int64_t C, const float* weight, int64_t wstride, void* stream);
+int mrfp_upsample_soft_nll_fwd(const void* P, int64_t ld, const int32_t* words, int dtype, int64_t B, int64_t Hi, int64_t Wi,
+                               int64_t H, int64_t W, int64_t C, const float* weight, int64_t wstride, float* ws, float* loss,
+                               void* stream);
+int mrfp_upsample_soft_nll_bwd(const void* P, int64_t ld, const int32_t* words, const float* loss, const float* gscale,
+                               void* dlogits, int64_t Cd, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
+                               int64_t C, const float* weight, int64_t wstride, void* stream);
+
 /* Eval: argmax over classes + 19x19 confusion histogram on the device (reference main.py:898-909,
  * metrics.py:122-126): hist[num_classes*gt + pred] += 1 for gt in [0,num_classes).  hist: int64
  * [C*C], accumulated (not cleared).  pred (optional, uint8 [npix]) receives the arg-max. */

@@ -42,6 +42,12 @@ class AttrDict(dict):
 cfg = AttrDict()
 cfg.ITER = 0
 cfg.EPOCH = 0
+# boundary label relaxation (reference config.py:55-64; input_pipeline.RelaxedBoundaryTarget and loss.ImgWtLossSoftNLL read them):
+# class weights from the whole batch instead of per image; half-width of the relaxation window; class ids that are not relaxed.
+# The reference's REDUCE_BORDER_ITER branch is not built: a caller passes BORDER_WINDOW // 2 itself.
+cfg.BATCH_WEIGHTING = False
+cfg.BORDER_WINDOW = 1
+cfg.STRICTBORDERCLASS = None
 cfg.MODEL = AttrDict()
 cfg.MODEL.BN = "hip-batchnorm"
 # set lazily by network.mynn (the HIP BatchNorm2d subclass); the reference default is
@@ -77,5 +83,10 @@ def assert_and_infer_cfg(args=None, make_immutable=True, train_mode=True):
     semantics."""
     if args is not None and getattr(args, "syncbn", False):
         cfg.MODEL.SYNC_BN = True
+    if args is not None and train_mode:          # reference config.py:118-123
+        if getattr(args, "batch_weighting", False):
+            cfg.BATCH_WEIGHTING = True
+        if getattr(args, "jointwtborder", False) and getattr(args, "strict_bdr_cls", "") != "":
+            cfg.STRICTBORDERCLASS = [int(i) for i in args.strict_bdr_cls.split(",")]
     if make_immutable:
         cfg.immutable(True)

@@ -761,6 +761,36 @@ def _to_int64(lab_u8: torch.Tensor, table: Optional[torch.Tensor], out: Optional
     return out
 
 
+class RelaxedBoundaryTarget:
+    """The reference's RelaxedBoundaryLossToTensor (transforms/transforms.py:75-124) on the device: an int64 label map [H,W] or
+    [B,H,W] -> the relaxed target as int32 words of the same shape (csrc/relax.hip, mrfp_relax_labels): bit c =
+    class c occurs within `border` pixels, bit num_classes = ignore or the outside of the image does.  border / strict_classes None:
+    cfg.BORDER_WINDOW / cfg.STRICTBORDERCLASS, read at call time as the reference's transform reads them.  The reference's
+    REDUCE_BORDER_ITER branch is not built.  to_multihot(words) gives the reference's uint8 [C+1,H,W] layout."""
+
+    def __init__(self, num_classes, ignore_id=255, border=None, strict_classes=None):
+        self.num_classes, self.ignore_id = int(num_classes), int(ignore_id)
+        if 0 <= self.ignore_id < self.num_classes:
+            raise ValueError("RelaxedBoundaryTarget: ignore_id %d is a class of 0..%d" % (self.ignore_id, self.num_classes - 1))
+        self.border, self.strict_classes = border, strict_classes
+
+    def __call__(self, label: torch.Tensor) -> torch.Tensor:
+        from . import ops
+        from .config import cfg
+        border = cfg.BORDER_WINDOW if self.border is None else self.border
+        strict = cfg.STRICTBORDERCLASS if self.strict_classes is None else self.strict_classes
+        if not (isinstance(label, torch.Tensor) and label.dim() in (2, 3)):
+            raise _lib.MrfpHipError("RelaxedBoundaryTarget: an int64 label map [H,W] or [B,H,W] expected")
+        words = ops.relax_labels(label if label.dim() == 3 else label.unsqueeze(0), self.num_classes, border, strict)
+        return words if label.dim() == 3 else words[0]
+
+    def to_multihot(self, words: torch.Tensor) -> torch.Tensor:
+        """int32 words [H,W] / [B,H,W] -> uint8 [C+1,H,W] / [B,C+1,H,W], plane c = bit c (for callers that want the reference's bytes;
+        the loss takes the words)."""
+        bits = torch.arange(self.num_classes + 1, dtype=torch.int32, device=words.device).view(-1, 1, 1)
+        return ((words.unsqueeze(-3) >> bits) & 1).to(torch.uint8)
+
+
 # Label ids of the 19 evaluation classes, in train-id order (road, sidewalk, building, wall, fence, pole, traffic light, traffic
 # sign, vegetation, terrain, sky, person, rider, car, truck, bus, train, motorcycle, bicycle), per label set.
 _CITYSCAPES_IDS = (7, 8, 11, 12, 13, 17, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 31, 32, 33)      # Cityscapes labelIds; GTAV shares them

@@ -6,14 +6,21 @@ ImageBasedCrossEntropyLoss2d is the per-image class-weighted loss the DeepLabV3+
 trained with.  Its source is not in the reference tree: the rule stated in ops.label_class_weights is the definition here
 (build-defined).  The published form copies the label map to the host every step for np.histogram; here the
 histogram, the weights and the loss stay on the device, with no synchronisation.
+
+ImgWtLossSoftNLL is the joint-weighted soft-NLL loss of that baseline, the criterion that consumes the relaxed boundary targets of
+the reference's transforms/transforms.py:75-124 (`jointwtborder`, utils/misc.py:51).  Its source is not in the reference tree
+either: include/mrfp_hip.h and DESIGN.md section 8 hold the definition.  The published form builds a [B, C+1, H, W] uint8 multi-hot on
+the host and copies it back every step for the class histogram; here a relaxed target is one int32 word per pixel (ops.relax_labels),
+and relaxation, histogram, weights and loss are device kernels (csrc/relax.hip).
 """
 from __future__ import annotations
 
+import torch
 from torch import nn
 
 from . import ops
 
-__all__ = ["ImageBasedCrossEntropyLoss2d", "fused_ce_kwargs", "fused_loss"]
+__all__ = ["ImageBasedCrossEntropyLoss2d", "ImgWtLossSoftNLL", "fused_ce_kwargs", "fused_loss"]
 
 
 class ImageBasedCrossEntropyLoss2d(nn.Module):
@@ -40,11 +47,60 @@ class ImageBasedCrossEntropyLoss2d(nn.Module):
         return ops.cross_entropy(inputs, targets, self.ignore_index, weight=self.class_weights(targets), per_image=True)
 
 
+class ImgWtLossSoftNLL(nn.Module):
+    """sum over the images of sum_valid (W_i / k_i) (-log sum_{c in set_i} softmax_c) / (valid_b + 1), the class weights w from the
+    relaxed target's own per-image bit counts (batch_weights: from the whole batch's).  The target is an int64 [B,H,W] label map
+    (relaxed here with `border` / `strict_classes`), int32 [B,H,W] words (ops.relax_labels, input_pipeline.RelaxedBoundaryTarget) or
+    the reference's uint8 [B, C+1, H, W] multi-hot."""
+
+    def __init__(self, classes, ignore_index=255, weights=None, upper_bound=1.0, norm=False, batch_weights=False, border=1,
+                 strict_classes=None):
+        super().__init__()
+        if weights is not None:
+            raise ValueError("ImgWtLossSoftNLL computes its class weights from the relaxed target on every call (the original "
+                             "overwrites a fixed weight): weights must be None")
+        self.num_classes, self.border = ops._relax_args("ImgWtLossSoftNLL", classes, border)
+        self.strict_classes = None if strict_classes is None else [int(c) for c in strict_classes]
+        ops.strict_class_mask(self.strict_classes, self.num_classes)
+        self.ignore_index = int(ignore_index)        # documentation only: every label outside 0..classes-1 is ignore
+        self.upper_bound = float(upper_bound)
+        self.norm = bool(norm)
+        self.batch_weights = bool(batch_weights)
+
+    def relaxed(self, target):
+        """(int32 [B,H,W] words, int64 [B, C+1] counts) of a target in any of the three forms."""
+        if target.dtype == torch.int32 and target.dim() == 3:
+            return target, ops.relaxed_counts(target, self.num_classes)
+        if target.dtype == torch.uint8 and target.dim() == 4:
+            if target.shape[1] != self.num_classes + 1:
+                raise ValueError("ImgWtLossSoftNLL: a multi-hot target has classes + 1 = %d planes (got %d)" % (
+                    self.num_classes + 1, target.shape[1]))
+            return ops.pack_multihot(target, want_counts=True)
+        if target.dtype == torch.int64 and target.dim() == 3:
+            return ops.relax_labels(target, self.num_classes, self.border, self.strict_classes, want_counts=True)
+        raise ValueError("ImgWtLossSoftNLL: the target is an int64 [B,H,W] label map, int32 [B,H,W] words or a uint8 [B,C+1,H,W] "
+                         "multi-hot (got %s %s)" % (target.dtype, tuple(target.shape)))
+
+    def fused(self, logits, target, size=None, channels=None):
+        """The loss on the kernels: of dense logits, or with `size` of the channel-padded low-resolution scores."""
+        words, counts = self.relaxed(target)
+        w = ops.relaxed_class_weights(counts, self.upper_bound, self.norm, self.batch_weights)
+        if size is not None:
+            return ops.upsample_soft_nll(logits, words, size, channels, weight=w)
+        return ops.soft_nll(logits, words, self.num_classes, weight=w)
+
+    def forward(self, inputs, target):
+        return self.fused(inputs, target)
+
+
 def fused_ce_kwargs(criterion):
     """The keyword arguments with which ops.cross_entropy / ops.upsample_cross_entropy compute `criterion`, or None for a criterion
     they cannot (reduction='none', a foreign module): that one keeps the stock call on the full-resolution fp32 logits.  `weight` is
-    a tensor, None, or -- for the per-image criterion -- a callable of the label map (fused_loss calls it)."""
+    a tensor, None, or -- for the per-image criterion -- a callable of the label map (fused_loss calls it).  ImgWtLossSoftNLL is not a
+    cross entropy: its entry is dict(soft_nll=<its own fused call>), which fused_loss calls with (logits, gts, size, channels)."""
     c = criterion
+    if isinstance(c, ImgWtLossSoftNLL):          # not a cross entropy: fused_loss hands the call to the criterion's own kernels
+        return dict(soft_nll=c.fused)
     if isinstance(c, ImageBasedCrossEntropyLoss2d):
         return dict(ignore_index=c.ignore_index, weight=c.class_weights, label_smoothing=0.0, reduction="mean", per_image=True)
     if isinstance(c, nn.CrossEntropyLoss) and c.reduction in ("mean", "sum"):
@@ -59,6 +115,8 @@ def fused_loss(criterion, logits, gts, size=None, channels=None):
     kw = fused_ce_kwargs(criterion)
     if kw is None:
         return None
+    if "soft_nll" in kw:
+        return kw["soft_nll"](logits, gts, size, channels)
     ignore = kw.pop("ignore_index")
     if callable(kw["weight"]):
         kw["weight"] = kw["weight"](gts)

@@ -23,7 +23,7 @@ from .. import ops
 from ..config import cfg
 from ..conv import wgrad_boundary
 from ..deepv3 import _AtrousSpatialPyramidPoolingModule, _ConvBnRelu, _DeepLabBase
-from ..loss import fused_loss
+from ..loss import ImgWtLossSoftNLL, fused_loss
 from . import Mobilenet, Resnet
 from .mynn import HipConv2d, Norm2d, freeze_weights, initialize_weights, unfreeze_weights  # noqa: F401
 from .wider_resnet import HipDropout2d
@@ -170,7 +170,9 @@ class DeepV3Plus(_DeepLabBase):
         # F.interpolate(mode='nearest') of the label map: ATen's float32 source-index rule, as the activations' nearest resizes use
         th = torch.as_tensor(ops._nearest_table(Hs, h, None), dtype=torch.long, device=aux_gts.device)
         tw = torch.as_tensor(ops._nearest_table(Ws, w, None), dtype=torch.long, device=aux_gts.device)
-        aux_gts = aux_gts.long().index_select(1, th).index_select(2, tw).contiguous()
+        if not (isinstance(self.criterion_aux, ImgWtLossSoftNLL) and aux_gts.dtype in (torch.int32, torch.uint8)):
+            aux_gts = aux_gts.long()          # a label map; relaxed words [B,H,W] and multi-hot planes [B,C+1,H,W] keep their type
+        aux_gts = aux_gts.index_select(-2, th).index_select(-1, tw).contiguous()
         loss = fused_loss(self.criterion_aux, aux_out, aux_gts)
         if loss is None:
             loss = self.criterion_aux(aux_out.float(), aux_gts)

@@ -1165,6 +1165,167 @@ def label_class_weights(target, num_classes, upper_bound=1.0, norm=False, batch=
     return out
 
 
+# ---- boundary label relaxation and the joint-weighted soft-NLL loss (csrc/relax.hip; include/mrfp_hip.h and DESIGN.md section 8
+# hold the definitions): the relaxed target of a pixel is one int32 word, bit c = class c occurs in its window, bit C = ignore ----
+RELAX_MAX_CLASSES, RELAX_MAX_BORDER = 31, 8
+
+
+def strict_class_mask(strict_classes, num_classes):
+    """STRICTBORDERCLASS (None or a list of class ids, reference config.py:64) as the bit mask the kernel takes."""
+    mask = 0
+    for c in strict_classes or ():
+        c = int(c)
+        if not 0 <= c < num_classes:
+            raise _lib.MrfpHipError("strict_classes: %d is not a class of 0..%d" % (c, num_classes - 1))
+        mask |= 1 << c
+    return mask
+
+
+def _relax_args(who, num_classes, border=0):
+    C, r = int(num_classes), int(border)
+    if not 1 <= C <= RELAX_MAX_CLASSES:
+        raise _lib.MrfpHipError("%s: 1 <= num_classes <= %d: the classes and the ignore bit share one 32-bit word (got %d)" % (
+            who, RELAX_MAX_CLASSES, C))
+    if not 0 <= r <= RELAX_MAX_BORDER:
+        raise _lib.MrfpHipError("%s: 0 <= border <= %d (got %d)" % (who, RELAX_MAX_BORDER, r))
+    return C, r
+
+
+def _chk_target(who, t, dtype, dims):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.MrfpHipError("%s: the target must be a GPU tensor: the HIP path has no CPU fallback" % who)
+    if t.dtype != dtype or t.dim() != dims:
+        raise _lib.MrfpHipError("%s: expected a %d-dimensional %s tensor (got %s %s)" % (who, dims, dtype, t.dtype, tuple(t.shape)))
+    return t.contiguous()
+
+
+def relax_labels(target, num_classes, border=1, strict_classes=None, want_counts=False):
+    """int64 [B,H,W] label map -> int32 [B,H,W] relaxed words (reference transforms/transforms.py:91-118), and with want_counts the
+    int64 [B, C+1] number of pixels per image that carry each bit."""
+    C, r = _relax_args("relax_labels", num_classes, border)
+    mask = strict_class_mask(strict_classes, C)
+    target = _chk_target("relax_labels", target, torch.int64, 3)
+    B, H, W = target.shape
+    words = torch.empty(B, H, W, dtype=torch.int32, device=target.device)
+    counts = torch.empty(B, C + 1, dtype=torch.int64, device=target.device) if want_counts else None
+    call("mrfp_relax_labels", ptr(target), B, H, W, C, r, mask, ptr(words), ptr(counts), stream())
+    return (words, counts) if want_counts else words
+
+
+def pack_multihot(onehot_u8, want_counts=False):
+    """uint8 [B, C+1, H, W] multi-hot (what the reference's transform emits; any non-zero byte is set) -> int32 [B,H,W] words."""
+    m = _chk_target("pack_multihot", onehot_u8, torch.uint8, 4)
+    B, C1, H, W = m.shape
+    C, _ = _relax_args("pack_multihot", C1 - 1)
+    words = torch.empty(B, H, W, dtype=torch.int32, device=m.device)
+    counts = torch.empty(B, C + 1, dtype=torch.int64, device=m.device) if want_counts else None
+    call("mrfp_multihot_pack", ptr(m), B, H * W, C, ptr(words), ptr(counts), stream())
+    return (words, counts) if want_counts else words
+
+
+def relaxed_counts(words, num_classes):
+    """int32 [B,H,W] words -> int64 [B, C+1] pixels per image with each bit set."""
+    C, _ = _relax_args("relaxed_counts", num_classes)
+    words = _chk_target("relaxed_counts", words, torch.int32, 3)
+    B, H, W = words.shape
+    counts = torch.empty(B, C + 1, dtype=torch.int64, device=words.device)
+    call("mrfp_relax_word_counts", ptr(words), B, H * W, C, ptr(counts), stream())
+    return counts
+
+
+def relaxed_class_weights(counts, upper_bound=1.0, norm=False, batch=False):
+    """int64 [B, C+1] counts -> float32 [B, C] class weights, or [C] from the pooled counts of all images (batch): with
+    f_c = n_c / sum_{c=0..C} n_c, w_c = 1 + upper_bound * (1 - f_c) (norm: 1 + upper_bound / f_c) where n_c > 0, else 1."""
+    counts = _chk_target("relaxed_class_weights", counts, torch.int64, 2)
+    B, C1 = counts.shape
+    C, _ = _relax_args("relaxed_class_weights", C1 - 1)
+    out = torch.empty((C,) if batch else (B, C), dtype=torch.float32, device=counts.device)
+    call("mrfp_relax_class_weights", ptr(counts), B, C, float(upper_bound), int(bool(norm)), int(bool(batch)), ptr(out), stream())
+    return out
+
+
+def _soft_nll_options(who, relaxed, weight, B, H, W, C, device):
+    if not isinstance(relaxed, torch.Tensor) or relaxed.dtype != torch.int32 or tuple(relaxed.shape) != (B, H, W) \
+            or relaxed.device != device:
+        raise _lib.MrfpHipError("%s: the relaxed target must be int32 [B,H,W] words on %s (ops.relax_labels / ops.pack_multihot)" % (
+            who, device))
+    _relax_args(who, C)
+    weight, wstride, _, _ = _ce_options(who, weight, 0.0, "mean", False, B, C, device)
+    L = _lib.lib()
+    ws = torch.empty(2 * int(L.mrfp_soft_nll_nblocks(B, H * W)), dtype=torch.float32, device=device)
+    loss = torch.empty(int(L.mrfp_soft_nll_loss_floats(B)), dtype=torch.float32, device=device)
+    return relaxed.contiguous(), weight, wstride, ws, loss
+
+
+class _SoftNLL(torch.autograd.Function):
+    """The joint-weighted soft-NLL loss of relaxed targets on dense logits (mrfp_soft_nll_*)."""
+
+    @staticmethod
+    def forward(ctx, logits, relaxed, C, weight):
+        logits = _chk(logits, "logits")
+        B, Cl, H, W = logits.shape
+        if Cl != C:
+            raise _lib.MrfpHipError("soft_nll: logits have %d channels, num_classes is %d" % (Cl, C))
+        relaxed, weight, wstride, ws, loss = _soft_nll_options("soft_nll", relaxed, weight, B, H, W, C, logits.device)
+        call("mrfp_soft_nll_fwd", ptr(logits), ptr(relaxed), dt(logits), B, H * W, C, ptr(weight), wstride, ptr(ws), ptr(loss), stream())
+        ctx.save_for_backward(logits, relaxed, loss, weight)
+        ctx.wstride = wstride
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, relaxed, loss, weight = ctx.saved_tensors
+        B, C, H, W = logits.shape
+        gs = g.detach().float().reshape(1).contiguous()
+        d = torch.empty_like(logits, memory_format=CL)
+        call("mrfp_soft_nll_bwd", ptr(logits), ptr(relaxed), ptr(loss), ptr(gs), ptr(d), dt(logits), B, H * W, C, ptr(weight),
+             ctx.wstride, stream())
+        return d, None, None, None
+
+
+def soft_nll(logits, relaxed, num_classes, weight=None):
+    """logits [B,C,H,W]; relaxed: int32 [B,H,W] words; weight: float32 [C] (shared) or [B, C] (one row per image) on the device, None =
+    ones.  -> the sum over the images of sum_valid (W_i / k_i) (lse_all - lse_set) / (valid_b + 1), fp32 scalar."""
+    return _SoftNLL.apply(logits, relaxed, int(num_classes), weight)
+
+
+class _UpsampleSoftNLL(torch.autograd.Function):
+    """soft_nll(Upsample(P[:, :C], size), relaxed) without materialising the full-resolution logits (mrfp_upsample_soft_nll_*)."""
+
+    @staticmethod
+    def forward(ctx, P, relaxed, H, W, C, weight):
+        P = _chk(P, "P")
+        B, ld, Hi, Wi = P.shape
+        relaxed, weight, wstride, ws, loss = _soft_nll_options("upsample_soft_nll", relaxed, weight, B, H, W, C, P.device)
+        call("mrfp_upsample_soft_nll_fwd", ptr(P), ld, ptr(relaxed), dt(P), B, Hi, Wi, H, W, C, ptr(weight), wstride, ptr(ws), ptr(loss),
+             stream())
+        ctx.save_for_backward(P, relaxed, loss, weight)
+        ctx.cfg = (H, W, C, wstride)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        P, relaxed, loss, weight = ctx.saved_tensors
+        H, W, C, wstride = ctx.cfg
+        B, ld, Hi, Wi = P.shape
+        epc = 16 // P.element_size()
+        Cd = (C + epc - 1) // epc * epc
+        gs = g.detach().float().reshape(1).contiguous()
+        dP = empty_cl(B, ld, Hi, Wi, P.dtype, P.device)
+        dlog = empty_cl(B, Cd, H, W, P.dtype, P.device)
+        call("mrfp_upsample_soft_nll_bwd", ptr(P), ld, ptr(relaxed), ptr(loss), ptr(gs), ptr(dlog), Cd, dt(P), B, Hi, Wi, H, W, C,
+             ptr(weight), wstride, stream())
+        if ld != Cd:
+            dP.zero_()
+        call("mrfp_bilinear_bwd", ptr(dlog), ptr(dP), dt(P), B, Hi, Wi, H, W, Cd, ld, stream())
+        return dP, None, None, None, None, None
+
+
+def upsample_soft_nll(P, relaxed, size, channels, weight=None):
+    """P: channel-padded low-resolution class scores [B,ld,Hi,Wi] (ld a multiple of the 16-byte chunk); the rest as soft_nll."""
+    return _UpsampleSoftNLL.apply(P, relaxed, int(size[0]), int(size[1]), int(channels), weight)
+
+
 # ------------------------------------------------------------------------------------------
 # eval: arg-max + confusion histogram on the device
 # ------------------------------------------------------------------------------------------
