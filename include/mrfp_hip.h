@@ -692,6 +692,42 @@ int mrfp_prob_accum(const void* logits, int dtype, int64_t B, int64_t hs, int64_
 int mrfp_acc_argmax_hist(const float* acc, const float* cnt, const int64_t* target, int64_t npix, int64_t NC, int64_t* hist,
                          uint8_t* pred, int64_t* uncovered, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Prediction path (csrc/predict.hip): label maps, validation loss and colour images without the full-resolution logits.
+ * Replaces the reference's outputs = model(inputs) + np.argmax on the host + fast_hist (main.py:896-909), the val_loss its
+ * evaluation bookkeeping tracks beside mIoU (utils/misc.py:139-156) and decode_segmap / get_cityscapes_labels
+ * (utils_main.py:28-103); in this build, the chain mrfp_bilinear_fwd -> fp32 copy -> mrfp_argmax_hist.
+ *
+ * mrfp_upsample_argmax: P[B,Hi,Wi,ld] low-resolution class scores in `dtype`, NHWC, ld a multiple of the 16-byte chunk and at
+ * least C rounded up to one (what mrfp_upsample_ce_fwd accepts; pad channels and chunks past the class count are never read into
+ * the result), C <= 64.  For output pixel (b, y, x) of the H x W map:
+ *   z_c   the align_corners=True bilinear sample of class c in fp32 (the arithmetic of mrfp_bilinear_fwd), rounded to `dtype` and
+ *         widened again for the 16-bit types: the value mrfp_bilinear_fwd stores.  The predictions are therefore those of the
+ *         materialised chain, pixel for pixel, in every dtype.
+ *   pred  uint8 [B,H,W], optional: the first maximum of z (np.argmax's rule).
+ *   conf  fp32 [B,H,W], optional: 1 / sum_c exp(z_c - max z), the largest soft-max probability.
+ *   hist  int64, optional, needs target: hist[t*C + pred] += 1 for t = target[b,y,x] in 0..C-1; added to, never cleared.
+ *         per_image != 0: the layout is [B][C][C], one matrix per image.
+ *   loss  optional (loss_acc != NULL), needs target and ws: plain cross entropy on z; labels equal to ignore_index, < 0 or >= C
+ *         are ignored.  Every workgroup writes one (sum nll, count) fp32 partial into ws (2 * mrfp_upsample_argmax_nblocks(B, H, W)
+ *         floats); a one-workgroup kernel adds them in double, in a fixed order, ONTO loss_acc = double[2] (sum nll, valid
+ *         pixels) on the device, which the caller owns and clears.  No floating-point atomics: runs are bitwise reproducible.
+ *         The validation loss of a data set is loss_acc[0] / loss_acc[1] over all of its batches (build-defined: pixel-weighted;
+ *         no valid pixel gives NaN).
+ * Every output is optional on its own; none at all is refused.  Grid: (workgroups per image, B), at most 2048 workgroups;
+ * mrfp_upsample_argmax_nblocks returns their number.  All argument checks happen before any launch.
+ *
+ * mrfp_colorize_u8: pred uint8 [npix], palette uint8 [256][3] on the device, image uint8 [npix][3] or NULL, out uint8 [npix][3].
+ * image == NULL: out = palette[pred].  Otherwise out = (a * palette[pred] + (256 - a) * image + 128) >> 8 per byte in integer
+ * arithmetic, 0 <= a <= 256 (256: the palette colour, 0: the image).  No pointer needs an alignment (4-byte aligned ones move
+ * four pixels per lane); out must not overlap an input.
+ * ------------------------------------------------------------------------------------------- */
+int64_t mrfp_upsample_argmax_nblocks(int64_t B, int64_t H, int64_t W);
+int mrfp_upsample_argmax(const void* P, int64_t ld, const int64_t* target, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H,
+                         int64_t W, int64_t C, int64_t ignore_index, uint8_t* pred, float* conf, int64_t* hist, int per_image,
+                         float* ws, double* loss_acc, void* stream);
+int mrfp_colorize_u8(const void* pred, const void* palette, const void* image, void* out, int64_t npix, int a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ process per MI355X:
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import List, Optional
@@ -620,6 +621,100 @@ def evaluate(model, batches, num_classes=19, fold=False):
         dist.all_reduce(hist)
     h = hist.cpu().numpy() if hist is not None else None
     return h, (metrics.miou_from_hist(h) if h is not None else 0.0), dropped
+
+
+@contextlib.contextmanager
+def _eval_mode(model, fold):
+    """model.eval() for the length of a `with`, inside inference.fold_norms(model) when `fold`; the training flags of every module
+    are put back on the way out."""
+    flags = [(m, m.training) for m in model.modules()]
+    try:
+        with contextlib.ExitStack() as stack:
+            if fold:
+                from .inference import fold_norms
+                stack.enter_context(fold_norms(model))
+            model.eval()
+            yield
+    finally:
+        for m, f in flags:
+            m.training = f
+
+
+@torch.no_grad()
+def predict(model, images, fold=False, want_conf=False):
+    """Label maps of a trained model, a generator: per float32 [B,3,H,W] batch of `images` (as the evaluation transforms produce
+    them) ONE forward with low_res=True and ONE ops.upsample_argmax at the image's own size -> (pred uint8 [B,H,W], conf float32
+    [B,H,W] or None).  The prediction is np.argmax of model(img, training=False), pixel for pixel (reference main.py:896-900); the
+    full-resolution logits are never written.  conf: the largest soft-max probability.  Runs under torch.no_grad (the caller's grad
+    mode is untouched between two batches) with model.eval(); fold=True: inside inference.fold_norms(model).  The model stays in
+    eval() while the generator is being consumed; its training flags are restored when the generator ends or is closed."""
+    from . import ops
+    with _eval_mode(model, fold):
+        for img in images:
+            low = model(img, training=False, low_res=True)
+            r = ops.upsample_argmax(low, img.shape[2:], _num_classes(model, low), want_pred=True, want_conf=want_conf)
+            yield r.pred, r.conf
+
+
+def _num_classes(model, low):
+    nc = getattr(model, "num_classes", None)
+    if nc is None:
+        final2 = getattr(model, "final2", None)
+        nc = final2[0].out_channels if final2 is not None else None
+    if nc is None:
+        raise _lib.MrfpHipError("predict: cannot tell the class count of %s (no num_classes, no final2)" % type(model).__name__)
+    return int(nc)
+
+
+@torch.no_grad()
+def validate(model, batches, num_classes=19, fold=False, ignore_index=255, per_image=False):
+    """evaluate()'s loop on the fused kernel (ops.upsample_argmax): one forward with low_res=True per batch, then arg-max, confusion
+    histogram and the plain cross entropy in one launch -- the full-resolution logits are never written -- and ONE device -> host
+    copy at the end.  Same drop rule for size mismatches (reference main.py:894, 910-912), histograms (and the two loss
+    accumulators) summed over the data-parallel ranks as in evaluate(); `dropped` stays per rank.  -> dict:
+      hist, mean_iu, dropped   what evaluate() returns (hist None / mean_iu 0.0 when every batch was dropped)
+      val_loss                 sum nll / valid pixels over ALL batches, pixel-weighted (build-defined: the reference's evaluation
+                               bookkeeping, utils/misc.py:139-156, tracks a val_loss its eval loop never computes); NaN without a
+                               valid pixel
+      pixels                   the valid pixels (labels in 0..num_classes-1 other than ignore_index)
+      image_hists              int64 [N,C,C], one matrix per kept image in order (per_image only; per rank)"""
+    import numpy as np
+    from . import metrics, ops
+    C = int(num_classes)
+    dev = next(model.parameters()).device
+    hist = torch.zeros(C, C, dtype=torch.int64, device=dev)
+    loss_acc = torch.zeros(2, dtype=torch.float64, device=dev)
+    per, dropped, kept = [], 0, 0
+    with _eval_mode(model, fold):
+        for img, label in batches:
+            if img.shape[2:] != label.shape[1:]:        # reference main.py:894, 910-912
+                dropped += 1
+                continue
+            low = model(img, training=False, low_res=True)
+            if per_image:
+                r = ops.upsample_argmax(low, img.shape[2:], C, label, ignore_index, per_image=True, want_pred=False, loss_acc=loss_acc)
+                per.append(r.hist)
+            else:
+                ops.upsample_argmax(low, img.shape[2:], C, label, ignore_index, hist=hist, want_pred=False, loss_acc=loss_acc)
+            kept += 1
+    image_hists = None
+    if per_image:
+        image_hists = torch.cat(per) if per else torch.zeros(0, C, C, dtype=torch.int64, device=dev)
+        hist = image_hists.sum(0)
+    distributed = dist.is_initialized() and dist.get_world_size() > 1
+    if distributed:
+        dist.all_reduce(hist)                         # (a rank that dropped all of its batches still takes part, as in evaluate)
+        dist.all_reduce(loss_acc)
+    # one device -> host copy: the histogram, the two accumulators (their bits) and the per-image matrices in one int64 buffer
+    parts = [hist.reshape(-1), loss_acc.view(torch.int64)] + ([image_hists.reshape(-1)] if per_image else [])
+    host = torch.cat(parts).cpu().numpy()
+    h = host[:C * C].reshape(C, C).copy() if (kept or distributed) else None
+    nll, pixels = (float(v) for v in host[C * C:C * C + 2].view(np.float64))
+    out = {"hist": h, "mean_iu": metrics.miou_from_hist(h) if h is not None else 0.0, "dropped": dropped,
+           "val_loss": nll / pixels if pixels > 0 else float("nan"), "pixels": int(pixels)}
+    if per_image:
+        out["image_hists"] = host[C * C + 2:].reshape(-1, C, C).copy()
+    return out
 
 
 def eval_batches(samples, transform, encoder=None):

@@ -735,6 +735,21 @@ class LabelEncoder:
     def device_table(self, dev) -> torch.Tensor:
         return _cached(self._dev_tables, str(dev), lambda: _dev(dev, self.table.copy())[0])
 
+    def inverse(self, fill: int = 0) -> "LabelEncoder":
+        """The way back from train ids to the dataset's own ids, as a new LabelEncoder: inv[t] = the smallest id i with
+        table[i] == t, for every t != 255 some id maps to; every other entry (255 included) is `fill`.  For the Cityscapes preset:
+        0 -> 7, 1 -> 8, ... 18 -> 33, 255 -> fill.  Build-defined (the reference has no inverse); a many-to-one encoding such as
+        Mapillary's returns the smallest of the ids that share a train id."""
+        fill = int(fill)
+        if not 0 <= fill <= 255:
+            raise ValueError("LabelEncoder.inverse: fill must be in 0..255, got %r" % (fill,))
+        inv = np.full(256, fill, dtype=np.int64)
+        for i in range(255, -1, -1):                 # descending: the smallest id is written last
+            t = int(self.table[i])
+            if t != 255:
+                inv[t] = i
+        return LabelEncoder(inv)
+
     def _arg(self, name: str, lab_u8: torch.Tensor) -> torch.Tensor:
         if not (isinstance(lab_u8, torch.Tensor) and lab_u8.is_cuda and lab_u8.dtype == torch.uint8):
             raise _lib.MrfpHipError("LabelEncoder%s: a uint8 CUDA tensor expected (there is no CPU path)" % name)

@@ -8,6 +8,7 @@ an activation goes through a hand-written HIP kernel, and a missing library rais
 """
 from __future__ import annotations
 
+import collections
 import math
 import os
 import weakref
@@ -1402,6 +1403,110 @@ def acc_argmax_hist(acc, cnt, target, hist: Optional[torch.Tensor] = None, want_
     pred = torch.empty(B, H, W, dtype=torch.uint8, device=acc.device) if want_pred else None
     call("mrfp_acc_argmax_hist", ptr(acc), ptr(cnt), ptr(target), B * H * W, NC, ptr(hist), ptr(pred), ptr(uncovered), stream())
     return hist, pred
+
+
+# ------------------------------------------------------------------------------------------
+# prediction path: upsample + arg-max (+ histogram, confidence, validation loss) in one launch; colour coding
+# ------------------------------------------------------------------------------------------
+Prediction = collections.namedtuple("Prediction", ("pred", "conf", "hist", "loss_acc"))
+
+
+def upsample_argmax(P, size, channels, target=None, ignore_index=255, hist=None, per_image=False, want_pred=True, want_conf=False,
+                    loss_acc=None):
+    """arg-max over the classes of Upsample(P[:, :channels], size) without the full-resolution logits (mrfp_upsample_argmax,
+    include/mrfp_hip.h): the label map ops.argmax_hist(ops.upsample_bilinear(P, size, channels=channels).float(), ...) gives, pixel
+    for pixel.  P: channel-padded low-resolution class scores [B,ld,Hi,Wi] in NHWC storage (ld a multiple of the 16-byte chunk), as
+    model(x, training=False, low_res=True) returns them.  -> Prediction(pred, conf, hist, loss_acc); members not asked for are None.
+      pred      uint8 [B,H,W] (want_pred)
+      conf      float32 [B,H,W], the largest soft-max probability (want_conf)
+      hist      with `target` (int64 [B,H,W]): the confusion histogram int64 [C,C], or [B,C,C] with per_image; `hist` given: added to
+      loss_acc  float64 [2] on the device, (sum nll, valid pixels) of the plain cross entropy with ignore_index, ADDED to: pass
+                True for a fresh accumulator or the tensor of an earlier call; the validation loss is loss_acc[0] / loss_acc[1]."""
+    who = "upsample_argmax"
+    if not isinstance(P, torch.Tensor) or not P.is_cuda:
+        raise _lib.MrfpHipError("%s: P must be a GPU tensor: the HIP path has no CPU fallback" % who)
+    if P.dim() != 4 or not P.is_contiguous(memory_format=CL):
+        raise _lib.MrfpHipError("%s: P must be a 4-D tensor in channels_last (NHWC) storage, got %s strides %s"
+                                % (who, tuple(P.shape), tuple(P.stride())))
+    P = P.detach()
+    B, ld, Hi, Wi = P.shape
+    H, W, C = int(size[0]), int(size[1]), int(channels)
+    if H < 1 or W < 1 or not 1 <= C <= min(64, ld):
+        raise _lib.MrfpHipError("%s: size %s / channels %d do not fit P %s (1 <= channels <= 64)" % (who, (H, W), C, tuple(P.shape)))
+    if target is not None:
+        if (not isinstance(target, torch.Tensor) or target.device != P.device or target.dtype != torch.int64
+                or tuple(target.shape) != (B, H, W)):
+            raise _lib.MrfpHipError("%s: target must be int64 %s on P's GPU" % (who, (B, H, W)))
+        target = target.contiguous()
+    elif hist is not None or (loss_acc is not None and loss_acc is not False):
+        raise _lib.MrfpHipError("%s: hist / loss_acc need a target" % who)
+    hshape = (B, C, C) if per_image else (C, C)
+    if target is None:
+        hist = None
+    elif hist is None:
+        hist = torch.zeros(hshape, dtype=torch.int64, device=P.device)
+    elif (not isinstance(hist, torch.Tensor) or hist.dtype != torch.int64 or tuple(hist.shape) != hshape or not hist.is_contiguous()
+          or hist.device != P.device):
+        raise _lib.MrfpHipError("%s: hist must be a contiguous int64 %s on P's GPU" % (who, hshape))
+    ws = None
+    if loss_acc is None or loss_acc is False:
+        loss_acc = None
+    else:
+        if loss_acc is True:
+            loss_acc = torch.zeros(2, dtype=torch.float64, device=P.device)
+        elif (not isinstance(loss_acc, torch.Tensor) or loss_acc.dtype != torch.float64 or tuple(loss_acc.shape) != (2,)
+              or not loss_acc.is_contiguous() or loss_acc.device != P.device):
+            raise _lib.MrfpHipError("%s: loss_acc must be True or a contiguous float64 [2] on P's GPU" % who)
+        ws = torch.empty(2 * int(_lib.lib().mrfp_upsample_argmax_nblocks(B, H, W)), dtype=torch.float32, device=P.device)
+    if not (want_pred or want_conf or hist is not None or loss_acc is not None):
+        raise _lib.MrfpHipError("%s: no output requested" % who)
+    pred = torch.empty(B, H, W, dtype=torch.uint8, device=P.device) if want_pred else None
+    conf = torch.empty(B, H, W, dtype=torch.float32, device=P.device) if want_conf else None
+    call("mrfp_upsample_argmax", ptr(P), ld, ptr(target), dt(P), B, Hi, Wi, H, W, C, int(ignore_index), ptr(pred), ptr(conf),
+         ptr(hist), 1 if per_image else 0, ptr(ws), ptr(loss_acc), stream())
+    return Prediction(pred, conf, hist, loss_acc)
+
+
+def _chk_u8(who, name, t, dev=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or (dev is not None and t.device != dev):
+        raise _lib.MrfpHipError("%s: %s must be a uint8 tensor on the GPU%s: the HIP path has no CPU fallback"
+                                % (who, name, "" if dev is None else " of pred"))
+    if t.dtype != torch.uint8 or not t.is_contiguous():
+        raise _lib.MrfpHipError("%s: %s must be a contiguous uint8 tensor (got %s, strides %s)" % (who, name, t.dtype, tuple(t.stride())))
+
+
+def colorize(pred_u8, palette, image_u8=None, alpha=0.5, out=None):
+    """pred_u8 uint8 [...] -> uint8 [..., 3]: palette[pred] (mrfp_colorize_u8), or with image_u8 (uint8 [..., 3]) the blend
+    (a * palette[pred] + (256 - a) * image + 128) >> 8 with a = round(alpha * 256), 0 <= alpha <= 1.  palette: uint8 [256,3] on the
+    device (predict.Palette.device_table).  out: a contiguous uint8 [..., 3] to write into (any byte alignment)."""
+    who = "colorize"
+    _chk_u8(who, "pred_u8", pred_u8)
+    dev = pred_u8.device
+    _chk_u8(who, "palette", palette, dev)
+    if tuple(palette.shape) != (256, 3):
+        raise _lib.MrfpHipError("%s: palette must be uint8 [256,3], got %s" % (who, tuple(palette.shape)))
+    shape = tuple(pred_u8.shape) + (3,)
+    a = 256
+    if image_u8 is not None:
+        _chk_u8(who, "image_u8", image_u8, dev)
+        if tuple(image_u8.shape) != shape:
+            raise _lib.MrfpHipError("%s: image_u8 must be uint8 %s, got %s" % (who, shape, tuple(image_u8.shape)))
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError("%s: alpha must be in [0, 1], got %r" % (who, alpha))
+        a = int(round(float(alpha) * 256))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    else:
+        _chk_u8(who, "out", out, dev)
+        if tuple(out.shape) != shape:
+            raise _lib.MrfpHipError("%s: out must be uint8 %s, got %s" % (who, shape, tuple(out.shape)))
+        lo, hi = out.data_ptr(), out.data_ptr() + out.numel()
+        for t in (pred_u8, image_u8):
+            if t is not None and t.data_ptr() < hi and lo < t.data_ptr() + t.numel():
+                raise _lib.MrfpHipError("%s: out overlaps an input" % who)
+    if pred_u8.numel():
+        call("mrfp_colorize_u8", ptr(pred_u8), ptr(palette), ptr(image_u8), ptr(out), pred_u8.numel(), a, stream())
+    return out
 
 
 # ------------------------------------------------------------------------------------------
