@@ -415,6 +415,22 @@ int mrfp_conv_fwd_gated(const void* x, const void* wpack, const float* bias, voi
                         int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S,
                         int64_t Ho, int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil,
                         int64_t sstride, const void* addend, const void* addend_mask, void* stream);
+/* mrfp_conv_fwd with a LOW-RANK epilogue operand: y = conv(x) + round(lr_x . lr_w^T) with lr_x [B*Ho*Wo][lr_k] and lr_w [N][lr_k], both
+ * dense, in `dtype`; lr_k must be 32.  The product is one more k step in registers of the weight-stationary 3x3 kernel and the rank-32
+ * tensor is never written: the input gradient of a pointwise classifier on a convolution's skip alias (mrfp_amd/conv.py: the `final2`
+ * of the MRFP+ head, reference deepv3.py:355-361) rides in that convolution's dgrad, with lr_x = the score gradient and lr_w = the
+ * classifier's dgrad pack wd[C][1][1][32].  The product is rounded to `dtype` before it is added, so the result equals, bit for bit,
+ * mrfp_conv_fwd with the tensor a pointwise mrfp_conv_fwd(lr_x, lr_w) writes as its addend.  mrfp_conv_fwd's arguments plus the three;
+ * 16-bit activations, addend and colstats must be NULL; an error (nothing launched) when mrfp_conv_lowrank_ok says 0 for the geometry. */
+int mrfp_conv_fwd_lowrank(const void* x, const void* wpack, const float* bias, void* y, int dtype,
+                          int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S,
+                          int64_t Ho, int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil,
+                          int64_t sstride, const void* addend, float* colstats, const void* lr_x, const void* lr_w, int64_t lr_k,
+                          void* stream);
+/* Host only: 1 when the launch plan sends a stride-1 launch of these operands (no bias, addend or statistics) to the kernel that takes
+ * the low-rank operand, 0 otherwise (bad geometry and fp32 included).  The rule is the plan's own (mrfp_conv_fwd_lowrank asks it too). */
+int mrfp_conv_lowrank_ok(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S,
+                         int64_t Ho, int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil);
 /* Diagnostic (no reference counterpart): in a library built with -DMRFP_CLOCK_STAMP=1 (tools/clock_stamp.py; never the product
  * build, where this returns -1) every convolution workgroup records d(s_memtime) and d(s_memrealtime) around its main loop; out
  * receives n pairs {shader cycles, 100 MHz ticks} of the LAST launch of `family` (0: conv_igemm, 1: pointwise, 2: wgrad).

@@ -662,6 +662,38 @@ def ungate(t):
     return out
 
 
+# The input gradient of a shared pointwise classifier on a convolution's skip alias (_SharedConv1x1Pair: `final2` of the MRFP+ head on
+# the 256-channel half-resolution HRFP map) has rank <= 32 per pixel: dskip = dP . Wf.  Instead of writing it (1.2 GB at the bench
+# shape) and reading it back as the dgrad's addend, the pair returns a storage-less stand-in tagged with its two factors and the
+# dgrad multiplies them in registers, rounds the product as the written tensor was and adds it (mrfp_conv_fwd_lowrank): same bits.  MRFP_LOWRANK_SKIP=0: the materialised gradient (A/B runs, tests)
+LOWRANK_SKIP = [_os.environ.get("MRFP_LOWRANK_SKIP", "1") != "0"]
+LOWRANK_SKIP_HITS = [0]     # dgrad launches that took a skip gradient as its two low-rank factors (tests)
+_LOWRANK_K = 32             # the K of mrfp_conv_fwd_lowrank: the classifier's padded score planes
+
+
+def unlowrank(t):
+    """The plain gradient for a tensor that carries a `_mrfp_lowrank` (dP, dgrad pack, K, version) tag: the pointwise dgrad launch
+    dP . Wd the tag stands for.  Tensors without the tag (and None) pass through."""
+    lr = getattr(t, "_mrfp_lowrank", None) if t is not None else None
+    if lr is None:
+        return t
+    dp, wd, K, version = lr
+    if version != t._version:
+        raise _lib.MrfpHipError("a low-rank skip gradient was modified in place before it reached its consumer")
+    B, C, H, W = t.shape
+    out = empty_cl(B, C, H, W, dp.dtype, dp.device)
+    call("mrfp_conv_fwd", ptr(dp), ptr(wd), None, ptr(out), dt(dp), B, H, W, K, C, C, 1, 1, H, W, 1, 0, 0, 1, 1, None, None, stream())
+    return out
+
+
+def _dgrad_lowrank_ok(dtype, B, H, W, Cphys, Nphys, R, S, Ho, Wo, stride, pad_h, pad_w, dil):
+    """whether the dgrad launch of this convolution can take its skip gradient as low-rank factors (the launch plan's answer)"""
+    if dtype not in (torch.bfloat16, torch.float16) or stride != 1:
+        return False
+    return bool(_lib.lib().mrfp_conv_lowrank_ok(_lib._DT[dtype], B, Ho, Wo, Nphys, Cphys, Cphys, R, S, H, W, 1, dil * (R - 1) - pad_h,
+                                                dil * (S - 1) - pad_w, dil))
+
+
 def L_single(B, H, W, Cphys, Ho, Wo, Nphys, esz):
     """both operands of a weight-gradient problem fit one 3.75 GB buffer-descriptor range (a grouped launch needs that)"""
     return max(B * H * W * Cphys, B * Ho * Wo * Nphys) * esz < 0xF0000000
@@ -708,8 +740,15 @@ class _Conv2d(torch.autograd.Function):
                 raise _lib.MrfpHipError("a gated skip gradient reached its convolution without its gate: the skip alias was "
                                         "also consumed by an operator outside mrfp_amd.ops (set MRFP_GATED_SKIP=0)")
             cell[1] = False
+        lr = getattr(dskip, "_mrfp_lowrank", None) if dskip is not None else None
+        if cell is not None and cell[2]:
+            # the same for the low-rank stand-in of _SharedConv1x1Pair.backward: it has no storage, a sum with it is garbage
+            if lr is None or lr[3] != dskip._version:
+                raise _lib.MrfpHipError("a low-rank skip gradient reached its convolution without its factors: the skip alias was "
+                                        "also consumed by an operator outside mrfp_amd.ops (set MRFP_LOWRANK_SKIP=0)")
+            cell[2] = False
         if dy is None:            # only the skip alias was used downstream
-            return (ungate(dskip),) + (None,) * 10
+            return (unlowrank(ungate(dskip)),) + (None,) * 10
         stride, pad_h, pad_w, dil, Nphys, Ho, Wo = ctx.cfg
         dy = _chk(dy, "dy")
         B, Cphys, H, W = x.shape
@@ -719,6 +758,13 @@ class _Conv2d(torch.autograd.Function):
             pk = get_pack(weight, bias, x.dtype, Cphys, Nphys)
             dx = empty_cl(B, Cphys, H, W, x.dtype, x.device)
             gate = None
+            if lr is not None:
+                # the factors go to the dgrad kernel as one more k step; a launch that cannot take them gets the plain gradient
+                if (lr[3] == dskip._version and lr[2] == _LOWRANK_K and lr[0].dtype == dy.dtype == x.dtype and dskip.shape == dx.shape
+                        and _dgrad_lowrank_ok(x.dtype, B, H, W, Cphys, Nphys, R, S, Ho, Wo, stride, pad_h, pad_w, dil)):
+                    dskip = None
+                else:
+                    dskip, lr = unlowrank(dskip), None
             if dskip is not None:
                 g = getattr(dskip, "_mrfp_gate", None)
                 if g is not None:
@@ -734,7 +780,11 @@ class _Conv2d(torch.autograd.Function):
                 if dskip.dtype != x.dtype:
                     dskip = dskip.to(x.dtype)
             _lib.NOTE[0] = (N, C)
-            if gate is not None:
+            if lr is not None:
+                call("mrfp_conv_fwd_lowrank", ptr(dy), ptr(pk.wd), None, ptr(dx), dt(dy), B, Ho, Wo, Nphys, Cphys, Cphys, R, S, H, W,
+                     1, dil * (R - 1) - pad_h, dil * (S - 1) - pad_w, dil, stride, None, None, ptr(lr[0]), ptr(lr[1]), lr[2], stream())
+                LOWRANK_SKIP_HITS[0] += 1
+            elif gate is not None:
                 call("mrfp_conv_fwd_gated", ptr(dy), ptr(pk.wd), None, ptr(dx), dt(dy), B, Ho, Wo, Nphys, Cphys, Cphys, R, S, H, W,
                      1, dil * (R - 1) - pad_h, dil * (S - 1) - pad_w, dil, stride, ptr(dskip), ptr(gate), stream())
                 GATED_SKIP_HITS[0] += 1
@@ -787,6 +837,9 @@ class _SharedConv1x1Pair(torch.autograd.Function):
             ys.append(y)
         ctx.save_for_backward(x1, x2, weight, bias)
         ctx.Nphys = Nphys
+        # x2 is a convolution's skip alias whose dgrad can take this operator's input gradient as its two factors (conv2d marked it):
+        # the alias's cell -- [consumers counted by _chk, gated gradient issued, low-rank gradient issued] -- is read in backward
+        ctx.lr_cell = getattr(x2, "_mrfp_uses", None) if getattr(x2, "_mrfp_lowrank_ok", False) else None
         ctx.set_materialize_grads(False)
         return ys[0], ys[1]
 
@@ -798,14 +851,22 @@ class _SharedConv1x1Pair(torch.autograd.Function):
         pk = get_pack(weight, bias, x1.dtype, C, Nphys)
         dxs, dws = [], []
         db = None
-        for x, dy, need_dx in ((x1, dy1, ctx.needs_input_grad[0]), (x2, dy2, ctx.needs_input_grad[1])):
+        for x, dy, need_dx, cell in ((x1, dy1, ctx.needs_input_grad[0], None), (x2, dy2, ctx.needs_input_grad[1], ctx.lr_cell)):
             if dy is None:
                 dxs.append(None)
                 continue
             dy = _chk(dy, "dy")
             B, _, H, W = x.shape
             dx = None
-            if need_dx:
+            if (need_dx and cell is not None and LOWRANK_SKIP[0] and cell[0] == 1 and Nphys == _LOWRANK_K and dy.dtype == x.dtype
+                    and x.element_size() == 2):
+                # this operator is the alias's only consumer: nothing behind dx but the producing convolution's dgrad, which
+                # multiplies dy . Wd itself -- dx is a stand-in without storage (an expanded scalar) that carries the factors
+                # (never read: torch.empty, not zeros -- no fill launch)
+                dx = torch.empty((), dtype=x.dtype, device=x.device).expand(B, C, H, W)
+                dx._mrfp_lowrank = (dy, pk.wd, Nphys, dx._version)
+                cell[2] = True          # told to that convolution: anything but this tagged tensor arriving there raises
+            elif need_dx:
                 dx = empty_cl(B, C, H, W, x.dtype, x.device)
                 call("mrfp_conv_fwd", ptr(dy), ptr(pk.wd), None, ptr(dx), dt(dy), B, H, W, Nphys, C, C, 1, 1, H, W, 1, 0, 0, 1, 1,
                      None, None, stream())
@@ -895,7 +956,11 @@ def conv2d(x, weight, bias, stride, padding, dilation, phys_out: Optional[int] =
     if skip is not None:
         skip._mrfp_skip_alias = True      # its gradient goes to this convolution's dgrad epilogue and nowhere else
         # [operators that consumed the alias so far (ops._chk): a gated gradient needs exactly one, a gated gradient was issued]
-        skip._mrfp_uses = [0, False]
+        # ..., a low-rank gradient was issued (_SharedConv1x1Pair.backward)]
+        skip._mrfp_uses = [0, False, False]
+        if (LOWRANK_SKIP[0] and y.grad_fn is not None and x.requires_grad
+                and _dgrad_lowrank_ok(x.dtype, B, H, W, Cphys, Nphys, R, S, Ho, Wo, st, ph, pw, dl)):
+            skip._mrfp_lowrank_ok = True  # this convolution's dgrad can take the alias's gradient as low-rank factors
         if y.grad_fn is not None:
             y.grad_fn._mrfp_cell = skip._mrfp_uses     # (the autograd node IS the ctx of _Conv2d.backward)
     if stats is not None and (phys_out is not None or Nphys == N):

@@ -41,12 +41,20 @@ struct C64P {
     int units;           // B * strips * H  (output row strips)
     int spi;             // statistics row slots per image and sub-strip (>= workgroups that can touch one image)
     unsigned xbytes, wbytes, ybytes;
+    const char* lr_x;    // low-rank addend (LR): [M][32] 16-bit, dense, or null
+    const char* lr_w;    // ... and its factor [N][32]: y += round(lr_x . lr_w^T), the product never leaves the registers
+    unsigned lrbytes;    // size of lr_x (64 bytes per pixel)
 };
 
 constexpr int kC64Slots = 4;
 
-template <typename T, int CB, int NCG, bool STATS, bool ADD, int ACT = 0>
+// LR: the epilogue operand is a rank-32 product instead of a tensor -- y = conv(x) + round_T(lr_x[M][32] . lr_w[N][32]^T), one more k
+// step of 32 behind the 18 * CB of the filter, into accumulators of its own (the input gradient of a pointwise classifier on the skip
+// alias, never materialised).  The product is rounded to T before it is added, as the tensor it replaces was when a pointwise dgrad
+// launch wrote it: the result is the addend form's, bit for bit.
+template <typename T, int CB, int NCG, bool STATS, bool ADD, int ACT = 0, bool LR = false>
 __global__ __launch_bounds__(256, (CB == 1 ? 2 : 1)) void conv3x3_c64_kernel(C64P p) {
+    static_assert(!LR || (!STATS && !ADD && ACT == 0), "the low-rank operand excludes statistics, an addend and an activation");
     constexpr int PSN = 4 / NCG;                 // pixel sub-strips per workgroup
     constexpr int SW = 64 * PSN;                 // strip width
     constexpr int NPIECE = (SW + 4 + 7) / 8;     // 8-pixel DMA pieces per window row and 64-channel half (dilation <= 2: 2 halo pixels either side)
@@ -82,6 +90,19 @@ __global__ __launch_bounds__(256, (CB == 1 ? 2 : 1)) void conv3x3_c64_kernel(C64
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int j = 0; j < 2; ++j) settle(fw[ks][j]);
+    // low-rank factor: the same channel rows, K = 32 = one k step (a row of lr_w is 64 bytes)
+    const __amdgpu_buffer_rsrc_t lxr = __builtin_amdgcn_make_buffer_rsrc((void*)p.lr_x, 0, (int)p.lrbytes, 0x00020000);
+    uint4 fl[2];
+    if constexpr (LR) {
+        const __amdgpu_buffer_rsrc_t lwr = __builtin_amdgcn_make_buffer_rsrc((void*)p.lr_w, 0, p.N * 64, 0x00020000);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = n0 + 8 * (l15 >> 2) + 4 * j + (l15 & 3);
+            fl[j] = bload(lwr, n < p.N ? (unsigned)(n * 64 + lq * 16) : kOOB);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) settle(fl[j]);
+    }
     float bv[2][4];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -193,7 +214,7 @@ __global__ __launch_bounds__(256, (CB == 1 ? 2 : 1)) void conv3x3_c64_kernel(C64
             if (i + 1 < i1) issue_row(i + 2);
             const int oh = q + d * i;
             // addend / statistics weights of this row: fetched before the multiplies, used behind them
-            uint4 av[4];
+            uint4 av[4];          // (LR: the row's lr_x fragments, 16 bytes per lane and pixel block)
             unsigned wt[4];
             const int owl = ow0 + ps * 64 + l15;                                  // this lane's column in pixel block 0
             const unsigned ml = (unsigned)((b * p.H + oh) * p.W + owl);           // ... and its output row index
@@ -203,6 +224,7 @@ __global__ __launch_bounds__(256, (CB == 1 ? 2 : 1)) void conv3x3_c64_kernel(C64
 #pragma unroll
             for (int bk = 0; bk < 4; ++bk) {
                 if constexpr (ADD) av[bk] = bload(ar, out_off(bk));
+                if constexpr (LR) av[bk] = bload(lxr, owl + bk * 16 < p.W ? (ml + (unsigned)(bk * 16)) * 64u + (unsigned)(lq * 16) : kOOB);
                 if constexpr (STATS) {
                     const bool ok = owl + bk * 16 < p.W;
                     wt[bk] = ok ? (p.rowweight ? (unsigned)p.rowweight[ml + bk * 16] : 1u) : 0u;
@@ -235,11 +257,20 @@ __global__ __launch_bounds__(256, (CB == 1 ? 2 : 1)) void conv3x3_c64_kernel(C64
                     }
                 __builtin_amdgcn_sched_barrier(0);
             }
+            if constexpr (LR) {       // the row's addend, made here: 8 channels of one pixel per lane and pixel block, rounded to T
+#pragma unroll
+                for (int bk = 0; bk < 4; ++bk) {
+                    f32x4 t0 = {0.f, 0.f, 0.f, 0.f}, t1 = {0.f, 0.f, 0.f, 0.f};
+                    Mma16<T>::run(t0, fl[0], av[bk]);
+                    Mma16<T>::run(t1, fl[1], av[bk]);
+                    av[bk] = make_uint4(pack2<T>(t0[0], t0[1]), pack2<T>(t0[2], t0[3]), pack2<T>(t1[0], t1[1]), pack2<T>(t1[2], t1[3]));
+                }
+            }
             // epilogue: 8 consecutive channels of one pixel per lane and pixel block
 #pragma unroll
             for (int bk = 0; bk < 4; ++bk) {
                 uint4 v;
-                if constexpr (ADD) {
+                if constexpr (ADD || LR) {
                     float a[8];
                     unpack2<T>(av[bk].x, a[0], a[1]);
                     unpack2<T>(av[bk].y, a[2], a[3]);
@@ -322,22 +353,26 @@ bool c64_plan(const ConvP& p, int esz, ConvPlan& plan) {
     return true;
 }
 
-template <typename T, int CB, int NCG, bool STATS, bool ADD, int ACT = 0>
+template <typename T, int CB, int NCG, bool STATS, bool ADD, int ACT = 0, bool LR = false>
 static int c64_launch(const C64P& q, int grid, hipStream_t st) {
     constexpr int SW = 64 * (4 / NCG), NPIECE = (SW + 4 + 7) / 8;
     const int lds = kC64Slots * CB * NPIECE * 1024 + 1024;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c64_kernel<T, CB, NCG, STATS, ADD, ACT>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c64_kernel<T, CB, NCG, STATS, ADD, ACT, LR>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set = true;
     }
-    hipLaunchKernelGGL((conv3x3_c64_kernel<T, CB, NCG, STATS, ADD, ACT>), dim3((unsigned)grid, (unsigned)((q.N + 127) / 128)), dim3(256), lds, st, q);
+    hipLaunchKernelGGL((conv3x3_c64_kernel<T, CB, NCG, STATS, ADD, ACT, LR>), dim3((unsigned)grid, (unsigned)((q.N + 127) / 128)), dim3(256), lds, st, q);
     MRFP_LAUNCH_CHECK();
     return 0;
 }
 template <typename T, int CB, int NCG>
 static int c64_pick(const ConvP& p, const C64P& q, int grid, hipStream_t st, int act) {
+    if (q.lr_x) {         // mrfp_conv_fwd_lowrank: its own instance; the other epilogue operands are refused
+        MRFP_CHECK(act == 0 && !p.colstats && !p.addend, "conv_fwd_lowrank: no activation, statistics or addend beside the low-rank operand");
+        return c64_launch<T, CB, NCG, false, false, 0, true>(q, grid, st);
+    }
     if (act != 0) {       // folded inference launches (mrfp_conv_fwd_act): never with statistics
         if (p.colstats) return -1;
         if (act == 1) return p.addend ? c64_launch<T, CB, NCG, false, true, 1>(q, grid, st) : c64_launch<T, CB, NCG, false, false, 1>(q, grid, st);
@@ -349,8 +384,9 @@ static int c64_pick(const ConvP& p, const C64P& q, int grid, hipStream_t st, int
 }
 
 template <typename T>
-static int c64_run_t(const ConvP& p, const ConvPlan& plan, hipStream_t st, int act) {
+static int c64_run_t(const ConvP& p, const ConvPlan& plan, hipStream_t st, int act, const void* lr_x, const void* lr_w) {
     C64P q;
+    q.lr_x = (const char*)lr_x; q.lr_w = (const char*)lr_w; q.lrbytes = lr_x ? (unsigned)((int64_t)p.M * 64) : 0u;
     q.x = p.x; q.w = p.w; q.y = p.y; q.bias = p.bias; q.addend = p.addend; q.colstats = p.colstats; q.rowweight = p.rowweight;
     q.B = p.B; q.H = p.H; q.W = p.W; q.N = p.N; q.ldy = p.ldy; q.dil = p.dil;
     const int SW = p.N == 64 ? 128 : 64;
@@ -362,8 +398,9 @@ static int c64_run_t(const ConvP& p, const ConvPlan& plan, hipStream_t st, int a
     if (p.C == 64) return p.N == 64 ? c64_pick<T, 1, 2>(p, q, grid, st, act) : c64_pick<T, 1, 4>(p, q, grid, st, act);
     return p.N == 64 ? c64_pick<T, 2, 2>(p, q, grid, st, act) : c64_pick<T, 2, 4>(p, q, grid, st, act);
 }
-int c64_run(const ConvP& p, const ConvPlan& plan, bool is_f16, hipStream_t st, int act) {
-    return is_f16 ? c64_run_t<f16>(p, plan, st, act) : c64_run_t<bf16>(p, plan, st, act);
+int c64_run(const ConvP& p, const ConvPlan& plan, bool is_f16, hipStream_t st, int act, const void* lr_x, const void* lr_w) {
+    MRFP_CHECK(!lr_x == !lr_w, "conv_fwd_lowrank: both low-rank operands or neither");
+    return is_f16 ? c64_run_t<f16>(p, plan, st, act, lr_x, lr_w) : c64_run_t<bf16>(p, plan, st, act, lr_x, lr_w);
 }
 
 }  // namespace mrfp

@@ -340,7 +340,9 @@ int pwk_run(const ConvP& p, bool is_f16, hipStream_t st, int act = 0);
 
 // ---- weight-stationary 3x3 kernel for the 64-input-channel layers (HRFP ends, stem / layer-1 3x3), conv_c64.hip ---------------
 bool c64_plan(const ConvP& p, int esz, ConvPlan& plan);      // statistics rows: [image][sub-strip][slot], per image (not per row count)
-int c64_run(const ConvP& p, const ConvPlan& plan, bool is_f16, hipStream_t st, int act = 0);
+// (lr_x / lr_w: the rank-32 epilogue operand of mrfp_conv_fwd_lowrank, both or neither; they exclude addend, statistics and act)
+int c64_run(const ConvP& p, const ConvPlan& plan, bool is_f16, hipStream_t st, int act = 0, const void* lr_x = nullptr,
+            const void* lr_w = nullptr);
 
 // ---- launch plan of a weight gradient (conv_wgrad.hip: wgrad_plan) -----------------------------------------------------------------
 // Host only.  The kernels in wgrad_plan's priority order: the accumulator-stationary 3x3 kernel (conv_wg3.hip), the accumulator-stationary

@@ -820,7 +820,7 @@ static int conv_fwd_impl(const void* x, const void* wpack, const float* bias, vo
                          int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S, int64_t Ho, int64_t Wo,
                          int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t sstride, const void* addend,
                          float* colstats, void* stream, const void* addend_mask = nullptr, const unsigned char* rowweight = nullptr,
-                         int act = 0) {
+                         int act = 0, const void* lr_x = nullptr, const void* lr_w = nullptr) {
     MRFP_CHECK(act >= 0 && act <= 2, "conv_fwd_act: act must be 0 (none), 1 (ReLU) or 2 (ReLU6), got %d", act);
     MRFP_CHECK(act == 0 || (sstride == 1 && !colstats && !addend_mask && !rowweight),
                "conv_fwd_act: an activation is a forward-launch option (sstride 1, no statistics, no gate mask)");
@@ -866,6 +866,9 @@ static int conv_fwd_impl(const void* x, const void* wpack, const float* bias, vo
     MRFP_CHECK(!chunked || !colstats, "conv_fwd: fused statistics are not available for inputs above 3.75 GB (see mrfp_conv_single_launch)");
     MRFP_CHECK(!rowweight || plan.kind != ConvKernel::pw, "conv_fwd_wstats: not available on the pointwise kernels");
     if (chunked) p.classed = 0;          // (batch ranges: the class size would change per range)
+    // the low-rank epilogue operand exists on the weight-stationary 3x3 kernel alone (mrfp_conv_lowrank_ok asks the same plan)
+    MRFP_CHECK(!lr_x || (plan.kind == ConvKernel::c64 && !chunked),
+               "conv_fwd_lowrank: these operands do not run on the weight-stationary 3x3 kernel (see mrfp_conv_lowrank_ok)");
     // timing-only diagnostics: zero-record descriptors drop that operand's traffic, instruction stream unchanged
     static const int dbg_drop = env_switch("MRFP_DEBUG_DROP", 0);
     int rc = 0;
@@ -881,7 +884,8 @@ static int conv_fwd_impl(const void* x, const void* wpack, const float* bias, vo
         p.xbytes = (dbg_drop & 1) ? 0u : (unsigned)(bc * img);
         p.wbytes = (dbg_drop & 2) ? 0u : (unsigned)wb;
         if (chunked) plan = conv_plan(p, esz);       // a batch range is a launch of its own: a smaller M may take another kernel
-        rc = by_dtype(dtype, "conv_fwd", [&](auto t) { return run_igemm_act<typename decltype(t)::type>(p, plan, (hipStream_t)stream, act); });
+        if (lr_x) rc = c64_run(p, plan, dtype == MRFP_F16, (hipStream_t)stream, 0, lr_x, lr_w);
+        else rc = by_dtype(dtype, "conv_fwd", [&](auto t) { return run_igemm_act<typename decltype(t)::type>(p, plan, (hipStream_t)stream, act); });
     }
     if (rc || !colstats) return rc;
     if (plan.stats_blocks > kCompactAbove) {
@@ -946,6 +950,30 @@ int mrfp_conv_fwd_gated(const void* x, const void* wpack, const float* bias, voi
     MRFP_CHECK(addend && addend_mask, "conv_fwd_gated: addend and its gate mask are required");
     return conv_fwd_impl(x, wpack, bias, y, dtype, B, H, W, C, N, ldy, R, S, Ho, Wo, stride, pad_h, pad_w, dil, sstride, addend,
                          nullptr, stream, addend_mask);
+}
+
+/* y = conv(x) + round(lr_x[M][lr_k] . lr_w[N][lr_k]^T), the product taken in registers of the weight-stationary 3x3 kernel */
+int mrfp_conv_fwd_lowrank(const void* x, const void* wpack, const float* bias, void* y, int dtype, int64_t B, int64_t H,
+                          int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S, int64_t Ho, int64_t Wo,
+                          int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil, int64_t sstride, const void* addend,
+                          float* colstats, const void* lr_x, const void* lr_w, int64_t lr_k, void* stream) {
+    MRFP_CHECK(!addend && !colstats, "conv_fwd_lowrank: the low-rank operand excludes an addend and statistics");
+    MRFP_CHECK(lr_x && lr_w && aligned16(lr_x) && aligned16(lr_w), "conv_fwd_lowrank: both low-rank operands are required, 16-byte aligned");
+    MRFP_CHECK(lr_k == 32, "conv_fwd_lowrank: the low-rank K is 32, got %lld", (long long)lr_k);
+    MRFP_CHECK(dtype == MRFP_BF16 || dtype == MRFP_F16, "conv_fwd_lowrank: 16-bit activations only (dtype %d)", dtype);
+    return conv_fwd_impl(x, wpack, bias, y, dtype, B, H, W, C, N, ldy, R, S, Ho, Wo, stride, pad_h, pad_w, dil, sstride, nullptr,
+                         nullptr, stream, nullptr, nullptr, 0, lr_x, lr_w);
+}
+
+/* host only: 1 when the launch plan sends these operands (no bias, addend or statistics) to the kernel that takes a low-rank operand */
+int mrfp_conv_lowrank_ok(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S,
+                         int64_t Ho, int64_t Wo, int64_t stride, int64_t pad_h, int64_t pad_w, int64_t dil) {
+    if (!dtype_known(dtype) || dtype_bytes(dtype) != 2) return 0;
+    ConvP p;
+    if (conv_params(p, dtype, B, H, W, C, N, ldy, R, S, Ho, Wo, stride, pad_h, pad_w, dil, 1, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return 0;
+    if (!mrfp_conv_single_launch(B, H * W * C * 2)) return 0;
+    return conv_plan(p, 2).kind == ConvKernel::c64 ? 1 : 0;
 }
 
 int mrfp_conv_stats_layout(int dtype, int64_t B, int64_t H, int64_t W, int64_t C, int64_t N, int64_t ldy, int64_t R, int64_t S,
