@@ -10,7 +10,6 @@ namespace mrfp {
 template <typename T>
 __global__ __launch_bounds__(kCeThreads) void ce_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ target,
                                                             int64_t npix, int C, int64_t ignore, float* __restrict__ ws) {
-    __shared__ float sm[2][kCeThreads / 64];
     float nll = 0.f, cnt = 0.f;
     for (int64_t p = (int64_t)blockIdx.x * kCeThreads + threadIdx.x; p < npix; p += (int64_t)gridDim.x * kCeThreads) {
         const int64_t tg = target[p];
@@ -23,33 +22,15 @@ __global__ __launch_bounds__(kCeThreads) void ce_fwd_kernel(const T* __restrict_
         nll += (m + __logf(s)) - to_f(l[tg]);
         cnt += 1.f;
     }
-    nll = wave_sum(nll);
-    cnt = wave_sum(cnt);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sm[0][w] = nll; sm[1][w] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float a = 0.f, b = 0.f;
-        for (int i = 0; i < kCeThreads / 64; ++i) { a += sm[0][i]; b += sm[1][i]; }
-        ws[2 * blockIdx.x] = a;
-        ws[2 * blockIdx.x + 1] = b;
-    }
+    ce_store_partial(nll, cnt, ws + 2 * blockIdx.x);
 }
 
 __global__ void ce_finalize_kernel(const float* ws, int nblk, float* loss) {
-    __shared__ double sa[256], sb[256];
-    double a = 0.0, b = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) { a += ws[2 * i]; b += ws[2 * i + 1]; }
-    sa[threadIdx.x] = a;
-    sb[threadIdx.x] = b;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
-        __syncthreads();
-    }
+    double a, d;
+    ce_reduce_partials(ws, nblk, a, d);
     if (threadIdx.x == 0) {
-        loss[0] = (float)(sa[0] / sb[0]);   // 0/0 -> NaN, as torch does for an all-ignored batch
-        loss[1] = (float)sb[0];
+        loss[0] = (float)(a / d);   // 0/0 -> NaN, as torch does for an all-ignored batch
+        loss[1] = (float)d;
     }
 }
 
@@ -182,7 +163,6 @@ template <typename T, int CP>
 __global__ __launch_bounds__(kCeThreads) void upsample_ce_fwd_kernel(const T* __restrict__ P, int ld, const int64_t* __restrict__ target,
                                                                      int B, int Hi, int Wi, int H, int W, int C, int64_t ignore,
                                                                      float* __restrict__ ws) {
-    __shared__ float sm[2][kCeThreads / 64];
     const int64_t npix = (int64_t)B * H * W;
     float nll = 0.f, cnt = 0.f;
     for (int64_t p = (int64_t)blockIdx.x * kCeThreads + threadIdx.x; p < npix; p += (int64_t)gridDim.x * kCeThreads) {
@@ -202,17 +182,7 @@ __global__ __launch_bounds__(kCeThreads) void upsample_ce_fwd_kernel(const T* __
         nll += (m + __logf(s)) - zt;
         cnt += 1.f;
     }
-    nll = wave_sum(nll);
-    cnt = wave_sum(cnt);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sm[0][w] = nll; sm[1][w] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float a = 0.f, bsum = 0.f;
-        for (int i = 0; i < kCeThreads / 64; ++i) { a += sm[0][i]; bsum += sm[1][i]; }
-        ws[2 * blockIdx.x] = a;
-        ws[2 * blockIdx.x + 1] = bsum;
-    }
+    ce_store_partial(nll, cnt, ws + 2 * blockIdx.x);
 }
 
 template <typename T, int CP>
@@ -220,7 +190,6 @@ __global__ __launch_bounds__(kCeThreads) void upsample_ce_bwd_kernel(const T* __
                                                                      const float* __restrict__ loss, const float* __restrict__ gscale,
                                                                      T* __restrict__ dlogits, int Cd, int B, int Hi, int Wi, int H,
                                                                      int W, int C, int64_t ignore) {
-    constexpr int EPC = 16 / (int)sizeof(T);
     const int64_t npix = (int64_t)B * H * W;
     const float k = (gscale ? gscale[0] : 1.f) / loss[1];
     for (int64_t p = (int64_t)blockIdx.x * kCeThreads + threadIdx.x; p < npix; p += (int64_t)gridDim.x * kCeThreads) {
@@ -244,48 +213,12 @@ __global__ __launch_bounds__(kCeThreads) void upsample_ce_bwd_kernel(const T* __
 #pragma unroll
             for (int c = 0; c < CP; ++c) g[c] = c < C ? (g[c] * inv - (c == (int)tg ? 1.f : 0.f)) * k : 0.f;
         }
-#pragma unroll
-        for (int c0 = 0; c0 < CP; c0 += EPC) {
-            if (c0 < Cd) {
-                float o[EPC];
-#pragma unroll
-                for (int i = 0; i < EPC; ++i) o[i] = g[c0 + i];
-                store_f<T, EPC>(d + c0, o);
-            }
-        }
+        store_class_row<T, CP>(d, Cd, g);
     }
 }
 
 // (A backward in gather form over the LOW-resolution pixels -- the full-resolution gradient never written -- was built and
 // measured in round 2: 818 us against 276 + 255 us for the two passes at 16 x 768 x 768 x 19; removed, profiles/r02_experiments.md.)
-
-// dispatch on CP = C rounded up to 8 (8 .. kMaxClasses)
-struct UpCeArgs {
-    const void* P; int ld; const int64_t* target; const float* loss; const float* gscale; void* dlogits; int Cd;
-    int B, Hi, Wi, H, W, C; int64_t ignore; float* ws; int nb; hipStream_t st;
-};
-template <typename T, int CP>
-static void launch_up_ce(const UpCeArgs& a, bool bwd) {
-    if (!bwd)
-        hipLaunchKernelGGL((upsample_ce_fwd_kernel<T, CP>), dim3(a.nb), dim3(kCeThreads), 0, a.st, (const T*)a.P, a.ld, a.target,
-                           a.B, a.Hi, a.Wi, a.H, a.W, a.C, a.ignore, a.ws);
-    else
-        hipLaunchKernelGGL((upsample_ce_bwd_kernel<T, CP>), dim3(a.nb), dim3(kCeThreads), 0, a.st, (const T*)a.P, a.ld, a.target,
-                           a.loss, a.gscale, (T*)a.dlogits, a.Cd, a.B, a.Hi, a.Wi, a.H, a.W, a.C, a.ignore);
-}
-template <typename T>
-static void dispatch_up_ce(const UpCeArgs& a, bool bwd) {
-    switch ((a.C + 7) / 8) {
-        case 1: launch_up_ce<T, 8>(a, bwd); break;
-        case 2: launch_up_ce<T, 16>(a, bwd); break;
-        case 3: launch_up_ce<T, 24>(a, bwd); break;
-        case 4: launch_up_ce<T, 32>(a, bwd); break;
-        case 5: launch_up_ce<T, 40>(a, bwd); break;
-        case 6: launch_up_ce<T, 48>(a, bwd); break;
-        case 7: launch_up_ce<T, 56>(a, bwd); break;
-        default: launch_up_ce<T, 64>(a, bwd); break;
-    }
-}
 
 }  // namespace mrfp
 
@@ -295,21 +228,18 @@ int mrfp_upsample_ce_fwd(const void* P, int64_t ld, const int64_t* target, int d
                          int64_t H, int64_t W, int64_t C, int64_t ignore_index, float* ws, float* loss, void* stream) {
     MRFP_CHECK(P && target && ws && loss && B > 0 && Hi > 0 && Wi > 0 && H > 0 && W > 0 && C > 0 && C <= mrfp::kMaxClasses,
                "upsample_ce_fwd: bad arguments");
-    MRFP_CHECK(mrfp::dtype_known(dtype), "upsample_ce_fwd: unknown dtype %d", dtype);
-    const int epc = 16 / mrfp::dtype_bytes(dtype);
-    MRFP_CHECK(ld % epc == 0 && ld >= (C + epc - 1) / epc * epc && mrfp::aligned16(P),
-               "upsample_ce_fwd: the score buffer must be channel-padded to 16-byte chunks (ld=%lld)", (long long)ld);
+    if (int rc = mrfp::class_pitch_check("upsample_ce_fwd", P, ld, nullptr, 0, false, dtype, C)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int nb = mrfp::ce_blocks(B * H * W);
-    mrfp::UpCeArgs a{P, (int)ld, target, nullptr, nullptr, nullptr, 0, (int)B, (int)Hi, (int)Wi, (int)H, (int)W, (int)C,
-                     ignore_index, ws, nb, st};
-    return mrfp::by_dtype(dtype, "upsample_ce_fwd", [&](auto t) {
-        mrfp::dispatch_up_ce<typename decltype(t)::type>(a, false);
-        MRFP_LAUNCH_CHECK();
-        hipLaunchKernelGGL(mrfp::ce_finalize_kernel, dim3(1), dim3(256), 0, st, ws, nb, loss);
-        MRFP_LAUNCH_CHECK();
-        return 0;
-    });
+    if (int rc = mrfp::by_dtype_class_pad<mrfp::kMaxClasses>(dtype, "upsample_ce_fwd", (int)C, [&](auto t, auto cp) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((mrfp::upsample_ce_fwd_kernel<T, decltype(cp)::value>), dim3(nb), dim3(mrfp::kCeThreads), 0, st, (const T*)P,
+                               (int)ld, target, (int)B, (int)Hi, (int)Wi, (int)H, (int)W, (int)C, ignore_index, ws);
+        }))
+        return rc;
+    hipLaunchKernelGGL(mrfp::ce_finalize_kernel, dim3(1), dim3(256), 0, st, ws, nb, loss);
+    MRFP_LAUNCH_CHECK();
+    return 0;
 }
 
 int mrfp_upsample_ce_bwd(const void* P, int64_t ld, const int64_t* target, const float* loss, const float* gscale,
@@ -317,18 +247,14 @@ int mrfp_upsample_ce_bwd(const void* P, int64_t ld, const int64_t* target, const
                          int64_t C, int64_t ignore_index, void* stream) {
     MRFP_CHECK(P && target && loss && dlogits && B > 0 && Hi > 0 && Wi > 0 && H > 0 && W > 0 && C > 0 && C <= mrfp::kMaxClasses,
                "upsample_ce_bwd: bad arguments");
-    MRFP_CHECK(mrfp::dtype_known(dtype), "upsample_ce_bwd: unknown dtype %d", dtype);
-    const int epc = 16 / mrfp::dtype_bytes(dtype);
-    MRFP_CHECK(ld % epc == 0 && Cd % epc == 0 && Cd >= C && ld >= Cd && mrfp::aligned16(P) && mrfp::aligned16(dlogits),
-               "upsample_ce_bwd: channel pitches must be 16-byte multiples (ld=%lld Cd=%lld)", (long long)ld, (long long)Cd);
+    if (int rc = mrfp::class_pitch_check("upsample_ce_bwd", P, ld, dlogits, Cd, false, dtype, C)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int nb = mrfp::ce_blocks(B * H * W);
-    mrfp::UpCeArgs a{P, (int)ld, target, loss, gscale, dlogits, (int)Cd, (int)B, (int)Hi, (int)Wi, (int)H, (int)W, (int)C,
-                     ignore_index, nullptr, nb, st};
-    return mrfp::by_dtype(dtype, "upsample_ce_bwd", [&](auto t) {
-        mrfp::dispatch_up_ce<typename decltype(t)::type>(a, true);
-        MRFP_LAUNCH_CHECK();
-        return 0;
+    return mrfp::by_dtype_class_pad<mrfp::kMaxClasses>(dtype, "upsample_ce_bwd", (int)C, [&](auto t, auto cp) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((mrfp::upsample_ce_bwd_kernel<T, decltype(cp)::value>), dim3(nb), dim3(mrfp::kCeThreads), 0, st, (const T*)P,
+                           (int)ld, target, loss, gscale, (T*)dlogits, (int)Cd, (int)B, (int)Hi, (int)Wi, (int)H, (int)W, (int)C,
+                           ignore_index);
     });
 }
 
@@ -337,12 +263,13 @@ int mrfp_upsample_ce_bwd(const void* P, int64_t ld, const int64_t* target, const
 // =============================================================================================
 // Class weights, label smoothing and per-image means (include/mrfp_hip.h: mrfp_ce_w_*, mrfp_upsample_ce_w_*): the criteria a
 // caller hands to the reference's DeepV3Plus (network/deepv3.py:111 `criterion`, `criterion_aux`) instead of the plain one of
-// main.py:822.  Same streaming as the plain kernels above, which stay as they are; what differs:
-//   * the grid is (nbx, B): a workgroup works inside ONE image, stages that image's weight row (and its sum) in LDS once and reads
-//     w[t] / w[c] from there -- the run-time index never touches the register-resident class vector -- and its (num, den) partial
-//     belongs to one image's denominator;
-//   * the finalize kernel reduces the partials in double in a fixed order (no floating-point atomics) and leaves the denominators
-//     the backward divides by behind the loss.
+// main.py:822.  The plain kernels above keep their flat grid: they are the default step's path.  Here
+//   * the fused forward is the pixel-loop skeleton of loss_common.hpp (pixel_loss_fwd_kernel over BilinearRows) with the
+//     WeightedCe criterion below: grid (nbx, B), the image's weight row and its sum staged in LDS; the fused backward
+//     (upsample_ce_w_bwd_kernel) is that skeleton written out, for the registers it would otherwise lose;
+//   * the dense form (ce_w_fwd/bwd_kernel) walks a run-time C up to kCeDenseMaxC with the weight row in dynamic LDS: it has no
+//     register class vector, so it stays outside the skeleton and shares its grid, staging, partial and finalize;
+//   * ce_w_finalize_kernel (loss_common.hpp) leaves the denominators the backward divides by behind the loss.
 // =============================================================================================
 namespace mrfp {
 
@@ -401,33 +328,6 @@ __global__ __launch_bounds__(kCeThreads) void ce_w_fwd_kernel(const T* __restric
     ce_w_store_partial(num, den, ws);
 }
 
-// one workgroup.  MEAN / SUM: all nbx*B partials are one group; IMAGE_MEAN: the nbx partials of image b are group b.
-__global__ void ce_w_finalize_kernel(const float* __restrict__ ws, int nbx, int B, int mode, float* __restrict__ loss) {
-    __shared__ double sa[256], sb[256];
-    const int groups = mode == MRFP_CE_IMAGE_MEAN ? B : 1;
-    const int64_t per = mode == MRFP_CE_IMAGE_MEAN ? nbx : (int64_t)nbx * B;
-    double total = 0.0;        // thread 0
-    for (int g = 0; g < groups; ++g) {
-        const float* w = ws + 2 * (int64_t)g * per;
-        double a = 0.0, d = 0.0;
-        for (int64_t i = threadIdx.x; i < per; i += 256) { a += w[2 * i]; d += w[2 * i + 1]; }
-        sa[threadIdx.x] = a;
-        sb[threadIdx.x] = d;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            if (mode == MRFP_CE_SUM) total = sa[0];
-            else total += sa[0] / sb[0];          // 0/0 -> NaN: an all-ignored batch (MEAN, as torch) or image (IMAGE_MEAN)
-            loss[1 + g] = (float)sb[0];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (float)total;
-}
-
 template <typename T>
 __global__ __launch_bounds__(kCeThreads) void ce_w_bwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ target,
                                                               const float* __restrict__ loss, const float* __restrict__ gscale,
@@ -461,24 +361,20 @@ __global__ __launch_bounds__(kCeThreads) void ce_w_bwd_kernel(const T* __restric
     }
 }
 
-template <typename T, int CP>
-__global__ __launch_bounds__(kCeThreads) void upsample_ce_w_fwd_kernel(const T* __restrict__ P, int ld, const int64_t* __restrict__ target,
-                                                                       int Hi, int Wi, int H, int W, int C, int64_t ignore,
-                                                                       const float* __restrict__ weight, int64_t wstride, float eps,
-                                                                       float* __restrict__ ws) {
-    __shared__ float sw[kMaxClasses + 1];
-    const int b = blockIdx.y;
-    ce_stage_weights(sw, weight, wstride, b, C);
-    const float om = 1.f - eps, ec = eps / (float)C;
-    const int HW = H * W;
-    const int64_t* tb = target + (int64_t)b * HW;
-    float num = 0.f, den = 0.f;
-    for (int p = blockIdx.x * kCeThreads + threadIdx.x; p < HW; p += gridDim.x * kCeThreads) {
-        const int64_t tg = tb[p];
-        if (tg == ignore || tg < 0 || tg >= C) continue;
-        const int oh = p / W, ow = p - oh * W;
-        float z[CP];
-        up_logits<T, CP>(P, ld, Hi, Wi, H, W, C, b, oh, ow, z);
+// The criterion of the skeleton's forward: cross entropy of an int64 label (ignore, or outside 0..C-1: the pixel does not count)
+// with class weights and label smoothing eps.  sw: ce_stage_weights.
+struct WeightedCe {
+    static constexpr int kLdsFloats = kMaxClasses + 1, kMaxClassPad = kMaxClasses;
+    static constexpr double kDenBias = 0.0;
+    const int64_t* target; int64_t ignore; const float* weight; int64_t wstride; float eps; int mode;
+
+    __device__ __forceinline__ void stage(float* sw, int b, int C) const { ce_stage_weights(sw, weight, wstride, b, C); }
+    __device__ __forceinline__ int64_t label(int64_t tg, int) const { return tg; }
+    __device__ __forceinline__ bool valid(int64_t tg, int C) const { return !(tg == ignore || tg < 0 || tg >= C); }
+
+    template <int CP>
+    __device__ __forceinline__ void add_loss(const float (&z)[CP], int C, int64_t tg, const float* sw, float& num, float& den) const {
+        const float om = 1.f - eps, ec = eps / (float)C;
         float m = -INFINITY;
 #pragma unroll
         for (int c = 0; c < CP; ++c) if (c < C) m = fmaxf(m, z[c]);
@@ -497,16 +393,18 @@ __global__ __launch_bounds__(kCeThreads) void upsample_ce_w_fwd_kernel(const T* 
         num += v;
         den += wt;
     }
-    ce_w_store_partial(num, den, ws);
-}
+};
 
+// The fused backward keeps its own kernel, the skeleton's backward with this criterion's gradient written out: with the gradient
+// in a member function the compiler holds every `c < C` mask in scalar registers across the trip and three families of
+// instances lose an occupancy step (bf16 / fp16 CP 16: 95 -> 98 VGPRs, 5 -> 4 waves; CP 48: 253 -> 256 + 1 AGPR, 2 -> 1; fp32 CP 8:
+// 72 -> 78, 7 -> 6; profiles/loss_skeleton.md).
 template <typename T, int CP>
 __global__ __launch_bounds__(kCeThreads) void upsample_ce_w_bwd_kernel(const T* __restrict__ P, int ld, const int64_t* __restrict__ target,
                                                                        const float* __restrict__ loss, const float* __restrict__ gscale,
                                                                        T* __restrict__ dlogits, int Cd, int Hi, int Wi, int H, int W,
                                                                        int C, int64_t ignore, const float* __restrict__ weight,
                                                                        int64_t wstride, float eps, int mode) {
-    constexpr int EPC = 16 / (int)sizeof(T);
     __shared__ float sw[kMaxClasses + 1];
     const int b = blockIdx.y;
     ce_stage_weights(sw, weight, wstride, b, C);
@@ -539,23 +437,14 @@ __global__ __launch_bounds__(kCeThreads) void upsample_ce_w_bwd_kernel(const T* 
                 for (int c = 0; c < CP; ++c) g[c] = c < C ? (g[c] * A - (c == (int)tg ? wt : 0.f)) * k : 0.f;
             }
         }
-#pragma unroll
-        for (int c0 = 0; c0 < CP; c0 += EPC) {
-            if (c0 < Cd) {
-                float o[EPC];
-#pragma unroll
-                for (int i = 0; i < EPC; ++i) o[i] = g[c0 + i];
-                store_f<T, EPC>(d + c0, o);
-            }
-        }
+        store_class_row<T, CP>(d, Cd, g);
     }
 }
 
 // what the four entries refuse alike, each under its own name
 static int ce_w_check(const char* who, int64_t B, int64_t C, int64_t wstride, float eps, int mode) {
     MRFP_CHECK(B <= 65535, "%s: at most 65535 images (B=%lld)", who, (long long)B);
-    MRFP_CHECK(wstride == 0 || wstride == C, "%s: wstride must be 0 (one weight row) or C (one per image) (wstride=%lld C=%lld)", who,
-               (long long)wstride, (long long)C);
+    if (int rc = wstride_check(who, wstride, C)) return rc;
     MRFP_CHECK(eps >= 0.f && eps < 1.f, "%s: label smoothing must be in [0, 1) (got %g)", who, (double)eps);
     MRFP_CHECK(mode == MRFP_CE_MEAN || mode == MRFP_CE_SUM || mode == MRFP_CE_IMAGE_MEAN, "%s: unknown mode %d", who, mode);
     return 0;
@@ -624,7 +513,7 @@ int mrfp_ce_w_fwd(const void* logits, const int64_t* target, int dtype, int64_t 
         hipLaunchKernelGGL((mrfp::ce_w_fwd_kernel<T>), dim3(nbx, (unsigned)B), dim3(mrfp::kCeThreads), lds, st, (const T*)logits, target, HW,
                            (int)C, ignore_index, weight, wstride, smoothing, ws);
         MRFP_LAUNCH_CHECK();
-        hipLaunchKernelGGL(mrfp::ce_w_finalize_kernel, dim3(1), dim3(256), 0, st, ws, nbx, (int)B, mode, loss);
+        hipLaunchKernelGGL(mrfp::ce_w_finalize_kernel<mrfp::WeightedCe>, dim3(1), dim3(256), 0, st, ws, nbx, (int)B, mode, loss);
         MRFP_LAUNCH_CHECK();
         return 0;
     });
@@ -651,52 +540,32 @@ int mrfp_ce_w_bwd(const void* logits, const int64_t* target, const float* loss, 
 int mrfp_upsample_ce_w_fwd(const void* P, int64_t ld, const int64_t* target, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H,
                            int64_t W, int64_t C, int64_t ignore_index, const float* weight, int64_t wstride, float smoothing, int mode,
                            float* ws, float* loss, void* stream) {
-    MRFP_CHECK(P && target && ws && loss && B > 0 && Hi > 0 && Wi > 0 && H > 0 && W > 0 && H * W < (1LL << 30),
-               "upsample_ce_w_fwd: bad arguments");
-    MRFP_CHECK(C >= 1 && C <= mrfp::kMaxClasses, "upsample_ce_w_fwd: 1 <= C <= %d (C=%lld)", mrfp::kMaxClasses, (long long)C);
-    MRFP_CHECK(mrfp::dtype_known(dtype), "upsample_ce_w_fwd: unknown dtype %d", dtype);
-    if (int rc = mrfp::ce_w_check("upsample_ce_w_fwd", B, C, wstride, smoothing, mode)) return rc;
-    const int epc = 16 / mrfp::dtype_bytes(dtype);
-    MRFP_CHECK(ld % epc == 0 && ld >= (C + epc - 1) / epc * epc && mrfp::aligned16(P),
-               "upsample_ce_w_fwd: the score buffer must be channel-padded to 16-byte chunks (ld=%lld)", (long long)ld);
-    hipStream_t st = (hipStream_t)stream;
-    const int nbx = mrfp::ce_w_blocks_x(B, H * W);
-    return mrfp::by_dtype(dtype, "upsample_ce_w_fwd", [&](auto t) {
-        using T = typename decltype(t)::type;
-        mrfp::by_class_pad((int)C, [&](auto cp) {
-            hipLaunchKernelGGL((mrfp::upsample_ce_w_fwd_kernel<T, decltype(cp)::value>), dim3(nbx, (unsigned)B), dim3(mrfp::kCeThreads), 0, st,
-                               (const T*)P, (int)ld, target, (int)Hi, (int)Wi, (int)H, (int)W, (int)C, ignore_index, weight, wstride,
-                               smoothing, ws);
-        });
-        MRFP_LAUNCH_CHECK();
-        hipLaunchKernelGGL(mrfp::ce_w_finalize_kernel, dim3(1), dim3(256), 0, st, ws, nbx, (int)B, mode, loss);
-        MRFP_LAUNCH_CHECK();
-        return 0;
-    });
+    const char* who = "upsample_ce_w_fwd";
+    MRFP_CHECK(P && target && ws && loss && B > 0, "%s: bad arguments", who);
+    MRFP_CHECK(C >= 1 && C <= mrfp::kMaxClasses, "%s: 1 <= C <= %d (C=%lld)", who, mrfp::kMaxClasses, (long long)C);
+    if (int rc = mrfp::ce_w_check(who, B, C, wstride, smoothing, mode)) return rc;
+    mrfp::BilinearRows src;
+    if (int rc = mrfp::bilinear_rows(who, P, ld, nullptr, 0, false, dtype, Hi, Wi, H, W, C, src)) return rc;
+    return mrfp::launch_pixel_loss_fwd(who, dtype, B, src, mrfp::WeightedCe{target, ignore_index, weight, wstride, smoothing, mode}, ws, loss,
+                                       (hipStream_t)stream);
 }
 
 int mrfp_upsample_ce_w_bwd(const void* P, int64_t ld, const int64_t* target, const float* loss, const float* gscale, void* dlogits,
                            int64_t Cd, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int64_t C,
                            int64_t ignore_index, const float* weight, int64_t wstride, float smoothing, int mode, void* stream) {
-    MRFP_CHECK(P && target && loss && dlogits && B > 0 && Hi > 0 && Wi > 0 && H > 0 && W > 0 && H * W < (1LL << 30),
-               "upsample_ce_w_bwd: bad arguments");
-    MRFP_CHECK(C >= 1 && C <= mrfp::kMaxClasses, "upsample_ce_w_bwd: 1 <= C <= %d (C=%lld)", mrfp::kMaxClasses, (long long)C);
-    MRFP_CHECK(mrfp::dtype_known(dtype), "upsample_ce_w_bwd: unknown dtype %d", dtype);
-    if (int rc = mrfp::ce_w_check("upsample_ce_w_bwd", B, C, wstride, smoothing, mode)) return rc;
-    const int epc = 16 / mrfp::dtype_bytes(dtype);
-    MRFP_CHECK(ld % epc == 0 && Cd % epc == 0 && Cd >= C && ld >= Cd && mrfp::aligned16(P) && mrfp::aligned16(dlogits),
-               "upsample_ce_w_bwd: channel pitches must be 16-byte multiples (ld=%lld Cd=%lld)", (long long)ld, (long long)Cd);
+    const char* who = "upsample_ce_w_bwd";
+    MRFP_CHECK(P && target && loss && dlogits && B > 0, "%s: bad arguments", who);
+    MRFP_CHECK(C >= 1 && C <= mrfp::kMaxClasses, "%s: 1 <= C <= %d (C=%lld)", who, mrfp::kMaxClasses, (long long)C);
+    if (int rc = mrfp::ce_w_check(who, B, C, wstride, smoothing, mode)) return rc;
+    mrfp::BilinearRows src;
+    if (int rc = mrfp::bilinear_rows(who, P, ld, dlogits, Cd, false, dtype, Hi, Wi, H, W, C, src)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int nbx = mrfp::ce_w_blocks_x(B, H * W);
-    return mrfp::by_dtype(dtype, "upsample_ce_w_bwd", [&](auto t) {
+    const int nbx = mrfp::ce_w_blocks_x(B, src.HW);
+    return mrfp::by_dtype_class_pad<mrfp::kMaxClasses>(dtype, who, src.C, [&](auto t, auto cp) {
         using T = typename decltype(t)::type;
-        mrfp::by_class_pad((int)C, [&](auto cp) {
-            hipLaunchKernelGGL((mrfp::upsample_ce_w_bwd_kernel<T, decltype(cp)::value>), dim3(nbx, (unsigned)B), dim3(mrfp::kCeThreads), 0, st,
-                               (const T*)P, (int)ld, target, loss, gscale, (T*)dlogits, (int)Cd, (int)Hi, (int)Wi, (int)H, (int)W, (int)C,
-                               ignore_index, weight, wstride, smoothing, mode);
-        });
-        MRFP_LAUNCH_CHECK();
-        return 0;
+        hipLaunchKernelGGL((mrfp::upsample_ce_w_bwd_kernel<T, decltype(cp)::value>), dim3(nbx, (unsigned)B), dim3(mrfp::kCeThreads), 0, st,
+                           (const T*)P, src.ld, target, loss, gscale, (T*)dlogits, src.Cd, src.Hi, src.Wi, src.H, src.W, src.C, ignore_index,
+                           weight, wstride, smoothing, mode);
     });
 }
 

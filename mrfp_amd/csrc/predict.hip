@@ -91,17 +91,9 @@ __global__ __launch_bounds__(kCeThreads) void upsample_argmax_kernel(const T* __
 
 // the (sum nll, count) partials of one launch, added in double in a fixed order ONTO the caller's accumulator
 __global__ __launch_bounds__(256) void predict_loss_finalize_kernel(const float* __restrict__ ws, int n, double* __restrict__ acc) {
-    __shared__ double sa[256], sb[256];
-    double a = 0.0, d = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) { a += (double)ws[2 * i]; d += (double)ws[2 * i + 1]; }
-    sa[threadIdx.x] = a;
-    sb[threadIdx.x] = d;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { acc[0] += sa[0]; acc[1] += sb[0]; }
+    double a, d;
+    ce_reduce_partials(ws, n, a, d);
+    if (threadIdx.x == 0) { acc[0] += a; acc[1] += d; }
 }
 
 // ---- colour coding ----------------------------------------------------------------------------------------------------------

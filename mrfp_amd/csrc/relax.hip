@@ -282,153 +282,30 @@ __device__ __forceinline__ void soft_pixel_grad(float (&z)[CP], int C, unsigned 
     }
 }
 
-template <typename T, int CP>
-__global__ __launch_bounds__(kCeThreads) void soft_nll_fwd_kernel(const T* __restrict__ logits, const int32_t* __restrict__ words,
-                                                                  int64_t HW, int C, const float* __restrict__ weight, int64_t wstride,
-                                                                  float* __restrict__ ws) {
-    __shared__ float sw[32];
-    const int b = blockIdx.y;
-    soft_stage_weights(sw, weight, wstride, b, C);
-    const unsigned classes = (1u << C) - 1u;
-    const T* lb = logits + (int64_t)b * HW * C;
-    const int32_t* wb = words + (int64_t)b * HW;
-    float num = 0.f, den = 0.f;
-    for (int64_t p = (int64_t)blockIdx.x * kCeThreads + threadIdx.x; p < HW; p += (int64_t)gridDim.x * kCeThreads) {
-        const unsigned S = (unsigned)wb[p] & classes;
-        if (!S) continue;
-        const T* l = lb + p * C;
-        float z[CP];
-#pragma unroll
-        for (int c = 0; c < CP; ++c) z[c] = c < C ? to_f(l[c]) : 0.f;
+// The criterion of the pixel-loop skeleton (loss_common.hpp): the target is a word, its class bits the set S; a pixel counts while S
+// is not empty.  One group of partials per image; the finalize adds 1 to each denominator (the published valid_b + 1: an
+// all-ignored image adds 0 / 1), and the backward divides by it.  Built for CP <= 32: the class counts a word holds.
+struct SoftNll {
+    static constexpr int kLdsFloats = 32, kMaxClassPad = 32, mode = MRFP_CE_IMAGE_MEAN;
+    static constexpr double kDenBias = 1.0;
+    const int32_t* target; const float* weight; int64_t wstride;
+
+    __device__ __forceinline__ void stage(float* sw, int b, int C) const { soft_stage_weights(sw, weight, wstride, b, C); }
+    __device__ __forceinline__ unsigned label(int32_t word, int C) const { return (unsigned)word & ((1u << C) - 1u); }
+    __device__ __forceinline__ bool valid(unsigned S, int) const { return S != 0u; }
+    __device__ __forceinline__ float bwd_factor(const float* __restrict__ loss, const float* __restrict__ gscale, int b) const {
+        return (gscale ? gscale[0] : 1.f) / loss[1 + b];
+    }
+    template <int CP>
+    __device__ __forceinline__ void add_loss(const float (&z)[CP], int C, unsigned S, const float* sw, float& num, float& den) const {
         num += soft_pixel_loss<CP>(z, C, S, sw);
         den += 1.f;
     }
-    ce_w_store_partial(num, den, ws);
-}
-
-// one workgroup; the nbx partials of image b in double in a fixed order: loss[0] = sum_b num_b / (valid_b + 1), loss[1 + b] = valid_b + 1
-__global__ void soft_nll_finalize_kernel(const float* __restrict__ ws, int nbx, int B, float* __restrict__ loss) {
-    __shared__ double sa[256], sb[256];
-    double total = 0.0;        // thread 0
-    for (int g = 0; g < B; ++g) {
-        const float* w = ws + 2 * (int64_t)g * nbx;
-        double a = 0.0, d = 0.0;
-        for (int i = threadIdx.x; i < nbx; i += 256) { a += w[2 * i]; d += w[2 * i + 1]; }
-        sa[threadIdx.x] = a;
-        sb[threadIdx.x] = d;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if (threadIdx.x < s) { sa[threadIdx.x] += sa[threadIdx.x + s]; sb[threadIdx.x] += sb[threadIdx.x + s]; }
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            total += sa[0] / (sb[0] + 1.0);          // the published denominator: an all-ignored image adds 0 / 1
-            loss[1 + g] = (float)(sb[0] + 1.0);
-        }
-        __syncthreads();
+    template <int CP>
+    __device__ __forceinline__ void grad(float (&g)[CP], int C, unsigned S, const float* sw, float k) const {
+        soft_pixel_grad<CP>(g, C, S, sw, k);
     }
-    if (threadIdx.x == 0) loss[0] = (float)total;
-}
-
-template <typename T, int CP>
-__global__ __launch_bounds__(kCeThreads) void soft_nll_bwd_kernel(const T* __restrict__ logits, const int32_t* __restrict__ words,
-                                                                  const float* __restrict__ loss, const float* __restrict__ gscale,
-                                                                  T* __restrict__ dlogits, int64_t HW, int C,
-                                                                  const float* __restrict__ weight, int64_t wstride) {
-    __shared__ float sw[32];
-    const int b = blockIdx.y;
-    soft_stage_weights(sw, weight, wstride, b, C);
-    const unsigned classes = (1u << C) - 1u;
-    const float k = (gscale ? gscale[0] : 1.f) / loss[1 + b];
-    const T* lb = logits + (int64_t)b * HW * C;
-    T* db = dlogits + (int64_t)b * HW * C;
-    const int32_t* wb = words + (int64_t)b * HW;
-    for (int64_t p = (int64_t)blockIdx.x * kCeThreads + threadIdx.x; p < HW; p += (int64_t)gridDim.x * kCeThreads) {
-        const unsigned S = (unsigned)wb[p] & classes;
-        const T* l = lb + p * C;
-        T* d = db + p * C;
-        float g[CP];
-#pragma unroll
-        for (int c = 0; c < CP; ++c) g[c] = 0.f;
-        if (S) {
-#pragma unroll
-            for (int c = 0; c < CP; ++c) g[c] = c < C ? to_f(l[c]) : 0.f;
-            soft_pixel_grad<CP>(g, C, S, sw, k);
-        }
-#pragma unroll
-        for (int c = 0; c < CP; ++c)
-            if (c < C) d[c] = from_f<T>(g[c]);
-    }
-}
-
-template <typename T, int CP>
-__global__ __launch_bounds__(kCeThreads) void upsample_soft_nll_fwd_kernel(const T* __restrict__ P, int ld, const int32_t* __restrict__ words,
-                                                                           int Hi, int Wi, int H, int W, int C,
-                                                                           const float* __restrict__ weight, int64_t wstride,
-                                                                           float* __restrict__ ws) {
-    __shared__ float sw[32];
-    const int b = blockIdx.y;
-    soft_stage_weights(sw, weight, wstride, b, C);
-    const unsigned classes = (1u << C) - 1u;
-    const int HW = H * W;
-    const int32_t* wb = words + (int64_t)b * HW;
-    float num = 0.f, den = 0.f;
-    for (int p = blockIdx.x * kCeThreads + threadIdx.x; p < HW; p += gridDim.x * kCeThreads) {
-        const unsigned S = (unsigned)wb[p] & classes;
-        if (!S) continue;
-        const int oh = p / W, ow = p - oh * W;
-        float z[CP];
-        up_logits<T, CP>(P, ld, Hi, Wi, H, W, C, b, oh, ow, z);
-        num += soft_pixel_loss<CP>(z, C, S, sw);
-        den += 1.f;
-    }
-    ce_w_store_partial(num, den, ws);
-}
-
-template <typename T, int CP>
-__global__ __launch_bounds__(kCeThreads) void upsample_soft_nll_bwd_kernel(const T* __restrict__ P, int ld, const int32_t* __restrict__ words,
-                                                                           const float* __restrict__ loss, const float* __restrict__ gscale,
-                                                                           T* __restrict__ dlogits, int Cd, int Hi, int Wi, int H, int W,
-                                                                           int C, const float* __restrict__ weight, int64_t wstride) {
-    constexpr int EPC = 16 / (int)sizeof(T);
-    __shared__ float sw[32];
-    const int b = blockIdx.y;
-    soft_stage_weights(sw, weight, wstride, b, C);
-    const unsigned classes = (1u << C) - 1u;
-    const float k = (gscale ? gscale[0] : 1.f) / loss[1 + b];
-    const int HW = H * W;
-    const int32_t* wb = words + (int64_t)b * HW;
-    T* db = dlogits + (int64_t)b * HW * Cd;
-    for (int p = blockIdx.x * kCeThreads + threadIdx.x; p < HW; p += gridDim.x * kCeThreads) {
-        const unsigned S = (unsigned)wb[p] & classes;
-        T* d = db + (int64_t)p * Cd;
-        float g[CP];
-#pragma unroll
-        for (int c = 0; c < CP; ++c) g[c] = 0.f;
-        if (S) {
-            const int oh = p / W, ow = p - oh * W;
-            up_logits<T, CP>(P, ld, Hi, Wi, H, W, C, b, oh, ow, g);
-            soft_pixel_grad<CP>(g, C, S, sw, k);
-        }
-#pragma unroll
-        for (int c0 = 0; c0 < CP; c0 += EPC) {
-            if (c0 < Cd) {
-                float o[EPC];
-#pragma unroll
-                for (int i = 0; i < EPC; ++i) o[i] = g[c0 + i];
-                store_f<T, EPC>(d + c0, o);
-            }
-        }
-    }
-}
-
-// by_class_pad restricted to the class counts a word holds (CP <= 32): the wider instances are never built
-template <typename F>
-static void by_word_class_pad(int C, F&& f) {
-    by_class_pad(C, [&](auto cp) {
-        if constexpr (decltype(cp)::value <= 32) f(cp);
-    });
-}
+};
 
 // what every entry that takes a class count refuses alike, each under its own name
 static int relax_check(const char* who, int64_t B, int64_t C) {
@@ -437,12 +314,9 @@ static int relax_check(const char* who, int64_t B, int64_t C) {
     return 0;
 }
 
-static int soft_nll_check(const char* who, int64_t B, int64_t C, int64_t wstride, int dtype) {
+static int soft_nll_check(const char* who, int64_t B, int64_t C, int64_t wstride) {
     if (int rc = relax_check(who, B, C)) return rc;
-    MRFP_CHECK(wstride == 0 || wstride == C, "%s: wstride must be 0 (one weight row) or C (one per image) (wstride=%lld C=%lld)", who,
-               (long long)wstride, (long long)C);
-    MRFP_CHECK(dtype_known(dtype), "%s: unknown dtype %d", who, dtype);
-    return 0;
+    return wstride_check(who, wstride, C);
 }
 
 static int clear_counts(int64_t* counts, int64_t B, int64_t C, hipStream_t st) {
@@ -528,86 +402,43 @@ int64_t mrfp_soft_nll_loss_floats(int64_t B) { return 1 + (B > 0 ? B : 1); }
 
 int mrfp_soft_nll_fwd(const void* logits, const int32_t* words, int dtype, int64_t B, int64_t HW, int64_t C, const float* weight,
                       int64_t wstride, float* ws, float* loss, void* stream) {
-    MRFP_CHECK(logits && words && ws && loss, "soft_nll_fwd: null pointer");
-    MRFP_CHECK(HW > 0, "soft_nll_fwd: bad size (HW=%lld)", (long long)HW);
-    if (int rc = mrfp::soft_nll_check("soft_nll_fwd", B, C, wstride, dtype)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int nbx = mrfp::ce_w_blocks_x(B, HW);
-    return mrfp::by_dtype(dtype, "soft_nll_fwd", [&](auto t) {
-        using T = typename decltype(t)::type;
-        mrfp::by_word_class_pad((int)C, [&](auto cp) {
-            hipLaunchKernelGGL((mrfp::soft_nll_fwd_kernel<T, decltype(cp)::value>), dim3(nbx, (unsigned)B), dim3(mrfp::kCeThreads), 0, st,
-                               (const T*)logits, words, HW, (int)C, weight, wstride, ws);
-        });
-        MRFP_LAUNCH_CHECK();
-        hipLaunchKernelGGL(mrfp::soft_nll_finalize_kernel, dim3(1), dim3(256), 0, st, ws, nbx, (int)B, loss);
-        MRFP_LAUNCH_CHECK();
-        return 0;
-    });
+    const char* who = "soft_nll_fwd";
+    MRFP_CHECK(logits && words && ws && loss, "%s: null pointer", who);
+    MRFP_CHECK(HW > 0, "%s: bad size (HW=%lld)", who, (long long)HW);
+    if (int rc = mrfp::soft_nll_check(who, B, C, wstride)) return rc;
+    return mrfp::launch_pixel_loss_fwd(who, dtype, B, mrfp::DenseRows{logits, nullptr, HW, (int)C}, mrfp::SoftNll{words, weight, wstride}, ws,
+                                       loss, (hipStream_t)stream);
 }
 
 int mrfp_soft_nll_bwd(const void* logits, const int32_t* words, const float* loss, const float* gscale, void* dlogits, int dtype,
                       int64_t B, int64_t HW, int64_t C, const float* weight, int64_t wstride, void* stream) {
-    MRFP_CHECK(logits && words && loss && dlogits, "soft_nll_bwd: null pointer");
-    MRFP_CHECK(HW > 0, "soft_nll_bwd: bad size (HW=%lld)", (long long)HW);
-    if (int rc = mrfp::soft_nll_check("soft_nll_bwd", B, C, wstride, dtype)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int nbx = mrfp::ce_w_blocks_x(B, HW);
-    return mrfp::by_dtype(dtype, "soft_nll_bwd", [&](auto t) {
-        using T = typename decltype(t)::type;
-        mrfp::by_word_class_pad((int)C, [&](auto cp) {
-            hipLaunchKernelGGL((mrfp::soft_nll_bwd_kernel<T, decltype(cp)::value>), dim3(nbx, (unsigned)B), dim3(mrfp::kCeThreads), 0, st,
-                               (const T*)logits, words, loss, gscale, (T*)dlogits, HW, (int)C, weight, wstride);
-        });
-        MRFP_LAUNCH_CHECK();
-        return 0;
-    });
+    const char* who = "soft_nll_bwd";
+    MRFP_CHECK(logits && words && loss && dlogits, "%s: null pointer", who);
+    MRFP_CHECK(HW > 0, "%s: bad size (HW=%lld)", who, (long long)HW);
+    if (int rc = mrfp::soft_nll_check(who, B, C, wstride)) return rc;
+    return mrfp::launch_pixel_loss_bwd(who, dtype, B, mrfp::DenseRows{logits, dlogits, HW, (int)C}, mrfp::SoftNll{words, weight, wstride}, loss,
+                                       gscale, (hipStream_t)stream);
 }
 
 int mrfp_upsample_soft_nll_fwd(const void* P, int64_t ld, const int32_t* words, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H,
                                int64_t W, int64_t C, const float* weight, int64_t wstride, float* ws, float* loss, void* stream) {
-    MRFP_CHECK(P && words && ws && loss, "upsample_soft_nll_fwd: null pointer");
-    MRFP_CHECK(Hi > 0 && Wi > 0 && H > 0 && W > 0 && H * W < (1LL << 30), "upsample_soft_nll_fwd: bad size");
-    if (int rc = mrfp::soft_nll_check("upsample_soft_nll_fwd", B, C, wstride, dtype)) return rc;
-    const int epc = 16 / mrfp::dtype_bytes(dtype);
-    MRFP_CHECK(ld % epc == 0 && ld >= (C + epc - 1) / epc * epc && mrfp::aligned16(P),
-               "upsample_soft_nll_fwd: the score buffer must be channel-padded to 16-byte chunks (ld=%lld)", (long long)ld);
-    hipStream_t st = (hipStream_t)stream;
-    const int nbx = mrfp::ce_w_blocks_x(B, H * W);
-    return mrfp::by_dtype(dtype, "upsample_soft_nll_fwd", [&](auto t) {
-        using T = typename decltype(t)::type;
-        mrfp::by_word_class_pad((int)C, [&](auto cp) {
-            hipLaunchKernelGGL((mrfp::upsample_soft_nll_fwd_kernel<T, decltype(cp)::value>), dim3(nbx, (unsigned)B), dim3(mrfp::kCeThreads), 0,
-                               st, (const T*)P, (int)ld, words, (int)Hi, (int)Wi, (int)H, (int)W, (int)C, weight, wstride, ws);
-        });
-        MRFP_LAUNCH_CHECK();
-        hipLaunchKernelGGL(mrfp::soft_nll_finalize_kernel, dim3(1), dim3(256), 0, st, ws, nbx, (int)B, loss);
-        MRFP_LAUNCH_CHECK();
-        return 0;
-    });
+    const char* who = "upsample_soft_nll_fwd";
+    MRFP_CHECK(P && words && ws && loss, "%s: null pointer", who);
+    if (int rc = mrfp::soft_nll_check(who, B, C, wstride)) return rc;
+    mrfp::BilinearRows src;
+    if (int rc = mrfp::bilinear_rows(who, P, ld, nullptr, 0, true, dtype, Hi, Wi, H, W, C, src)) return rc;
+    return mrfp::launch_pixel_loss_fwd(who, dtype, B, src, mrfp::SoftNll{words, weight, wstride}, ws, loss, (hipStream_t)stream);
 }
 
 int mrfp_upsample_soft_nll_bwd(const void* P, int64_t ld, const int32_t* words, const float* loss, const float* gscale, void* dlogits,
                                int64_t Cd, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int64_t C,
                                const float* weight, int64_t wstride, void* stream) {
-    MRFP_CHECK(P && words && loss && dlogits, "upsample_soft_nll_bwd: null pointer");
-    MRFP_CHECK(Hi > 0 && Wi > 0 && H > 0 && W > 0 && H * W < (1LL << 30), "upsample_soft_nll_bwd: bad size");
-    if (int rc = mrfp::soft_nll_check("upsample_soft_nll_bwd", B, C, wstride, dtype)) return rc;
-    const int epc = 16 / mrfp::dtype_bytes(dtype);
-    MRFP_CHECK(ld % epc == 0 && Cd == (C + epc - 1) / epc * epc && ld >= Cd && mrfp::aligned16(P) && mrfp::aligned16(dlogits),
-               "upsample_soft_nll_bwd: ld a 16-byte multiple, Cd = C rounded up to one (ld=%lld Cd=%lld)", (long long)ld, (long long)Cd);
-    hipStream_t st = (hipStream_t)stream;
-    const int nbx = mrfp::ce_w_blocks_x(B, H * W);
-    return mrfp::by_dtype(dtype, "upsample_soft_nll_bwd", [&](auto t) {
-        using T = typename decltype(t)::type;
-        mrfp::by_word_class_pad((int)C, [&](auto cp) {
-            hipLaunchKernelGGL((mrfp::upsample_soft_nll_bwd_kernel<T, decltype(cp)::value>), dim3(nbx, (unsigned)B), dim3(mrfp::kCeThreads), 0,
-                               st, (const T*)P, (int)ld, words, loss, gscale, (T*)dlogits, (int)Cd, (int)Hi, (int)Wi, (int)H, (int)W, (int)C,
-                               weight, wstride);
-        });
-        MRFP_LAUNCH_CHECK();
-        return 0;
-    });
+    const char* who = "upsample_soft_nll_bwd";
+    MRFP_CHECK(P && words && loss && dlogits, "%s: null pointer", who);
+    if (int rc = mrfp::soft_nll_check(who, B, C, wstride)) return rc;
+    mrfp::BilinearRows src;
+    if (int rc = mrfp::bilinear_rows(who, P, ld, dlogits, Cd, true, dtype, Hi, Wi, H, W, C, src)) return rc;
+    return mrfp::launch_pixel_loss_bwd(who, dtype, B, src, mrfp::SoftNll{words, weight, wstride}, loss, gscale, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -958,6 +958,29 @@ def add(a, b):
 # ------------------------------------------------------------------------------------------
 # cross entropy (ignore_index) -- scalar fp32 loss
 # ------------------------------------------------------------------------------------------
+def _ce_target(who, target, B, H, W):
+    target = target.contiguous()
+    if target.dtype != torch.int64 or tuple(target.shape) != (B, H, W):
+        raise _lib.MrfpHipError("%s: target must be int64 [B,H,W]" % who)
+    return target
+
+
+def _fused_loss_bwd(entry, P, target, loss, g, H, W, C, *extra):
+    """The backward tail of every fused loss: `entry` writes d(loss)/d(logits) at full resolution once, channel-padded to Cd, and the
+    gather-form bilinear backward takes it to dP.  extra: what the entry takes between C and the stream."""
+    B, ld, Hi, Wi = P.shape
+    epc = 16 // P.element_size()
+    Cd = (C + epc - 1) // epc * epc
+    gs = g.detach().float().reshape(1).contiguous()
+    dP = empty_cl(B, ld, Hi, Wi, P.dtype, P.device)
+    dlog = empty_cl(B, Cd, H, W, P.dtype, P.device)
+    call(entry, ptr(P), ld, ptr(target), ptr(loss), ptr(gs), ptr(dlog), Cd, dt(P), B, Hi, Wi, H, W, C, *extra, stream())
+    if ld != Cd:
+        dP.zero_()
+    call("mrfp_bilinear_bwd", ptr(dlog), ptr(dP), dt(P), B, Hi, Wi, H, W, Cd, ld, stream())
+    return dP
+
+
 class _CrossEntropy(torch.autograd.Function):
     """nn.CrossEntropyLoss(ignore_index=255): reference main.py:822, deepv3.py:363."""
 
@@ -965,9 +988,7 @@ class _CrossEntropy(torch.autograd.Function):
     def forward(ctx, logits, target, ignore_index):
         logits = _chk(logits, "logits")
         B, C, H, W = logits.shape
-        target = target.contiguous()
-        if target.dtype != torch.int64 or tuple(target.shape) != (B, H, W):
-            raise _lib.MrfpHipError("cross_entropy: target must be int64 [B,H,W]")
+        target = _ce_target("cross_entropy", target, B, H, W)
         npix = B * H * W
         nblk = int(_lib.lib().mrfp_ce_nblocks(npix))
         ws = torch.empty(2 * nblk, dtype=torch.float32, device=logits.device)
@@ -1032,9 +1053,7 @@ class _CrossEntropyW(torch.autograd.Function):
     def forward(ctx, logits, target, ignore_index, weight, label_smoothing, reduction, per_image):
         logits = _chk(logits, "logits")
         B, C, H, W = logits.shape
-        target = target.contiguous()
-        if target.dtype != torch.int64 or tuple(target.shape) != (B, H, W):
-            raise _lib.MrfpHipError("cross_entropy: target must be int64 [B,H,W]")
+        target = _ce_target("cross_entropy", target, B, H, W)
         weight, wstride, eps, mode = _ce_options("cross_entropy", weight, label_smoothing, reduction, per_image, B, C, logits.device)
         ws, loss = _ce_buffers(B, H * W, mode, logits.device)
         call("mrfp_ce_w_fwd", ptr(logits), ptr(target), dt(logits), B, H * W, C, int(ignore_index), ptr(weight), wstride, eps, mode,
@@ -1072,9 +1091,7 @@ class _UpsampleCrossEntropy(torch.autograd.Function):
     def forward(ctx, P, target, H, W, C, ignore_index):
         P = _chk(P, "P")
         B, ld, Hi, Wi = P.shape
-        target = target.contiguous()
-        if target.dtype != torch.int64 or tuple(target.shape) != (B, H, W):
-            raise _lib.MrfpHipError("upsample_cross_entropy: target must be int64 [B,H,W]")
+        target = _ce_target("upsample_cross_entropy", target, B, H, W)
         npix = B * H * W
         nblk = int(_lib.lib().mrfp_ce_nblocks(npix))
         ws = torch.empty(2 * nblk, dtype=torch.float32, device=P.device)
@@ -1089,18 +1106,7 @@ class _UpsampleCrossEntropy(torch.autograd.Function):
     def backward(ctx, g):
         P, target, loss = ctx.saved_tensors
         H, W, C, ignore = ctx.cfg
-        B, ld, Hi, Wi = P.shape
-        epc = 16 // P.element_size()
-        Cd = (C + epc - 1) // epc * epc
-        gs = g.detach().float().reshape(1).contiguous()
-        dP = empty_cl(B, ld, Hi, Wi, P.dtype, P.device)
-        dlog = empty_cl(B, Cd, H, W, P.dtype, P.device)
-        call("mrfp_upsample_ce_bwd", ptr(P), ld, ptr(target), ptr(loss), ptr(gs), ptr(dlog), Cd, dt(P), B, Hi, Wi, H, W, C,
-             ignore, stream())
-        if ld != Cd:
-            dP.zero_()
-        call("mrfp_bilinear_bwd", ptr(dlog), ptr(dP), dt(P), B, Hi, Wi, H, W, Cd, ld, stream())
-        return dP, None, None, None, None, None
+        return _fused_loss_bwd("mrfp_upsample_ce_bwd", P, target, loss, g, H, W, C, ignore), None, None, None, None, None
 
 
 class _UpsampleCrossEntropyW(torch.autograd.Function):
@@ -1110,9 +1116,7 @@ class _UpsampleCrossEntropyW(torch.autograd.Function):
     def forward(ctx, P, target, H, W, C, ignore_index, weight, label_smoothing, reduction, per_image):
         P = _chk(P, "P")
         B, ld, Hi, Wi = P.shape
-        target = target.contiguous()
-        if target.dtype != torch.int64 or tuple(target.shape) != (B, H, W):
-            raise _lib.MrfpHipError("upsample_cross_entropy: target must be int64 [B,H,W]")
+        target = _ce_target("upsample_cross_entropy", target, B, H, W)
         weight, wstride, eps, mode = _ce_options("upsample_cross_entropy", weight, label_smoothing, reduction, per_image, B, C, P.device)
         ws, loss = _ce_buffers(B, H * W, mode, P.device)
         call("mrfp_upsample_ce_w_fwd", ptr(P), ld, ptr(target), dt(P), B, Hi, Wi, H, W, C, int(ignore_index), ptr(weight), wstride,
@@ -1125,17 +1129,7 @@ class _UpsampleCrossEntropyW(torch.autograd.Function):
     def backward(ctx, g):
         P, target, loss, weight = ctx.saved_tensors
         H, W, C, ignore, wstride, eps, mode = ctx.cfg
-        B, ld, Hi, Wi = P.shape
-        epc = 16 // P.element_size()
-        Cd = (C + epc - 1) // epc * epc
-        gs = g.detach().float().reshape(1).contiguous()
-        dP = empty_cl(B, ld, Hi, Wi, P.dtype, P.device)
-        dlog = empty_cl(B, Cd, H, W, P.dtype, P.device)
-        call("mrfp_upsample_ce_w_bwd", ptr(P), ld, ptr(target), ptr(loss), ptr(gs), ptr(dlog), Cd, dt(P), B, Hi, Wi, H, W, C,
-             ignore, ptr(weight), wstride, eps, mode, stream())
-        if ld != Cd:
-            dP.zero_()
-        call("mrfp_bilinear_bwd", ptr(dlog), ptr(dP), dt(P), B, Hi, Wi, H, W, Cd, ld, stream())
+        dP = _fused_loss_bwd("mrfp_upsample_ce_w_bwd", P, target, loss, g, H, W, C, ignore, ptr(weight), wstride, eps, mode)
         return dP, None, None, None, None, None, None, None, None, None
 
 
@@ -1308,17 +1302,7 @@ class _UpsampleSoftNLL(torch.autograd.Function):
     def backward(ctx, g):
         P, relaxed, loss, weight = ctx.saved_tensors
         H, W, C, wstride = ctx.cfg
-        B, ld, Hi, Wi = P.shape
-        epc = 16 // P.element_size()
-        Cd = (C + epc - 1) // epc * epc
-        gs = g.detach().float().reshape(1).contiguous()
-        dP = empty_cl(B, ld, Hi, Wi, P.dtype, P.device)
-        dlog = empty_cl(B, Cd, H, W, P.dtype, P.device)
-        call("mrfp_upsample_soft_nll_bwd", ptr(P), ld, ptr(relaxed), ptr(loss), ptr(gs), ptr(dlog), Cd, dt(P), B, Hi, Wi, H, W, C,
-             ptr(weight), wstride, stream())
-        if ld != Cd:
-            dP.zero_()
-        call("mrfp_bilinear_bwd", ptr(dlog), ptr(dP), dt(P), B, Hi, Wi, H, W, Cd, ld, stream())
+        dP = _fused_loss_bwd("mrfp_upsample_soft_nll_bwd", P, relaxed, loss, g, H, W, C, ptr(weight), wstride)
         return dP, None, None, None, None, None
 
 
