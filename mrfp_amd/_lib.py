@@ -112,7 +112,7 @@ def source_hash() -> str:
     root = os.path.dirname(_HERE)
     files = [HEADER] + [os.path.join(_HERE, "csrc", f) for f in sorted(os.listdir(os.path.join(_HERE, "csrc")))
                         if f.endswith((".hip", ".hpp"))]
-    files += [os.path.join(_HERE, f) for f in ("ops.py", "conv.py", "deepv3.py", "harness.py")]
+    files += [os.path.join(_HERE, f) for f in ("ops.py", "conv.py", "skipgrad.py", "deepv3.py", "harness.py")]
     for f in files:
         h.update(os.path.relpath(f, root).encode())
         with open(f, "rb") as fh:

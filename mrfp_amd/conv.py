@@ -20,6 +20,7 @@ from . import _lib
 from ._lib import call, dt, ptr, stream
 from .ops import CL, GRAD_DEFERRED, _chk, channel_sums, empty_cl, grad_sink, notify_grad, wgrad_workspace, zeros_cl
 from .ops import _inside_autograd_engine as _in_backward
+from .skipgrad import ALIAS, GATE, LOWRANK, AliasCell, alias_cell, gateable, mask_possible, ungate, unlowrank
 
 _PACKS = {}      # id(weight Parameter) -> {key: _Pack}; entry dropped when the Parameter dies
 FUSE_STATS = [_os.environ.get("MRFP_FUSE_STATS", "1") != "0"]   # conv epilogues emit BatchNorm partial statistics for bias-free convolutions
@@ -646,22 +647,7 @@ def _boundary_hook(_grad):
 
 
 GATED_SKIP_HITS = [0]       # dgrad launches that applied a residual tail's gate to their addend (tests)
-
-
-def ungate(t):
-    """The plain gradient for a tensor that carries a `_mrfp_gate` (sign mask, version) tag: t * [mask bit set].  Tensors
-    without the tag (and None) pass through."""
-    g = getattr(t, "_mrfp_gate", None) if t is not None else None
-    if g is None:
-        return t
-    if g[1] != t._version:
-        raise _lib.MrfpHipError("a gated skip gradient was modified in place before it reached its consumer")
-    B, C, H, W = t.shape
-    out = empty_cl(B, C, H, W, t.dtype, t.device)
-    call("mrfp_affine_bwd_mask", ptr(t), None, ptr(g[0]), ptr(out), None, dt(t), B, H, W, C, None, None, None, 0, stream())
-    return out
-
-
+# (the hand-off itself -- the alias's cell, the GATE / LOWRANK tags, ungate / unlowrank -- is skipgrad.py)
 # The input gradient of a shared pointwise classifier on a convolution's skip alias (_SharedConv1x1Pair: `final2` of the MRFP+ head on
 # the 256-channel half-resolution HRFP map) has rank <= 32 per pixel: dskip = dP . Wf.  Instead of writing it (1.2 GB at the bench
 # shape) and reading it back as the dgrad's addend, the pair returns a storage-less stand-in tagged with its two factors and the
@@ -669,21 +655,6 @@ def ungate(t):
 LOWRANK_SKIP = [_os.environ.get("MRFP_LOWRANK_SKIP", "1") != "0"]
 LOWRANK_SKIP_HITS = [0]     # dgrad launches that took a skip gradient as its two low-rank factors (tests)
 _LOWRANK_K = 32             # the K of mrfp_conv_fwd_lowrank: the classifier's padded score planes
-
-
-def unlowrank(t):
-    """The plain gradient for a tensor that carries a `_mrfp_lowrank` (dP, dgrad pack, K, version) tag: the pointwise dgrad launch
-    dP . Wd the tag stands for.  Tensors without the tag (and None) pass through."""
-    lr = getattr(t, "_mrfp_lowrank", None) if t is not None else None
-    if lr is None:
-        return t
-    dp, wd, K, version = lr
-    if version != t._version:
-        raise _lib.MrfpHipError("a low-rank skip gradient was modified in place before it reached its consumer")
-    B, C, H, W = t.shape
-    out = empty_cl(B, C, H, W, dp.dtype, dp.device)
-    call("mrfp_conv_fwd", ptr(dp), ptr(wd), None, ptr(out), dt(dp), B, H, W, K, C, C, 1, 1, H, W, 1, 0, 0, 1, 1, None, None, stream())
-    return out
 
 
 def _dgrad_lowrank_ok(dtype, B, H, W, Cphys, Nphys, R, S, Ho, Wo, stride, pad_h, pad_w, dil):
@@ -701,7 +672,8 @@ def L_single(B, H, W, Cphys, Ho, Wo, Nphys, esz):
 
 class _Conv2d(torch.autograd.Function):
     """want_skip: also return an alias of x for a skip connection; the gradient arriving on that alias is added by
-    the dgrad kernel's epilogue (no separate accumulation pass over the activation).
+    the dgrad kernel's epilogue (no separate accumulation pass over the activation); it may arrive behind a GATE or LOWRANK tag, and
+    conv2d() hangs the alias's skipgrad.AliasCell (uses, gate_issued, lowrank_issued, lowrank_ok) on the alias and on this node.
     stats: the rows the epilogue writes its output statistics into (sized by conv2d(), which tags the output with them), or None;
     wtab: the pixel multiplicities that weight them (conv2d(stat_resize=))."""
 
@@ -730,23 +702,11 @@ class _Conv2d(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, dskip=None):
         x, weight, bias = ctx.saved_tensors
-        cell = getattr(ctx, "_mrfp_cell", None)
-        if cell is not None and cell[1]:
-            # a residual tail handed its UNMASKED incoming gradient to this alias (ops._BatchNormAct.backward): only the tagged
-            # tensor itself may arrive here.  Anything else means a consumer the use count did not see (a raw torch op on the
-            # alias) made autograd sum gradients into an untagged tensor -- fail loudly, the sum would be silently wrong
-            g = getattr(dskip, "_mrfp_gate", None) if dskip is not None else None
-            if g is None or g[1] != dskip._version:
-                raise _lib.MrfpHipError("a gated skip gradient reached its convolution without its gate: the skip alias was "
-                                        "also consumed by an operator outside mrfp_amd.ops (set MRFP_GATED_SKIP=0)")
-            cell[1] = False
-        lr = getattr(dskip, "_mrfp_lowrank", None) if dskip is not None else None
-        if cell is not None and cell[2]:
-            # the same for the low-rank stand-in of _SharedConv1x1Pair.backward: it has no storage, a sum with it is garbage
-            if lr is None or lr[3] != dskip._version:
-                raise _lib.MrfpHipError("a low-rank skip gradient reached its convolution without its factors: the skip alias was "
-                                        "also consumed by an operator outside mrfp_amd.ops (set MRFP_LOWRANK_SKIP=0)")
-            cell[2] = False
+        cell = getattr(ctx, ALIAS, None)
+        if cell is not None:
+            # a residual tail sent its UNMASKED incoming gradient to this alias (ops._BatchNormAct.backward), or the shared classifier
+            # a stand-in without storage (_SharedConv1x1Pair.backward): only that tagged tensor may arrive here, anything else raises
+            cell.redeem(dskip)
         if dy is None:            # only the skip alias was used downstream
             return (unlowrank(ungate(dskip)),) + (None,) * 10
         stride, pad_h, pad_w, dil, Nphys, Ho, Wo = ctx.cfg
@@ -758,22 +718,22 @@ class _Conv2d(torch.autograd.Function):
             pk = get_pack(weight, bias, x.dtype, Cphys, Nphys)
             dx = empty_cl(B, Cphys, H, W, x.dtype, x.device)
             gate = None
+            lr = LOWRANK.fetch(dskip) if dskip is not None else None
             if lr is not None:
                 # the factors go to the dgrad kernel as one more k step; a launch that cannot take them gets the plain gradient
-                if (lr[3] == dskip._version and lr[2] == _LOWRANK_K and lr[0].dtype == dy.dtype == x.dtype and dskip.shape == dx.shape
+                if (lr.K == _LOWRANK_K and lr.dp.dtype == dy.dtype == x.dtype and dskip.shape == dx.shape
                         and _dgrad_lowrank_ok(x.dtype, B, H, W, Cphys, Nphys, R, S, Ho, Wo, stride, pad_h, pad_w, dil)):
                     dskip = None
                 else:
                     dskip, lr = unlowrank(dskip), None
             if dskip is not None:
-                g = getattr(dskip, "_mrfp_gate", None)
+                g = GATE.fetch(dskip)
                 if g is not None:
                     # the skip-connection gradient of a residual tail arrives UNMASKED with that tail's sign mask attached
                     # (ops._BatchNormAct.backward): the dgrad epilogue applies the gate while it adds -- dy * [y > 0] is never
                     # written or re-read.  Anything this launch cannot do that way gets the plain gradient.
-                    if (g[1] == dskip._version and dskip.dtype == x.dtype and x.element_size() == 2
-                            and Cphys % 8 == 0 and dskip.shape == dx.shape and dskip.is_contiguous(memory_format=CL)):
-                        gate = g[0]
+                    if mask_possible(x) and gateable(dskip, x):
+                        gate = g.mask
                     else:
                         dskip = ungate(dskip)
                 dskip = _chk(dskip, "dskip")
@@ -782,7 +742,7 @@ class _Conv2d(torch.autograd.Function):
             _lib.NOTE[0] = (N, C)
             if lr is not None:
                 call("mrfp_conv_fwd_lowrank", ptr(dy), ptr(pk.wd), None, ptr(dx), dt(dy), B, Ho, Wo, Nphys, Cphys, Cphys, R, S, H, W,
-                     1, dil * (R - 1) - pad_h, dil * (S - 1) - pad_w, dil, stride, None, None, ptr(lr[0]), ptr(lr[1]), lr[2], stream())
+                     1, dil * (R - 1) - pad_h, dil * (S - 1) - pad_w, dil, stride, None, None, ptr(lr.dp), ptr(lr.wd), lr.K, stream())
                 LOWRANK_SKIP_HITS[0] += 1
             elif gate is not None:
                 call("mrfp_conv_fwd_gated", ptr(dy), ptr(pk.wd), None, ptr(dx), dt(dy), B, Ho, Wo, Nphys, Cphys, Cphys, R, S, H, W,
@@ -838,8 +798,9 @@ class _SharedConv1x1Pair(torch.autograd.Function):
         ctx.save_for_backward(x1, x2, weight, bias)
         ctx.Nphys = Nphys
         # x2 is a convolution's skip alias whose dgrad can take this operator's input gradient as its two factors (conv2d marked it):
-        # the alias's cell -- [consumers counted by _chk, gated gradient issued, low-rank gradient issued] -- is read in backward
-        ctx.lr_cell = getattr(x2, "_mrfp_uses", None) if getattr(x2, "_mrfp_lowrank_ok", False) else None
+        # the alias's cell (skipgrad.AliasCell) is read in backward
+        cell = alias_cell(x2)
+        ctx.x2_alias = cell if cell is not None and cell.lowrank_ok else None
         ctx.set_materialize_grads(False)
         return ys[0], ys[1]
 
@@ -851,21 +812,21 @@ class _SharedConv1x1Pair(torch.autograd.Function):
         pk = get_pack(weight, bias, x1.dtype, C, Nphys)
         dxs, dws = [], []
         db = None
-        for x, dy, need_dx, cell in ((x1, dy1, ctx.needs_input_grad[0], None), (x2, dy2, ctx.needs_input_grad[1], ctx.lr_cell)):
+        for x, dy, need_dx, cell in ((x1, dy1, ctx.needs_input_grad[0], None), (x2, dy2, ctx.needs_input_grad[1], ctx.x2_alias)):
             if dy is None:
                 dxs.append(None)
                 continue
             dy = _chk(dy, "dy")
             B, _, H, W = x.shape
             dx = None
-            if (need_dx and cell is not None and LOWRANK_SKIP[0] and cell[0] == 1 and Nphys == _LOWRANK_K and dy.dtype == x.dtype
+            if (need_dx and cell is not None and LOWRANK_SKIP[0] and cell.sole_consumer() and Nphys == _LOWRANK_K and dy.dtype == x.dtype
                     and x.element_size() == 2):
                 # this operator is the alias's only consumer: nothing behind dx but the producing convolution's dgrad, which
                 # multiplies dy . Wd itself -- dx is a stand-in without storage (an expanded scalar) that carries the factors
                 # (never read: torch.empty, not zeros -- no fill launch)
                 dx = torch.empty((), dtype=x.dtype, device=x.device).expand(B, C, H, W)
-                dx._mrfp_lowrank = (dy, pk.wd, Nphys, dx._version)
-                cell[2] = True          # told to that convolution: anything but this tagged tensor arriving there raises
+                LOWRANK.attach(dx, dy, pk.wd, Nphys)
+                cell.promise_lowrank()  # told to that convolution: anything but this tagged tensor arriving there raises
             elif need_dx:
                 dx = empty_cl(B, C, H, W, x.dtype, x.device)
                 call("mrfp_conv_fwd", ptr(dy), ptr(pk.wd), None, ptr(dx), dt(dy), B, H, W, Nphys, C, C, 1, 1, H, W, 1, 0, 0, 1, 1,
@@ -954,15 +915,10 @@ def conv2d(x, weight, bias, stride, padding, dilation, phys_out: Optional[int] =
     out = _Conv2d.apply(x, weight, bias, st, ph, pw, dl, Nphys, want_skip, stats, wtab)
     y, skip = out if want_skip else (out, None)
     if skip is not None:
-        skip._mrfp_skip_alias = True      # its gradient goes to this convolution's dgrad epilogue and nowhere else
-        # [operators that consumed the alias so far (ops._chk): a gated gradient needs exactly one, a gated gradient was issued]
-        # ..., a low-rank gradient was issued (_SharedConv1x1Pair.backward)]
-        skip._mrfp_uses = [0, False, False]
-        if (LOWRANK_SKIP[0] and y.grad_fn is not None and x.requires_grad
-                and _dgrad_lowrank_ok(x.dtype, B, H, W, Cphys, Nphys, R, S, Ho, Wo, st, ph, pw, dl)):
-            skip._mrfp_lowrank_ok = True  # this convolution's dgrad can take the alias's gradient as low-rank factors
-        if y.grad_fn is not None:
-            y.grad_fn._mrfp_cell = skip._mrfp_uses     # (the autograd node IS the ctx of _Conv2d.backward)
+        # an alias (skipgrad): its gradient goes to this convolution's dgrad epilogue and nowhere else -- which can take it as
+        # low-rank factors where the launch plan says so
+        AliasCell(skip, y.grad_fn, bool(LOWRANK_SKIP[0] and y.grad_fn is not None and x.requires_grad
+                                         and _dgrad_lowrank_ok(x.dtype, B, H, W, Cphys, Nphys, R, S, Ho, Wo, st, ph, pw, dl)))
     if stats is not None and (phys_out is not None or Nphys == N):
         # consumed by ops.batch_norm_act (statistics pass skipped).  final: the rows a BatchNorm finalize should read (compacted for
         # large launches); weighted statistics count the elements of the RESIZED tensor, have no per-image use, and the plan

@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import call, dt, ptr, stream
+from .skipgrad import ALIAS, GATE, AliasCell, gateable, mask_possible, ungate
 
 CL = torch.channels_last
 
@@ -70,9 +71,9 @@ def zeros_cl(B, C, H, W, dtype, device) -> torch.Tensor:
 def _chk(x: torch.Tensor, name="x") -> torch.Tensor:
     if not x.is_cuda:
         raise _lib.MrfpHipError("%s must live on the GPU (got %s): the HIP path has no CPU fallback" % (name, x.device))
-    uses = getattr(x, "_mrfp_uses", None)
-    if uses is not None:          # a convolution's skip alias (conv.conv2d(..., want_skip=True)): count the operators that consume it
-        uses[0] += 1
+    cell = getattr(x, ALIAS, None)
+    if cell is not None:          # a convolution's skip alias (conv.conv2d(..., want_skip=True)): count the operators that consume it
+        cell.use()
     if x.dim() != 4 or not x.is_contiguous(memory_format=CL):
         x = to_cl(x)
     return x
@@ -381,7 +382,7 @@ RELU6_GATE_HITS = [0]      # ReLU6 backward passes that gated with mrfp_mask_gat
 
 def _keeps_sign_mask(x, relu, res, plan):
     """Residual BatchNorm+ReLU on 16-bit activations: the apply pass writes the sign of its output as one bit per element."""
-    return bool(relu and res is not None and plan is None and SIGN_MASK[0] and x.element_size() == 2 and x.shape[1] % 8 == 0)
+    return bool(relu and res is not None and plan is None and SIGN_MASK[0] and mask_possible(x))
 
 
 class _BatchNormAct(torch.autograd.Function):
@@ -440,14 +441,11 @@ class _BatchNormAct(torch.autograd.Function):
         ctx.ymask = _keeps_sign_mask(x, relu, res, plan)
         # res is the skip alias of a convolution (conv.conv2d(..., want_skip=True)): its gradient is consumed by that
         # convolution's dgrad epilogue only, which can apply the gate itself -- backward then hands it the incoming
-        # gradient as it is, with the mask attached, instead of writing dy * [y > 0]
-        ctx.gate_skip = bool(ctx.ymask and GATED_SKIP[0] and getattr(res, "_mrfp_skip_alias", False))
+        # gradient as it is, with the mask attached, instead of writing dy * [y > 0] -- provided this tail stays the alias's ONLY
+        # consumer (skipgrad: the cell's use count is read in backward, when the whole forward has run)
+        ctx.res_alias = getattr(res, ALIAS, None) if ctx.ymask and GATED_SKIP[0] else None
         # this layer itself can take a gated gradient: plain BatchNorm (no activation, no residual, no resize), 16-bit, whole mask bytes
-        ctx.gate_ok = bool(act == ACT_NONE and res is None and plan is None and training and x.element_size() == 2 and C % 8 == 0)
-        # ... provided this tail stays the alias's ONLY consumer: with a second one autograd sums the two gradients into a fresh,
-        # untagged tensor and the unmasked one would be used as if it were masked.  Every operator of this layer counts its use
-        # of the alias (_chk); the count is read in backward, when the whole forward has run.
-        ctx.alias_uses = getattr(res, "_mrfp_uses", None)
+        ctx.gate_ok = bool(act == ACT_NONE and res is None and plan is None and training and mask_possible(x))
         keep = None
         if relu6:
             y = empty_cl(B, C, Ho, Wo, x.dtype, dev)
@@ -473,19 +471,14 @@ class _BatchNormAct(torch.autograd.Function):
         # its output as able to take that): the two passes below then gate dy while they read it, and dy * [out > 0] of the tail
         # is never written.  As in conv._Conv2d.backward: if the gate was promised and something else arrives, fail loudly.
         gate = None
-        cell = getattr(ctx, "_mrfp_cell", None)
-        g = getattr(dy, "_mrfp_gate", None)
-        if cell is not None and cell[1]:
-            if g is None or g[1] != dy._version:
-                raise _lib.MrfpHipError("a gated gradient reached its BatchNorm without its gate: the layer's output was also "
-                                        "consumed by an operator outside mrfp_amd.ops (set MRFP_GATED_SKIP=0)")
-            cell[1] = False
+        cell = getattr(ctx, ALIAS, None)
+        if cell is not None:
+            cell.redeem(dy, bn=True)
+        g = GATE.fetch(dy)
         if g is not None:
-            if (g[1] == dy._version and ctx.gate_ok and dy.dtype == x.dtype and dy.shape == x.shape
-                    and dy.is_contiguous(memory_format=CL)):
-                gate = g[0]
+            if ctx.gate_ok and gateable(dy, x):
+                gate = g.mask
             else:
-                from .conv import ungate
                 dy = ungate(dy)
         dy = _chk(dy, "dy")
         plan = ctx.plan
@@ -500,7 +493,7 @@ class _BatchNormAct(torch.autograd.Function):
         elif ctx.ymask:
             mask = keep
         elif ctx.act == ACT_RELU6:
-            if x.element_size() == 2 and C % 8 == 0 and dy.dtype == x.dtype:
+            if mask_possible(x) and dy.dtype == x.dtype:
                 mask = keep
             else:
                 gated = torch.empty_like(dy, memory_format=CL)
@@ -535,12 +528,12 @@ class _BatchNormAct(torch.autograd.Function):
             dx = empty_cl(B, C, Ho, Wo, dy.dtype, dy.device)
             dres = dres_out = None
             if ctx.ymask:
-                if ctx.gate_skip and ctx.needs_input_grad[5] and ctx.alias_uses is not None and ctx.alias_uses[0] == 1:
-                    dres = dy.view_as(dy)                  # unmasked; the consumer applies the mask (conv._Conv2d.backward / conv.ungate)
-                    dres._mrfp_gate = (mask, dres._version)
-                    # told to the convolution that owns the alias: if what reaches it is not this tagged tensor (a consumer of the
+                if ctx.res_alias is not None and ctx.needs_input_grad[5] and ctx.res_alias.sole_consumer():
+                    dres = dy.view_as(dy)                  # unmasked; the consumer applies the mask (conv._Conv2d.backward / ungate)
+                    GATE.attach(dres, mask)
+                    # told to the node that owns the alias: if what reaches it is not this tagged tensor (a consumer of the
                     # alias that bypassed _chk made autograd sum it into a fresh one), it raises instead of using it as if it were masked
-                    ctx.alias_uses[1] = True
+                    ctx.res_alias.promise_gate()
                 else:
                     dres = dres_out = empty_cl(B, C, Ho, Wo, dy.dtype, dy.device)
             call("mrfp_affine_bwd_mask", ptr(dy), ptr(x), ptr(mask), ptr(dx), ptr(dres_out), dt(dy), B, Ho, Wo, C, ptr(P), ptr(Q),
@@ -566,12 +559,10 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, *, training, mome
                             ACT_RELU if relu else ACT_NONE, plan, True, ps[1] if ps is not None else None)
     _tag_planestats(y, ps)
     if (GATED_BN[0] and GATED_SKIP[0] and SIGN_MASK[0] and not relu and res is None and plan is None and training and y.grad_fn is not None
-            and y.element_size() == 2 and y.shape[1] % 8 == 0):
+            and mask_possible(y)):
         # the plain BatchNorm of a downsample branch: a residual tail that consumes this output (and nothing else does: the use
         # count) may send its gradient gated -- see _BatchNormAct.backward.  Same protocol as a convolution's skip alias.
-        y._mrfp_skip_alias = True
-        y._mrfp_uses = [0, False]
-        y.grad_fn._mrfp_cell = y._mrfp_uses
+        AliasCell(y, y.grad_fn)
     return y
 
 

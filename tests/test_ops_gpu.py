@@ -624,7 +624,7 @@ def test_gated_skip_gradient_equals_the_materialised_one():
     UNMASKED dy + the mask and its dgrad epilogue gates the addend (mrfp_conv_fwd_gated) -- every parameter gradient of a
     ResNet-50 trunk must be bit-identical with the path that writes the masked gradient, and the gated launches must be the
     blocks without a downsample branch (12 of 16)."""
-    from mrfp_amd import conv
+    from mrfp_amd import conv, skipgrad
     from mrfp_amd.config import cfg
     from mrfp_amd.network import Resnet
     o = ops()
@@ -653,7 +653,7 @@ def test_gated_skip_gradient_equals_the_materialised_one():
         # the stand-alone form of the gate (what a consumer that cannot fuse it gets)
         t = torch.randn(2, 64, 5, 7, device=DEV).bfloat16().contiguous(memory_format=torch.channels_last)
         bits = torch.randint(0, 256, (t.numel() // 8,), dtype=torch.uint8, device=DEV)
-        t._mrfp_gate = (bits, t._version)
+        skipgrad.GATE.attach(t, bits)
         ref = t.permute(0, 2, 3, 1).reshape(-1, 8).float() * torch.stack([(bits >> i) & 1 for i in range(8)], 1).float()
         out = conv.ungate(t).permute(0, 2, 3, 1).reshape(-1, 8).float()
         assert torch.equal(out, ref)
