@@ -315,6 +315,41 @@ int mrfp_upsample_soft_nll_bwd(const void* P, int64_t ld, const int32_t* words, 
                                void* dlogits, int64_t Cd, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
                                int64_t C, const float* weight, int64_t wstride, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Online hard example mining for the cross entropy (csrc/ohem.hip): the exact kept set of a batch on the device.  Replaces the
+ * OHEM criterion (the published OhemCrossEntropy2dTensor; its source is not in the reference tree) a caller hands to DeepV3Plus as
+ * `criterion` / `criterion_aux` (network/deepv3.py:111), which on the stock path materialises the full-resolution fp32 logits,
+ * soft-maxes them, sorts every probability and branches on a host value.  Build-defined, DESIGN.md section 8:
+ *
+ * A pixel is valid iff its label t != ignore_index and 0 <= t < C.  N = valid pixels of the batch (of this rank: the selection is
+ * per rank, as the published form is per replica).  p = softmax(z)[t] in fp32 for a valid pixel (a NaN is stored as 0x7fc00000).
+ *     N == 0 or min_kept > N:  every valid pixel is kept                                                   (mode 0, theta = +inf)
+ *     otherwise:  theta = thresh; if min_kept > 0, q = the min_kept-th smallest p of the valid pixels (from 1; NaN sorts last, as
+ *                 torch.sort) and theta = q where q > thresh (a NaN q leaves thresh);  kept = valid and p <= theta: every tie at
+ *                 theta is kept, a NaN p never                                        (mode 1: theta == thresh, mode 2: theta == q)
+ * masked[i] = t_i where kept, ignore_index elsewhere.  The loss is CrossEntropyLoss(weight, ignore_index, 'mean') against masked
+ * (mrfp_ce_* / mrfp_upsample_ce_* above; nothing kept: 0/0 = NaN, as torch); the selection is a constant for the backward.
+ *
+ * prob: float [B][HW], p of a valid pixel, the sentinel 2.0f for an invalid one.  The upsample form computes p from the class
+ * vector rounded to the storage type, the logits mrfp_bilinear_fwd would store.  masked: int64 [B][HW].
+ * ws: mrfp_ohem_ws_bytes(B, HW) bytes (cleared by the entry; -1 for a size the entries refuse).  Its first words are the state,
+ * uint32: [0] N, [1] kept pixels, [2] bits of theta, [3] mode.  Nothing waits for the host or reads a device value there: the
+ * regime is decided inside the kernels, so a call can be captured in a graph.  Counts are integer sums: two runs are bit-identical.
+ *
+ * mrfp_select_kth replaces the sort of the published form: out[0] = the k-th smallest (from 1) element of x[n], exactly, by a
+ * three-level radix select (11 + 11 + 10 bits) on the bit patterns.  x: non-negative floats (unsigned order of the bits is then
+ * float order; NaN last); elements equal to the sentinel 2.0f are skipped and k counts the others; k above their number: NaN.
+ * ws as above.
+ * ------------------------------------------------------------------------------------------- */
+int64_t mrfp_ohem_ws_bytes(int64_t B, int64_t HW);
+int mrfp_select_kth(const float* x, int64_t n, int64_t k, void* ws, float* out, void* stream);
+int mrfp_ohem_target(const void* logits, const int64_t* target, int dtype, int64_t B, int64_t HW, int64_t C,
+                     int64_t ignore_index, float thresh, int64_t min_kept, float* prob, int64_t* masked, void* ws,
+                     void* stream);
+int mrfp_upsample_ohem_target(const void* P, int64_t ld, const int64_t* target, int dtype, int64_t B, int64_t Hi, int64_t Wi,
+                              int64_t H, int64_t W, int64_t C, int64_t ignore_index, float thresh, int64_t min_kept,
+                              float* prob, int64_t* masked, void* ws, void* stream);
+
 /* Eval: argmax over classes + 19x19 confusion histogram on the device (reference main.py:898-909,
  * metrics.py:122-126): hist[num_classes*gt + pred] += 1 for gt in [0,num_classes).  hist: int64
  * [C*C], accumulated (not cleared).  pred (optional, uint8 [npix]) receives the arg-max. */

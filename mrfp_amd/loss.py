@@ -12,6 +12,12 @@ the reference's transforms/transforms.py:75-124 (`jointwtborder`, utils/misc.py:
 either: include/mrfp_hip.h and DESIGN.md section 8 hold the definition.  The published form builds a [B, C+1, H, W] uint8 multi-hot on
 the host and copies it back every step for the class histogram; here a relaxed target is one int32 word per pixel (ops.relax_labels),
 and relaxation, histogram, weights and loss are device kernels (csrc/relax.hip).
+
+OhemCrossEntropy2d is the online-hard-example-mining cross entropy of the same lineage (the published OhemCrossEntropy2dTensor; its
+source is not in the reference tree: include/mrfp_hip.h and DESIGN.md section 8 hold the definition).  The published form soft-maxes
+the full-resolution logits, sorts every probability and branches on a host value; here the kept set is chosen by device kernels
+with no host wait (csrc/ohem.hip: probability plane, exact radix select, masked target) and the loss is the fused cross entropy on
+the masked target.
 """
 from __future__ import annotations
 
@@ -20,7 +26,7 @@ from torch import nn
 
 from . import ops
 
-__all__ = ["ImageBasedCrossEntropyLoss2d", "ImgWtLossSoftNLL", "fused_ce_kwargs", "fused_loss"]
+__all__ = ["ImageBasedCrossEntropyLoss2d", "ImgWtLossSoftNLL", "OhemCrossEntropy2d", "fused_ce_kwargs", "fused_loss"]
 
 
 class ImageBasedCrossEntropyLoss2d(nn.Module):
@@ -93,12 +99,39 @@ class ImgWtLossSoftNLL(nn.Module):
         return self.fused(inputs, target)
 
 
+class OhemCrossEntropy2d(nn.Module):
+    """nn.CrossEntropyLoss(weight, ignore_index) over the pixels the OHEM rule keeps: the valid pixels whose probability of the true
+    class is at most max(thresh, the min_kept-th smallest such probability of the batch); every valid pixel when the batch has fewer
+    than min_kept.  The selection is per rank and a constant for the backward."""
+
+    def __init__(self, ignore_index=255, thresh=0.7, min_kept=100000, weight=None):
+        super().__init__()
+        self.thresh, self.min_kept = ops._ohem_args("OhemCrossEntropy2d", thresh, min_kept)
+        self.ignore_index = int(ignore_index)
+        # moves with the model, stays out of its state_dict
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32).detach().clone(),
+                             persistent=False)
+
+    def fused(self, logits, gts, size=None, channels=None):
+        """The loss on the kernels: of dense logits, or with `size` of the channel-padded low-resolution scores."""
+        if size is not None:
+            return ops.upsample_ohem_cross_entropy(logits, gts, size, channels, self.ignore_index, thresh=self.thresh,
+                                                   min_kept=self.min_kept, weight=self.weight)
+        return ops.ohem_cross_entropy(logits, gts, self.ignore_index, thresh=self.thresh, min_kept=self.min_kept, weight=self.weight)
+
+    def forward(self, inputs, targets):
+        return self.fused(inputs, targets)
+
+
 def fused_ce_kwargs(criterion):
     """The keyword arguments with which ops.cross_entropy / ops.upsample_cross_entropy compute `criterion`, or None for a criterion
     they cannot (reduction='none', a foreign module): that one keeps the stock call on the full-resolution fp32 logits.  `weight` is
     a tensor, None, or -- for the per-image criterion -- a callable of the label map (fused_loss calls it).  ImgWtLossSoftNLL is not a
-    cross entropy: its entry is dict(soft_nll=<its own fused call>), which fused_loss calls with (logits, gts, size, channels)."""
+    cross entropy: its entry is dict(soft_nll=<its own fused call>), which fused_loss calls with (logits, gts, size, channels);
+    OhemCrossEntropy2d chooses its pixels first: dict(ohem=<its own fused call>), called the same way."""
     c = criterion
+    if isinstance(c, OhemCrossEntropy2d):
+        return dict(ohem=c.fused)
     if isinstance(c, ImgWtLossSoftNLL):          # not a cross entropy: fused_loss hands the call to the criterion's own kernels
         return dict(soft_nll=c.fused)
     if isinstance(c, ImageBasedCrossEntropyLoss2d):
@@ -115,8 +148,9 @@ def fused_loss(criterion, logits, gts, size=None, channels=None):
     kw = fused_ce_kwargs(criterion)
     if kw is None:
         return None
-    if "soft_nll" in kw:
-        return kw["soft_nll"](logits, gts, size, channels)
+    for own in ("soft_nll", "ohem"):
+        if own in kw:
+            return kw[own](logits, gts, size, channels)
     ignore = kw.pop("ignore_index")
     if callable(kw["weight"]):
         kw["weight"] = kw["weight"](gts)

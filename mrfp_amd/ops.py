@@ -1302,6 +1302,89 @@ def upsample_soft_nll(P, relaxed, size, channels, weight=None):
     return _UpsampleSoftNLL.apply(P, relaxed, int(size[0]), int(size[1]), int(channels), weight)
 
 
+# ---- online hard example mining for the cross entropy (csrc/ohem.hip; include/mrfp_hip.h and DESIGN.md section 8 hold the
+# definition): the kept set is chosen on the device -- probability plane, exact radix select, masked target -- with no host wait,
+# and the loss and its gradient are the cross-entropy operators above on the masked target ----
+OHEM_SENTINEL = 2.0                       # the probability plane's value at an invalid pixel
+OHEM_KEEP_ALL, OHEM_THRESH, OHEM_KTH = 0, 1, 2          # the state's mode word
+
+
+def _ohem_ws(B, HW, device):
+    n = int(_lib.lib().mrfp_ohem_ws_bytes(B, HW))
+    if n < 0:
+        raise _lib.MrfpHipError("ohem: unsupported size (B=%d, H*W=%d): 1 <= B <= 65535, H*W < 2^30, B*H*W < 2^31" % (B, HW))
+    return torch.empty(n // 4, dtype=torch.int32, device=device)
+
+
+def select_kth(x_f32, k):
+    """The k-th smallest (from 1) element of a float32 tensor, exactly, as a 0-d float32 tensor on the device (mrfp_select_kth: a
+    three-level radix select on the bit patterns, no sort and no host wait).  x holds non-negative values; NaN sorts last, as in
+    torch.sort; elements equal to OHEM_SENTINEL are skipped and k counts the others."""
+    if not isinstance(x_f32, torch.Tensor) or not x_f32.is_cuda or x_f32.dtype != torch.float32:
+        raise _lib.MrfpHipError("select_kth: x must be a float32 GPU tensor: the HIP path has no CPU fallback")
+    x = x_f32.detach().contiguous()
+    n, k = x.numel(), int(k)
+    if n < 1 or not 1 <= k <= n:
+        raise _lib.MrfpHipError("select_kth: 1 <= k <= numel (k=%d, numel=%d)" % (k, n))
+    ws = _ohem_ws(1, 1, x.device)
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    call("mrfp_select_kth", ptr(x), n, k, ptr(ws), ptr(out), stream())
+    return out
+
+
+def _ohem_args(who, thresh, min_kept):
+    thresh, min_kept = float(thresh), int(min_kept)
+    if not 0.0 <= thresh <= 1.0:              # also false for a NaN
+        raise _lib.MrfpHipError("%s: thresh must be in [0, 1] (got %r)" % (who, thresh))
+    if min_kept < 0:
+        raise _lib.MrfpHipError("%s: min_kept must not be negative (got %d)" % (who, min_kept))
+    return thresh, min_kept
+
+
+def ohem_target(logits, target, ignore_index=255, thresh=0.7, min_kept=100000, *, size=None, channels=None, want_prob=False,
+                want_state=False):
+    """The masked int64 target [B,H,W] of the OHEM rule (include/mrfp_hip.h): `target` where the pixel is kept, ignore_index
+    elsewhere.  logits: [B,C,H,W]; with `size` the channel-padded low-resolution class scores [B,ld,Hi,Wi] and `channels` classes,
+    as for upsample_cross_entropy.  want_prob: also the float32 plane [B,H,W] of p = softmax(z)[t] (OHEM_SENTINEL where the pixel is
+    invalid); want_state: also int32 [4] on the device, (valid pixels, kept pixels, bits of theta, mode).  No autograd through it:
+    the selection is a constant."""
+    who = "ohem_target"
+    thresh, min_kept = _ohem_args(who, thresh, min_kept)
+    x = _chk(logits.detach(), "logits")
+    B = x.shape[0]
+    if size is None:
+        C, H, W = x.shape[1:]
+    else:
+        ld, Hi, Wi = x.shape[1:]
+        H, W, C = int(size[0]), int(size[1]), int(channels)
+    target = _ce_target(who, target, B, H, W)
+    ws = _ohem_ws(B, H * W, x.device)
+    prob = torch.empty(B, H, W, dtype=torch.float32, device=x.device)
+    masked = torch.empty(B, H, W, dtype=torch.int64, device=x.device)
+    if size is None:
+        call("mrfp_ohem_target", ptr(x), ptr(target), dt(x), B, H * W, C, int(ignore_index), thresh, min_kept, ptr(prob), ptr(masked),
+             ptr(ws), stream())
+    else:
+        call("mrfp_upsample_ohem_target", ptr(x), ld, ptr(target), dt(x), B, Hi, Wi, H, W, C, int(ignore_index), thresh, min_kept,
+             ptr(prob), ptr(masked), ptr(ws), stream())
+    if not (want_prob or want_state):
+        return masked
+    return (masked,) + ((prob,) if want_prob else ()) + ((ws[:4],) if want_state else ())
+
+
+def ohem_cross_entropy(logits, target, ignore_index=255, *, thresh=0.7, min_kept=100000, weight=None):
+    """nn.CrossEntropyLoss(weight, ignore_index) of the pixels the OHEM rule keeps: cross_entropy on ohem_target's masked target."""
+    masked = ohem_target(logits, target, ignore_index, thresh, min_kept)
+    return cross_entropy(logits, masked, ignore_index, weight=weight)
+
+
+def upsample_ohem_cross_entropy(P, target, size, channels, ignore_index=255, *, thresh=0.7, min_kept=100000, weight=None):
+    """ohem_cross_entropy of Upsample(P[:, :channels], size) without materialising the full-resolution logits: upsample_cross_entropy
+    on the masked target ohem_target computes from the same low-resolution scores."""
+    masked = ohem_target(P, target, ignore_index, thresh, min_kept, size=size, channels=channels)
+    return upsample_cross_entropy(P, masked, size, channels, ignore_index, weight=weight)
+
+
 # ------------------------------------------------------------------------------------------
 # eval: arg-max + confusion histogram on the device
 # ------------------------------------------------------------------------------------------
