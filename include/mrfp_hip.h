@@ -511,6 +511,21 @@ int mrfp_sgd_step(float* p, const float* g, float* m, int64_t n, float lr, float
                   float weight_decay, float gscale, int first, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gradient accumulation over micro-batches on the flat arenas:
+ *   first != 0: acc[i] = g[i] (a bit copy; acc is not read);  otherwise acc[i] = acc[i] + g[i], one fp32 addition per element,
+ *   in this operand order.  One streaming launch (16-byte loads and stores, the capped grid of mrfp_sgd_step), no atomics, no
+ *   workspace; touches nothing outside [0, n).  Called on the whole arena and on contiguous sub-ranges (a data-parallel bucket):
+ *   any n that is a positive multiple of 4, any 16-byte-aligned acc / g.
+ * Replaces autograd's AccumulateGrad over k backward passes -- `optimizer.zero_grad()` once per k iterations in a stock loop.
+ * The backward kernels here OVERWRITE their slot of the gradient arena, so the sum over a window is kept by this entry: the
+ * harness calls it with (acc, g) = (accumulator, gradient arena) after each of the first k-1 passes and with the arenas in the
+ * other roles after the last, which leaves the sum where mrfp_sgd_step / mrfp_grad_check / mrfp_sgd_step_checked read it.
+ * The reference's loop (main.py:860-864) does not accumulate: build-defined.
+ * Refused before any launch: null pointers, n <= 0, n % 4 != 0, a misaligned acc or g.
+ * ------------------------------------------------------------------------------------------- */
+int mrfp_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Checked step: dynamic loss scale, skip on a non-finite gradient and gradient-norm clipping decided ON THE DEVICE -- the
  * semantics of torch.amp.GradScaler (unscale_ / step / update, i.e. torch._amp_update_scale_) and
  * torch.nn.utils.clip_grad_norm_ around the update rule of mrfp_sgd_step, without the host read of the overflow flag.

@@ -25,6 +25,8 @@ struct StepState {            // the device step state of include/mrfp_hip.h, wo
 };
 static_assert(sizeof(StepState) == 32, "step state: eight 32-bit words");
 
+constexpr int kArenaCap = 4096;            // workgroups of the streaming arena kernels (step, checked step, accumulate): 16 per CU
+
 __global__ __launch_bounds__(256) void sgd_kernel(float4* __restrict__ p, const float4* __restrict__ g,
                                                   float4* __restrict__ m, int64_t n4, float lr, float mu, float wd,
                                                   float gscale, int first) {
@@ -44,6 +46,19 @@ __global__ __launch_bounds__(256) void sgd_kernel(float4* __restrict__ p, const 
     }
 }
 
+// Gradient accumulation over micro-batches: acc = g (first: a bit copy, acc is not read) | acc = acc + g, one fp32 addition per
+// element in this operand order, nothing to contract with.  Streams 12 bytes per element (8 when first) against sgd_kernel's 20.
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float4* __restrict__ acc, const float4* __restrict__ g, int64_t n4,
+                                                              int first) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        float4 gv = g[i];
+        if (!first) {
+            const float4 av = acc[i];
+            gv.x = av.x + gv.x; gv.y = av.y + gv.y; gv.z = av.z + gv.z; gv.w = av.w + gv.w;
+        }
+        acc[i] = gv;
+    }
+}
 
 // ---- checked step: non-finite check + gradient norm + dynamic loss scale, all on the device ------------------------------------
 // Semantics of torch.amp.GradScaler (unscale_ -> step -> update) + torch.nn.utils.clip_grad_norm_ without the host read of the
@@ -160,9 +175,20 @@ extern "C" int mrfp_sgd_step(float* p, const float* g, float* m, int64_t n, floa
     MRFP_CHECK(p && g && m && n > 0 && n % 4 == 0, "sgd_step: bad arguments (n must be a multiple of 4)");
     MRFP_CHECK(mrfp::aligned16(p) && mrfp::aligned16(g) && mrfp::aligned16(m), "sgd_step: arenas must be 16-byte aligned");
     int64_t blocks = (n / 4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
+    if (blocks > mrfp::kArenaCap) blocks = mrfp::kArenaCap;
     hipLaunchKernelGGL(mrfp::sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (float4*)p,
                        (const float4*)g, (float4*)m, n / 4, lr, momentum, weight_decay, gscale, first);
+    MRFP_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mrfp_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream) {
+    MRFP_CHECK(acc && g && n > 0 && n % 4 == 0, "grad_accumulate: bad arguments (n must be a positive multiple of 4)");
+    MRFP_CHECK(mrfp::aligned16(acc) && mrfp::aligned16(g), "grad_accumulate: acc and g must be 16-byte aligned");
+    int64_t blocks = (n / 4 + 255) / 256;
+    if (blocks > mrfp::kArenaCap) blocks = mrfp::kArenaCap;
+    hipLaunchKernelGGL(mrfp::grad_accumulate_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (float4*)acc,
+                       (const float4*)g, n / 4, first);
     MRFP_LAUNCH_CHECK();
     return 0;
 }
@@ -194,7 +220,7 @@ extern "C" int mrfp_sgd_step_checked(float* p, const float* g, float* m, int64_t
     MRFP_CHECK(mrfp::aligned16(p) && mrfp::aligned16(g) && mrfp::aligned16(m) && mrfp::aligned16(state),
                "sgd_step_checked: arenas and state must be 16-byte aligned");
     int64_t blocks = (n / 4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
+    if (blocks > mrfp::kArenaCap) blocks = mrfp::kArenaCap;
     hipLaunchKernelGGL(mrfp::sgd_checked_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (float4*)p,
                        (const float4*)g, (float4*)m, n / 4, lr, momentum, weight_decay, (const mrfp::StepState*)state);
     MRFP_LAUNCH_CHECK();

@@ -105,9 +105,27 @@ def _check_max_grad_norm(max_grad_norm):
     return max_grad_norm
 
 
+def _check_accum_steps(accum_steps):
+    if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
+        raise ValueError("accum_steps must be an int >= 1, got %r" % (accum_steps,))
+    return accum_steps
+
+
+def _check_loss_weights(loss_weights):
+    if loss_weights is None:
+        return None
+    if not isinstance(loss_weights, (list, tuple)) or len(loss_weights) == 0:
+        raise ValueError("loss_weights must be None or a non-empty sequence of finite numbers, got %r" % (loss_weights,))
+    for w in loss_weights:
+        if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w):
+            raise ValueError("loss_weights must be None or a non-empty sequence of finite numbers, got %r" % (loss_weights,))
+    return tuple(float(w) for w in loss_weights)
+
+
 class FlatArena:
     """Trainable parameters and their gradients as views into two flat fp32 buffers (every tensor starts
-    16-byte aligned).  Device-agnostic host logic: the data-parallel buckets are ranges of `flat_g`."""
+    16-byte aligned).  Device-agnostic host logic: the data-parallel buckets are ranges of `flat_g`.
+    `flat_a`, the sum of a gradient-accumulation window, exists from the first accumulate() on (None until then)."""
 
     def __init__(self, model: torch.nn.Module):
         every = list(model.parameters())
@@ -126,6 +144,7 @@ class FlatArena:
         self.n = n
         self.flat_p = torch.zeros(n, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.flat_a = None
         for p, o in zip(self.params, self.offsets):
             self.flat_p[o:o + p.numel()].copy_(p.data.reshape(-1))
             p.data = self.flat_p[o:o + p.numel()].view(p.shape)
@@ -137,6 +156,23 @@ class FlatArena:
         for p, o in zip(self.params, self.offsets):   # keep .grad pointing into the arena
             if p.grad is None or p.grad.data_ptr() != self.flat_g.data_ptr() + 4 * o:
                 p.grad = self.flat_g[o:o + p.numel()].view(p.shape)
+
+    def accumulate(self, lo=0, hi=None, first=False, into_grad=False):
+        """mrfp_grad_accumulate over the arena range [lo, hi) on the current stream: flat_a = flat_g (first) | flat_a += flat_g, or,
+        with into_grad, flat_g += flat_a -- the same entry point with the arenas in the other roles (a + b is commutative bit for
+        bit), which closes a window with the sum where the optimiser and the all-reduce read it.  lo and hi are arena offsets of
+        tensors (multiples of 4: 16-byte aligned).  CPU arenas (the gloo tests of the bucket logic) take the plain torch add."""
+        hi = self.n if hi is None else hi
+        if self.flat_a is None:
+            self.flat_a = torch.empty_like(self.flat_g)
+        acc, g = (self.flat_g, self.flat_a) if into_grad else (self.flat_a, self.flat_g)
+        if not acc.is_cuda:
+            if first:
+                acc[lo:hi].copy_(g[lo:hi])
+            else:
+                acc[lo:hi].add_(g[lo:hi])
+            return
+        call("mrfp_grad_accumulate", ptr(acc) + 4 * lo, ptr(g) + 4 * lo, hi - lo, int(first), stream())
 
 
 class FlatSGD(FlatArena):
@@ -273,6 +309,7 @@ class GradSync:
         self.seen = [False] * len(opt.params)
         self.next = 0                    # buckets are launched strictly in index order on every rank
         self.works = []
+        self.reduce, self.accum = True, False        # this pass: exchange the buckets? add the window's flat_a to each one first?
         self.on_gpu = opt.flat_g.is_cuda
         self.side = torch.cuda.Stream() if self.on_gpu else None
         self._index = {id(p): i for i, p in enumerate(opt.params)}
@@ -304,7 +341,7 @@ class GradSync:
             # A parameter can be reported twice in one step: by the HIP backward kernel that wrote its gradient
             # straight into the arena (ops.notify_grad) and by autograd's post-accumulate hook (this PyTorch fires
             # it even when the backward returned None for the parameter).  Count each parameter once.
-            if self.seen[i]:
+            if not self.reduce or self.seen[i]:     # (an inner micro-batch of an accumulation window launches nothing)
                 return
             self.seen[i] = True
             self.pending[self.bucket_of[i]] -= 1
@@ -323,6 +360,8 @@ class GradSync:
     def _launch(self, b):
         lo, hi, _ = self.buckets[b]
         if not self.on_gpu:                      # gloo / CPU arenas (tests): no streams involved
+            if self.accum:
+                self.opt.accumulate(lo, hi, into_grad=True)
             self.works.append(dist.all_reduce(self.opt.flat_g[lo:hi], group=self.group, async_op=True))
             return
         ev = torch.cuda.Event()
@@ -331,10 +370,16 @@ class GradSync:
         with torch.cuda.stream(self.side):
             self.side.wait_event(ev)
             conv.join_wgrad_stream(self.side)        # the bucket's weight gradients are written on the wgrad stream
+            if self.accum:                           # last micro-batch of a window: the range's sum over the earlier ones, behind
+                self.opt.accumulate(lo, hi, into_grad=True)      # both waits and in front of the collective, on the side stream
             self.works.append(dist.all_reduce(self.opt.flat_g[lo:hi], group=self.group, async_op=True))
 
-    def begin(self):
+    def begin(self, reduce=True, accum=False):
+        """reduce=False: a pass whose gradient only joins an accumulation window -- the hooks launch nothing and finish() only joins
+        the weight-gradient stream.  accum=True (the window's last pass): each bucket's range of flat_g gets += flat_a before its
+        all-reduce, so one collective per bucket carries the whole window."""
         if self.enabled:
+            self.reduce, self.accum = bool(reduce), bool(accum)
             self.pending = [len(m) for _, _, m in self.buckets]
             self.seen = [False] * len(self.opt.params)
             self.next = 0
@@ -347,6 +392,8 @@ class GradSync:
         conv.join_wgrad_stream()                     # weight gradients are computed on a second stream (mrfp_amd/conv.py)
         if not self.enabled:
             return 1.0
+        if not self.reduce:
+            return 1.0 / self.world
         for b in range(self.next, len(self.buckets)):   # buckets with tensors that got no gradient this step: same order
             self.pending[b] = 0
         self._launch_ready()
@@ -397,10 +444,11 @@ def random_base_seed() -> int:
 
 
 class Trainer:
-    """zero_grad -> forward -> backward (+ overlapped all-reduce) -> fused SGD step -> LR step."""
+    """zero_grad -> forward -> backward (+ overlapped all-reduce) -> fused SGD step -> LR step; with accum_steps = k the
+    optimiser step, the all-reduce and the LR step happen once per window of k calls, on the sum of the k gradients."""
 
     def __init__(self, model, lr=1e-2, momentum=0.9, weight_decay=5e-4, max_iter=40000, bucket_mb=32.0,
-                 loss_scale=None, max_grad_norm=None):
+                 loss_scale=None, max_grad_norm=None, accum_steps=1, loss_weights=None):
         """loss_scale: scale of the backward pass for float16 activations (the per-pixel CE gradient is 1/#pixels ~ 1e-7, below
         float16's normal range).
           None / a float, no max_grad_norm: a STATIC host-side scale, default 65536 when cfg.MODEL.ACT_DTYPE is float16, else 1.
@@ -414,9 +462,23 @@ class Trainer:
         max_grad_norm: clip_grad_norm_(parameters, max_grad_norm) of the unscaled, averaged gradient, folded into the step.
         With a scaler no host value enters backward (it is seeded with scaler.scale_tensor) and no step waits for the host;
         step_info() reads the device state back on request.  The poly schedule advances on skipped steps too, and the BatchNorm
-        running statistics of a skipped step are kept, as with stock AMP."""
+        running statistics of a skipped step are kept, as with stock AMP.
+        accum_steps = k: gradient accumulation over k micro-batches.  Every step() call runs one forward and
+        backward pass and returns that micro-batch's loss; calls 1 .. k-1 of a window add their gradient arena to `flat_a`
+        (mrfp_grad_accumulate) and do nothing else -- no optimiser step, no repack, no schedule advance, no collective; call k adds
+        the partial sum back, ((g1 + g2) + ...) + gk in this fixed order, all-reduces once per bucket and makes ONE optimiser step
+        with the mean over the window (1 / (world * k) folded into the kernel's gradient factor).  The loss scale is constant
+        inside a window and the check looks at the summed arena, so a window is applied or skipped as a whole; taken / skipped
+        and the schedule count windows, max_grad_norm clips the averaged gradient, BatchNorm running statistics advance per
+        micro-batch.  `micro` is the position inside the window (0 .. k-1); save checkpoints at micro == 0, the partial sum is
+        not part of one.
+        loss_weights: for a model that returns a list / tuple of losses (the network/deepv3.py factories: [main, aux(, wt)]) the
+        pass backpropagates sum_i w_i * loss_i, formed on the device, and step() returns that scalar; None: all ones.  A length
+        that differs from the returned list, or weights for a model that returns one loss, is a ValueError."""
         from .config import cfg
         max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        self.accum_steps, self.micro = _check_accum_steps(accum_steps), 0
+        self.loss_weights = _check_loss_weights(loss_weights)
         if isinstance(loss_scale, str):
             if loss_scale != "dynamic":
                 raise ValueError("loss_scale must be None, a number, 'dynamic' or a LossScaler, got %r" % (loss_scale,))
@@ -450,10 +512,11 @@ class Trainer:
     def _fwd_bwd(self, img, label):
         from . import conv
         self.opt.zero_grad()
-        self.sync.begin()
+        last = self.micro == self.accum_steps - 1          # only the window's last pass exchanges gradients
+        self.sync.begin(reduce=last, accum=last and self.accum_steps > 1)
         ok = False
         try:
-            loss = self.model(img, label, training=True)
+            loss = self._total_loss(self.model(img, label, training=True))
             if self.scaler is not None:
                 loss.backward(self.scaler.scale_tensor)      # a device address: a replayed graph reads the scale of its own step
             elif self.loss_scale != 1.0:
@@ -465,6 +528,36 @@ class Trainer:
             if not ok:          # a pass that raised leaves queued weight gradients and a pending end-of-backward callback behind
                 conv.backward_failed()
         return loss
+
+    def _total_loss(self, loss):
+        """A list / tuple of losses -> sum_i w_i * loss_i on the device (a unit weight multiplies nothing: with all ones this is the
+        plain sum a hand-written loop forms)."""
+        if not isinstance(loss, (list, tuple)):
+            if self.loss_weights is not None:
+                raise ValueError("loss_weights given, but the model returned one loss")
+            return loss
+        weights = self.loss_weights if self.loss_weights is not None else (1.0,) * len(loss)
+        if len(weights) != len(loss):
+            raise ValueError("%d loss_weights for the %d losses the model returned" % (len(weights), len(loss)))
+        total = None
+        for w, term in zip(weights, loss):
+            term = term if w == 1.0 else w * term
+            total = term if total is None else total + term
+        return total
+
+    def _end_pass(self, gscale):
+        """After a pass whose gradients are complete on the current stream (GradSync.finish(), weight-gradient stream joined): an
+        inner micro-batch of a window joins the partial sum; the last one (every pass with accum_steps = 1) takes the partial sum
+        back -- the bucket path has done that range by range before its collectives -- and makes the optimiser step."""
+        k = self.accum_steps
+        if self.micro < k - 1:
+            self.opt.accumulate(first=self.micro == 0)
+            self.micro += 1
+            return
+        if k > 1 and not self.sync.enabled:
+            self.opt.accumulate(into_grad=True)
+        self.micro = 0
+        self._opt_step(gscale / k)
 
     def _opt_step(self, gscale):
         """After GradSync.finish(): every rank holds the same all-reduced arena, so with a scaler every rank's check decides from
@@ -488,7 +581,7 @@ class Trainer:
         gscale = self.sync.finish()
         from . import conv, ops
         conv.join_wgrad_stream()                       # weight gradients are computed on a second stream
-        self._opt_step(gscale)
+        self._end_pass(gscale)
         if ops._SYNC_BN_FLAG:                          # cfg.MODEL.SYNC_BN over several ranks: the device-side count check (no host wait)
             ops.sync_bn_poll()
         return loss
@@ -496,7 +589,8 @@ class Trainer:
     # ---- hipGraph mode --------------------------------------------------------------------------------------------
     # zero_grad + forward + backward (~2900 kernel launches, ~28 ms of Python + ctypes per ResNet-101 step) are captured
     # once per (perturbation toggle combination, input shape) and replayed with one hipGraphLaunch; the optimizer step
-    # (learning rate and first-step flag are by-value kernel arguments) and the batched weight repack stay eager.
+    # (learning rate and first-step flag are by-value kernel arguments), the batched weight repack and, with accum_steps > 1, the
+    # accumulate launch and the decision whether to step stay eager.
     # Single-process only: the overlapped all-reduce of GradSync is driven by Python hooks.
     def enable_graph(self):
         if self.sync.enabled:
@@ -537,7 +631,13 @@ class Trainer:
                 torch.cuda.current_stream().wait_stream(side)
                 from . import conv
                 conv.join_wgrad_stream()
-                self._opt_step(1.0)
+                self._end_pass(1.0)                      # (the window logic of an eager step: the warm-up call is one)
+                if self.micro != 0:
+                    # an inner micro-batch made no optimiser step: leave the weight packs as a step leaves them, so that the
+                    # capture records the lazy re-pack of the packs repack_all() does not cover (a pack with a bias: final2) --
+                    # every replay has to rebuild them from the parameters of ITS step
+                    conv.invalidate_packs()
+                    conv.repack_all()
                 conv.prebuild_repack_tables()            # (job tables of the batched re-packs: no host -> device copy inside the capture)
                 # capture on the warm-up's stream, with the warm-up's autograd graph gone (.detach() above): a gradient
                 # accumulator that remembers another stream makes autograd fork / join the capture once per parameter, and
@@ -564,7 +664,7 @@ class Trainer:
         for m in self._bns:
             if m.training and m.num_batches_tracked is not None:
                 m._nbt_pending += 1
-        self._opt_step(1.0)
+        self._end_pass(1.0)                               # eager, after the replay: accumulate, or close the window and step
         return static_loss
 
 
