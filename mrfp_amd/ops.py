@@ -949,64 +949,93 @@ def add(a, b):
 # ------------------------------------------------------------------------------------------
 # cross entropy (ignore_index) -- scalar fp32 loss
 # ------------------------------------------------------------------------------------------
-def _ce_target(who, target, B, H, W):
-    target = target.contiguous()
-    if target.dtype != torch.int64 or tuple(target.shape) != (B, H, W):
-        raise _lib.MrfpHipError("%s: target must be int64 [B,H,W]" % who)
-    return target
+# The loss operators have the two axes of the kernels under them (csrc/loss_common.hpp): where a pixel's class vector comes from
+# (_Scores: dense logits, or low-resolution scores the kernel upsamples) and which criterion reads it (_PlainCe, _WeightedCe,
+# _SoftNll).  One autograd function, _PixelLoss, serves every pair; the entry is mrfp_[upsample_]<stem>_{fwd,bwd}, and its arguments
+# are looked up by the names include/mrfp_hip.h gives them, never placed by position.
+def _call_named(entry, env):
+    """Calls `entry` with its positional arguments taken from env, a dictionary of named values to which the stream is added here; a
+    name the header asks for and env lacks is a KeyError, before anything is launched."""
+    env["stream"] = stream()
+    call(entry, *[env[n] for n in _lib.ARG_NAMES[entry]])
 
 
-def _fused_loss_bwd(entry, P, target, loss, g, H, W, C, *extra):
-    """The backward tail of every fused loss: `entry` writes d(loss)/d(logits) at full resolution once, channel-padded to Cd, and the
-    gather-form bilinear backward takes it to dP.  extra: what the entry takes between C and the stream."""
-    B, ld, Hi, Wi = P.shape
-    epc = 16 // P.element_size()
-    Cd = (C + epc - 1) // epc * epc
-    gs = g.detach().float().reshape(1).contiguous()
-    dP = empty_cl(B, ld, Hi, Wi, P.dtype, P.device)
-    dlog = empty_cl(B, Cd, H, W, P.dtype, P.device)
-    call(entry, ptr(P), ld, ptr(target), ptr(loss), ptr(gs), ptr(dlog), Cd, dt(P), B, Hi, Wi, H, W, C, *extra, stream())
-    if ld != Cd:
-        dP.zero_()
-    call("mrfp_bilinear_bwd", ptr(dlog), ptr(dP), dt(P), B, Hi, Wi, H, W, Cd, ld, stream())
-    return dP
+def _chk_target(who, t, dtype, dims, shape=None):
+    """A label-like operand, contiguous: a GPU tensor of `dims` dimensions, or with `shape` a loss's target of exactly that shape."""
+    if shape is not None:
+        t = t.contiguous()
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise _lib.MrfpHipError("%s: target must be int64 [B,H,W]" % who)
+        return t
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.MrfpHipError("%s: the target must be a GPU tensor: the HIP path has no CPU fallback" % who)
+    if t.dtype != dtype or t.dim() != dims:
+        raise _lib.MrfpHipError("%s: expected a %d-dimensional %s tensor (got %s %s)" % (who, dims, dtype, t.dtype, tuple(t.shape)))
+    return t.contiguous()
 
 
-class _CrossEntropy(torch.autograd.Function):
-    """nn.CrossEntropyLoss(ignore_index=255): reference main.py:822, deepv3.py:363."""
+class _Scores:
+    """Where the class vector of a pixel comes from: dense logits [B,C,H,W] (size None), or channel-padded low-resolution scores
+    P [B,ld,Hi,Wi] (ld a multiple of the 16-byte chunk) that the kernel upsamples to `size`, the first `channels` of them classes.
+    x: the tensor as _chk returned it."""
 
-    @staticmethod
-    def forward(ctx, logits, target, ignore_index):
-        logits = _chk(logits, "logits")
-        B, C, H, W = logits.shape
-        target = _ce_target("cross_entropy", target, B, H, W)
-        npix = B * H * W
-        nblk = int(_lib.lib().mrfp_ce_nblocks(npix))
-        ws = torch.empty(2 * nblk, dtype=torch.float32, device=logits.device)
-        loss = torch.empty(2, dtype=torch.float32, device=logits.device)
-        call("mrfp_ce_fwd", ptr(logits), ptr(target), dt(logits), npix, C, int(ignore_index), ptr(ws), ptr(loss), stream())
-        ctx.save_for_backward(logits, target, loss)
-        ctx.ignore = int(ignore_index)
-        return loss[0].clone()
+    def __init__(self, x, size=None, channels=None):
+        self.x, self.fused, self.B = x, size is not None, x.shape[0]
+        if self.fused:
+            self.ld, self.Hi, self.Wi = x.shape[1:]
+            self.H, self.W, self.C = int(size[0]), int(size[1]), int(channels)
+        else:
+            self.C, self.H, self.W = x.shape[1:]
+        self.prefix = "mrfp_upsample_" if self.fused else "mrfp_"
 
-    @staticmethod
-    def backward(ctx, g):
-        logits, target, loss = ctx.saved_tensors
-        B, C, H, W = logits.shape
-        gs = g.detach().float().reshape(1).contiguous()
-        d = torch.empty_like(logits, memory_format=CL)
-        call("mrfp_ce_bwd", ptr(logits), ptr(target), ptr(loss), ptr(gs), ptr(d), dt(logits), B * H * W, C, ctx.ignore, stream())
-        return d, None, None
+    def env(self):
+        """Head and geometry arguments under the header's names: logits and P are the one pointer; an entry takes the geometry it
+        names (npix, or B and HW, or B, Hi, Wi, H, W)."""
+        x = self.x
+        env = dict(logits=ptr(x), P=ptr(x), dtype=dt(x), B=self.B, H=self.H, W=self.W, HW=self.H * self.W, C=self.C,
+                   npix=self.B * self.H * self.W)
+        if self.fused:
+            env.update(ld=self.ld, Hi=self.Hi, Wi=self.Wi)
+        return env
+
+    def grad(self, entry, env):
+        """d(loss)/d(scores) by the backward `entry`.  Dense: the entry writes it.  Fused: the entry writes d(loss)/d(logits) at full
+        resolution once, channel-padded to Cd, and the gather-form bilinear backward takes it to dP."""
+        x = self.x
+        if not self.fused:
+            d = torch.empty_like(x, memory_format=CL)
+            env["dlogits"] = ptr(d)
+            _call_named(entry, env)
+            return d
+        B, ld, Hi, Wi, H, W = self.B, self.ld, self.Hi, self.Wi, self.H, self.W
+        epc = 16 // x.element_size()
+        Cd = (self.C + epc - 1) // epc * epc
+        dP = empty_cl(B, ld, Hi, Wi, x.dtype, x.device)
+        dlog = empty_cl(B, Cd, H, W, x.dtype, x.device)
+        env.update(dlogits=ptr(dlog), Cd=Cd)
+        _call_named(entry, env)
+        if ld != Cd:
+            dP.zero_()
+        call("mrfp_bilinear_bwd", ptr(dlog), ptr(dP), dt(x), B, Hi, Wi, H, W, Cd, ld, stream())
+        return dP
 
 
-# ---- class weights / label smoothing / sum / per-image mean: the criteria a caller hands to the reference's DeepV3Plus
-# (network/deepv3.py:111 `criterion`, `criterion_aux`) instead of the plain one of main.py:822 -- csrc/loss.hip, mrfp_ce_w_* ----
-CE_MEAN, CE_SUM, CE_IMAGE_MEAN = 0, 1, 2
+class _PlainCe:
+    """nn.CrossEntropyLoss(ignore_index=255): reference main.py:822, deepv3.py:363 (mrfp_[upsample_]ce_*).  A criterion record: its
+    entry stem, check() -> the validated (target, weight), extra() -> its own C arguments, sizes() -> (workgroups, loss floats)."""
+    stem = "ce"
 
+    def __init__(self, who, ignore_index):
+        self.who, self.ignore_index = who, ignore_index
 
-def _ce_general(weight, label_smoothing, reduction, per_image, _general):
-    """True when the call needs the weighted entries; with the four keywords at their defaults the plain kernels run untouched."""
-    return _general or weight is not None or float(label_smoothing) != 0.0 or reduction != "mean" or bool(per_image)
+    def check(self, src, target, weight):
+        return _chk_target(self.who, target, torch.int64, 3, (src.B, src.H, src.W)), None
+
+    def extra(self, weight):
+        return dict(ignore_index=int(self.ignore_index))
+
+    def sizes(self, L, src):
+        return L.mrfp_ce_nblocks(src.B * src.H * src.W), 2
 
 
 def _ce_options(who, weight, label_smoothing, reduction, per_image, B, C, device):
@@ -1026,111 +1055,91 @@ def _ce_options(who, weight, label_smoothing, reduction, per_image, B, C, device
                 who, device, C, B, (weight.dtype, tuple(weight.shape), weight.device) if isinstance(weight, torch.Tensor) else type(weight)))
         weight = weight.detach().contiguous()
         wstride = C if weight.dim() == 2 else 0
-    mode = CE_IMAGE_MEAN if per_image else (CE_MEAN if reduction == "mean" else CE_SUM)
+    mode = 2 if per_image else (0 if reduction == "mean" else 1)      # mrfp_ce_mode: MRFP_CE_IMAGE_MEAN, MRFP_CE_MEAN, MRFP_CE_SUM
     return weight, wstride, eps, mode
 
 
-def _ce_buffers(B, HW, mode, device):
-    L = _lib.lib()
-    ws = torch.empty(2 * int(L.mrfp_ce_w_nblocks(B, HW)), dtype=torch.float32, device=device)
-    loss = torch.empty(int(L.mrfp_ce_w_loss_floats(B, mode)), dtype=torch.float32, device=device)
-    return ws, loss
+class _WeightedCe(_PlainCe):
+    """nn.CrossEntropyLoss(weight, ignore_index, label_smoothing, reduction 'mean' / 'sum') and the per-image weighted mean: the
+    criteria a caller hands to the reference's DeepV3Plus (network/deepv3.py:111 `criterion`, `criterion_aux`) instead of the plain
+    one of main.py:822 -- csrc/loss.hip, mrfp_[upsample_]ce_w_*."""
+    stem = "ce_w"
+
+    def __init__(self, who, ignore_index, *options):
+        self.who, self.ignore_index, self.options = who, ignore_index, options
+
+    def check(self, src, target, weight):
+        target, _ = _PlainCe.check(self, src, target, weight)
+        weight, self.wstride, self.eps, self.mode = _ce_options(self.who, weight, *self.options, src.B, src.C, src.x.device)
+        return target, weight
+
+    def extra(self, weight):
+        return dict(ignore_index=int(self.ignore_index), weight=ptr(weight), wstride=self.wstride, smoothing=self.eps, mode=self.mode)
+
+    def sizes(self, L, src):
+        return L.mrfp_ce_w_nblocks(src.B, src.H * src.W), L.mrfp_ce_w_loss_floats(src.B, self.mode)
 
 
-class _CrossEntropyW(torch.autograd.Function):
-    """nn.CrossEntropyLoss(weight, ignore_index, label_smoothing, reduction 'mean' / 'sum') and the per-image weighted mean."""
+def _loss_env(src, crit, target, weight, loss):
+    """The named values a loss entry of (src, crit) can ask for, its own buffers and the stream apart: target and words are the one
+    pointer."""
+    env = src.env()
+    env.update(crit.extra(weight))
+    env["target"] = env["words"] = ptr(target)
+    env["loss"] = ptr(loss)
+    return env
+
+
+class _PixelLoss(torch.autograd.Function):
+    """loss = crit(the class scores of (x, size, channels) at full resolution, target): every loss operator of this section.  The
+    fused source never materialises the full-resolution logits (reference deepv3.py:361-365 in training mode)."""
 
     @staticmethod
-    def forward(ctx, logits, target, ignore_index, weight, label_smoothing, reduction, per_image):
-        logits = _chk(logits, "logits")
-        B, C, H, W = logits.shape
-        target = _ce_target("cross_entropy", target, B, H, W)
-        weight, wstride, eps, mode = _ce_options("cross_entropy", weight, label_smoothing, reduction, per_image, B, C, logits.device)
-        ws, loss = _ce_buffers(B, H * W, mode, logits.device)
-        call("mrfp_ce_w_fwd", ptr(logits), ptr(target), dt(logits), B, H * W, C, int(ignore_index), ptr(weight), wstride, eps, mode,
-             ptr(ws), ptr(loss), stream())
-        ctx.save_for_backward(logits, target, loss, weight)
-        ctx.cfg = (int(ignore_index), wstride, eps, mode)
+    def forward(ctx, x, target, weight, size, channels, crit):
+        src = _Scores(_chk(x, "logits" if size is None else "P"), size, channels)
+        target, weight = crit.check(src, target, weight)
+        nblk, nloss = crit.sizes(_lib.lib(), src)
+        ws = torch.empty(2 * int(nblk), dtype=torch.float32, device=src.x.device)
+        loss = torch.empty(int(nloss), dtype=torch.float32, device=src.x.device)
+        env = _loss_env(src, crit, target, weight, loss)
+        env["ws"] = ptr(ws)
+        _call_named(src.prefix + crit.stem + "_fwd", env)
+        ctx.save_for_backward(src.x, target, loss, weight)
+        ctx.size, ctx.channels, ctx.crit = size, channels, crit
         return loss[0].clone()
 
     @staticmethod
     def backward(ctx, g):
-        logits, target, loss, weight = ctx.saved_tensors
-        ignore, wstride, eps, mode = ctx.cfg
-        B, C, H, W = logits.shape
+        x, target, loss, weight = ctx.saved_tensors
+        src, crit = _Scores(x, ctx.size, ctx.channels), ctx.crit
         gs = g.detach().float().reshape(1).contiguous()
-        d = torch.empty_like(logits, memory_format=CL)
-        call("mrfp_ce_w_bwd", ptr(logits), ptr(target), ptr(loss), ptr(gs), ptr(d), dt(logits), B, H * W, C, ignore, ptr(weight),
-             wstride, eps, mode, stream())
-        return d, None, None, None, None, None, None
+        env = _loss_env(src, crit, target, weight, loss)
+        env["gscale"] = ptr(gs)
+        return src.grad(src.prefix + crit.stem + "_bwd", env), None, None, None, None, None
+
+
+def _cross_entropy(who, x, target, size, channels, ignore_index, weight, label_smoothing, reduction, per_image, _general):
+    """With the four keywords at their defaults the plain kernels run untouched; `_general` forces the weighted entries."""
+    if _general or weight is not None or float(label_smoothing) != 0.0 or reduction != "mean" or bool(per_image):
+        crit = _WeightedCe(who, ignore_index, label_smoothing, reduction, per_image)
+    else:
+        crit = _PlainCe(who, ignore_index)
+    return _PixelLoss.apply(x, target, weight, size, channels, crit)
 
 
 def cross_entropy(logits, target, ignore_index=255, *, weight=None, label_smoothing=0.0, reduction="mean", per_image=False,
                   _general=False):
     """weight: float32 [C] (shared) or [B, C] (one row per image) on the device; reduction 'mean' (sum of weighted losses over the
     sum of the target weights, as torch) or 'sum'; per_image: the sum over images of each image's weighted mean."""
-    if not _ce_general(weight, label_smoothing, reduction, per_image, _general):
-        return _CrossEntropy.apply(logits, target, ignore_index)
-    return _CrossEntropyW.apply(logits, target, ignore_index, weight, label_smoothing, reduction, per_image)
-
-
-class _UpsampleCrossEntropy(torch.autograd.Function):
-    """loss = CE(Upsample(P[:, :C], size), target) without materialising the full-resolution logits
-    (reference deepv3.py:361-365 in training mode)."""
-
-    @staticmethod
-    def forward(ctx, P, target, H, W, C, ignore_index):
-        P = _chk(P, "P")
-        B, ld, Hi, Wi = P.shape
-        target = _ce_target("upsample_cross_entropy", target, B, H, W)
-        npix = B * H * W
-        nblk = int(_lib.lib().mrfp_ce_nblocks(npix))
-        ws = torch.empty(2 * nblk, dtype=torch.float32, device=P.device)
-        loss = torch.empty(2, dtype=torch.float32, device=P.device)
-        call("mrfp_upsample_ce_fwd", ptr(P), ld, ptr(target), dt(P), B, Hi, Wi, H, W, C, int(ignore_index), ptr(ws),
-             ptr(loss), stream())
-        ctx.save_for_backward(P, target, loss)
-        ctx.cfg = (H, W, C, int(ignore_index))
-        return loss[0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        P, target, loss = ctx.saved_tensors
-        H, W, C, ignore = ctx.cfg
-        return _fused_loss_bwd("mrfp_upsample_ce_bwd", P, target, loss, g, H, W, C, ignore), None, None, None, None, None
-
-
-class _UpsampleCrossEntropyW(torch.autograd.Function):
-    """_UpsampleCrossEntropy with class weights / label smoothing / sum / per-image mean (mrfp_upsample_ce_w_*)."""
-
-    @staticmethod
-    def forward(ctx, P, target, H, W, C, ignore_index, weight, label_smoothing, reduction, per_image):
-        P = _chk(P, "P")
-        B, ld, Hi, Wi = P.shape
-        target = _ce_target("upsample_cross_entropy", target, B, H, W)
-        weight, wstride, eps, mode = _ce_options("upsample_cross_entropy", weight, label_smoothing, reduction, per_image, B, C, P.device)
-        ws, loss = _ce_buffers(B, H * W, mode, P.device)
-        call("mrfp_upsample_ce_w_fwd", ptr(P), ld, ptr(target), dt(P), B, Hi, Wi, H, W, C, int(ignore_index), ptr(weight), wstride,
-             eps, mode, ptr(ws), ptr(loss), stream())
-        ctx.save_for_backward(P, target, loss, weight)
-        ctx.cfg = (H, W, C, int(ignore_index), wstride, eps, mode)
-        return loss[0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        P, target, loss, weight = ctx.saved_tensors
-        H, W, C, ignore, wstride, eps, mode = ctx.cfg
-        dP = _fused_loss_bwd("mrfp_upsample_ce_w_bwd", P, target, loss, g, H, W, C, ignore, ptr(weight), wstride, eps, mode)
-        return dP, None, None, None, None, None, None, None, None, None
+    return _cross_entropy("cross_entropy", logits, target, None, None, ignore_index, weight, label_smoothing, reduction, per_image,
+                          _general)
 
 
 def upsample_cross_entropy(P, target, size, channels, ignore_index=255, *, weight=None, label_smoothing=0.0, reduction="mean",
                            per_image=False, _general=False):
     """P: channel-padded low-resolution class scores [B,ld,Hi,Wi] (ld a multiple of the 16-byte chunk).  Keywords as cross_entropy."""
-    if not _ce_general(weight, label_smoothing, reduction, per_image, _general):
-        return _UpsampleCrossEntropy.apply(P, target, int(size[0]), int(size[1]), int(channels), ignore_index)
-    return _UpsampleCrossEntropyW.apply(P, target, int(size[0]), int(size[1]), int(channels), ignore_index, weight, label_smoothing,
-                                        reduction, per_image)
+    return _cross_entropy("upsample_cross_entropy", P, target, (int(size[0]), int(size[1])), int(channels), ignore_index, weight,
+                          label_smoothing, reduction, per_image, _general)
 
 
 def label_class_weights(target, num_classes, upper_bound=1.0, norm=False, batch=False):
@@ -1175,14 +1184,6 @@ def _relax_args(who, num_classes, border=0):
     if not 0 <= r <= RELAX_MAX_BORDER:
         raise _lib.MrfpHipError("%s: 0 <= border <= %d (got %d)" % (who, RELAX_MAX_BORDER, r))
     return C, r
-
-
-def _chk_target(who, t, dtype, dims):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.MrfpHipError("%s: the target must be a GPU tensor: the HIP path has no CPU fallback" % who)
-    if t.dtype != dtype or t.dim() != dims:
-        raise _lib.MrfpHipError("%s: expected a %d-dimensional %s tensor (got %s %s)" % (who, dims, dtype, t.dtype, tuple(t.shape)))
-    return t.contiguous()
 
 
 def relax_labels(target, num_classes, border=1, strict_classes=None, want_counts=False):
@@ -1237,69 +1238,38 @@ def _soft_nll_options(who, relaxed, weight, B, H, W, C, device):
             who, device))
     _relax_args(who, C)
     weight, wstride, _, _ = _ce_options(who, weight, 0.0, "mean", False, B, C, device)
-    L = _lib.lib()
-    ws = torch.empty(2 * int(L.mrfp_soft_nll_nblocks(B, H * W)), dtype=torch.float32, device=device)
-    loss = torch.empty(int(L.mrfp_soft_nll_loss_floats(B)), dtype=torch.float32, device=device)
-    return relaxed.contiguous(), weight, wstride, ws, loss
+    return relaxed.contiguous(), weight, wstride
 
 
-class _SoftNLL(torch.autograd.Function):
-    """The joint-weighted soft-NLL loss of relaxed targets on dense logits (mrfp_soft_nll_*)."""
+class _SoftNll:
+    """The joint-weighted soft-NLL loss of relaxed targets (mrfp_[upsample_]soft_nll_*): a criterion record, as _PlainCe."""
+    stem = "soft_nll"
 
-    @staticmethod
-    def forward(ctx, logits, relaxed, C, weight):
-        logits = _chk(logits, "logits")
-        B, Cl, H, W = logits.shape
-        if Cl != C:
-            raise _lib.MrfpHipError("soft_nll: logits have %d channels, num_classes is %d" % (Cl, C))
-        relaxed, weight, wstride, ws, loss = _soft_nll_options("soft_nll", relaxed, weight, B, H, W, C, logits.device)
-        call("mrfp_soft_nll_fwd", ptr(logits), ptr(relaxed), dt(logits), B, H * W, C, ptr(weight), wstride, ptr(ws), ptr(loss), stream())
-        ctx.save_for_backward(logits, relaxed, loss, weight)
-        ctx.wstride = wstride
-        return loss[0].clone()
+    def __init__(self, who, num_classes):
+        self.who, self.C = who, num_classes
 
-    @staticmethod
-    def backward(ctx, g):
-        logits, relaxed, loss, weight = ctx.saved_tensors
-        B, C, H, W = logits.shape
-        gs = g.detach().float().reshape(1).contiguous()
-        d = torch.empty_like(logits, memory_format=CL)
-        call("mrfp_soft_nll_bwd", ptr(logits), ptr(relaxed), ptr(loss), ptr(gs), ptr(d), dt(logits), B, H * W, C, ptr(weight),
-             ctx.wstride, stream())
-        return d, None, None, None
+    def check(self, src, relaxed, weight):
+        if src.C != self.C:
+            raise _lib.MrfpHipError("%s: logits have %d channels, num_classes is %d" % (self.who, src.C, self.C))
+        relaxed, weight, self.wstride = _soft_nll_options(self.who, relaxed, weight, src.B, src.H, src.W, src.C, src.x.device)
+        return relaxed, weight
+
+    def extra(self, weight):
+        return dict(weight=ptr(weight), wstride=self.wstride)
+
+    def sizes(self, L, src):
+        return L.mrfp_soft_nll_nblocks(src.B, src.H * src.W), L.mrfp_soft_nll_loss_floats(src.B)
 
 
 def soft_nll(logits, relaxed, num_classes, weight=None):
     """logits [B,C,H,W]; relaxed: int32 [B,H,W] words; weight: float32 [C] (shared) or [B, C] (one row per image) on the device, None =
     ones.  -> the sum over the images of sum_valid (W_i / k_i) (lse_all - lse_set) / (valid_b + 1), fp32 scalar."""
-    return _SoftNLL.apply(logits, relaxed, int(num_classes), weight)
-
-
-class _UpsampleSoftNLL(torch.autograd.Function):
-    """soft_nll(Upsample(P[:, :C], size), relaxed) without materialising the full-resolution logits (mrfp_upsample_soft_nll_*)."""
-
-    @staticmethod
-    def forward(ctx, P, relaxed, H, W, C, weight):
-        P = _chk(P, "P")
-        B, ld, Hi, Wi = P.shape
-        relaxed, weight, wstride, ws, loss = _soft_nll_options("upsample_soft_nll", relaxed, weight, B, H, W, C, P.device)
-        call("mrfp_upsample_soft_nll_fwd", ptr(P), ld, ptr(relaxed), dt(P), B, Hi, Wi, H, W, C, ptr(weight), wstride, ptr(ws), ptr(loss),
-             stream())
-        ctx.save_for_backward(P, relaxed, loss, weight)
-        ctx.cfg = (H, W, C, wstride)
-        return loss[0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        P, relaxed, loss, weight = ctx.saved_tensors
-        H, W, C, wstride = ctx.cfg
-        dP = _fused_loss_bwd("mrfp_upsample_soft_nll_bwd", P, relaxed, loss, g, H, W, C, ptr(weight), wstride)
-        return dP, None, None, None, None, None
+    return _PixelLoss.apply(logits, relaxed, weight, None, None, _SoftNll("soft_nll", int(num_classes)))
 
 
 def upsample_soft_nll(P, relaxed, size, channels, weight=None):
     """P: channel-padded low-resolution class scores [B,ld,Hi,Wi] (ld a multiple of the 16-byte chunk); the rest as soft_nll."""
-    return _UpsampleSoftNLL.apply(P, relaxed, int(size[0]), int(size[1]), int(channels), weight)
+    return _PixelLoss.apply(P, relaxed, weight, (int(size[0]), int(size[1])), int(channels), _SoftNll("upsample_soft_nll", int(channels)))
 
 
 # ---- online hard example mining for the cross entropy (csrc/ohem.hip; include/mrfp_hip.h and DESIGN.md section 8 hold the
@@ -1350,23 +1320,16 @@ def ohem_target(logits, target, ignore_index=255, thresh=0.7, min_kept=100000, *
     the selection is a constant."""
     who = "ohem_target"
     thresh, min_kept = _ohem_args(who, thresh, min_kept)
-    x = _chk(logits.detach(), "logits")
-    B = x.shape[0]
-    if size is None:
-        C, H, W = x.shape[1:]
-    else:
-        ld, Hi, Wi = x.shape[1:]
-        H, W, C = int(size[0]), int(size[1]), int(channels)
-    target = _ce_target(who, target, B, H, W)
-    ws = _ohem_ws(B, H * W, x.device)
-    prob = torch.empty(B, H, W, dtype=torch.float32, device=x.device)
-    masked = torch.empty(B, H, W, dtype=torch.int64, device=x.device)
-    if size is None:
-        call("mrfp_ohem_target", ptr(x), ptr(target), dt(x), B, H * W, C, int(ignore_index), thresh, min_kept, ptr(prob), ptr(masked),
-             ptr(ws), stream())
-    else:
-        call("mrfp_upsample_ohem_target", ptr(x), ld, ptr(target), dt(x), B, Hi, Wi, H, W, C, int(ignore_index), thresh, min_kept,
-             ptr(prob), ptr(masked), ptr(ws), stream())
+    src = _Scores(_chk(logits.detach(), "logits"), size, channels)
+    B, H, W, dev = src.B, src.H, src.W, src.x.device
+    target = _chk_target(who, target, torch.int64, 3, (B, H, W))
+    ws = _ohem_ws(B, H * W, dev)
+    prob = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    masked = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+    env = src.env()
+    env.update(target=ptr(target), ignore_index=int(ignore_index), thresh=thresh, min_kept=min_kept, prob=ptr(prob), masked=ptr(masked),
+               ws=ptr(ws))
+    _call_named(src.prefix + "ohem_target", env)
     if not (want_prob or want_state):
         return masked
     return (masked,) + ((prob,) if want_prob else ()) + ((ws[:4],) if want_state else ())

@@ -238,16 +238,16 @@ def test_two_runs_are_bit_identical():
 
 @pytest.mark.parametrize("kind", ["dense", "fused"])
 def test_null_weights_agree_with_the_plain_path(kind):
-    """weight=None / label_smoothing=0 / 'mean' through the NEW autograd functions -- forced by the private `_general` switch (a null
-    weight pointer) and by weight=ones(C) -- against the existing plain path, within the fp32 bound; reduction='sum' and
-    label_smoothing=0.1 with a null weight against torch."""
+    """weight=None / label_smoothing=0 / 'mean' through the weighted criterion (the one autograd function's `crit`, entries
+    mrfp_[upsample_]ce_w_*) -- forced by the private `_general` switch (a null weight pointer) and by weight=ones(C) -- against the
+    plain criterion's path, within the fp32 bound; reduction='sum' and label_smoothing=0.1 with a null weight against torch."""
     case, out = (2, 19, 12, 10), (48, 40)
     x, _, y, _ = inputs(case, out, F32, False, 61, 2.0)
     l0, g0 = _run(kind, F32, x, y, out, 19)
-    assert "W" not in type(l0.grad_fn).__name__
+    assert l0.grad_fn.crit.stem == "ce"
     for kw in (dict(_general=True), dict(weight=torch.ones(19, device=DEV))):
         l1, g1 = _run(kind, F32, x, y, out, 19, **kw)
-        assert "W" in type(l1.grad_fn).__name__, type(l1.grad_fn).__name__
+        assert l1.grad_fn.crit.stem == "ce_w" and type(l1.grad_fn) is type(l0.grad_fn), l1.grad_fn.crit.stem
         assert abs(l1.item() - l0.item()) / abs(l0.item()) < LOSS_TOL[F32] and relerr(g1, g0) < GRAD_TOL[F32], kw
     for eps, mode in ((0.0, "sum"), (0.1, "mean")):
         xc = x.double().requires_grad_(True)
@@ -471,3 +471,23 @@ def test_plain_criterion_still_takes_the_plain_launches(model, monkeypatch):
     assert "mrfp_upsample_ce_fwd" in names and "mrfp_upsample_ce_bwd" in names and not [n for n in names if "_ce_w_" in n]
     again = o.upsample_cross_entropy(P.detach(), gts, size, nc, 255)
     assert torch.equal(again, out.detach()) and again.float().item() == loss.item()
+
+
+def test_loss_launches_equal_the_recorded_ones():
+    """tools/record_loss_launches.py replayed: for every case of its list, each entry point the public call reaches, every
+    non-pointer argument by value, every pointer argument as null or not, and the shape, dtype and strides of the returned loss and
+    of the gradient equal tests/golden/loss_launches.json -- recorded once, with the same script, from the commit before the loss
+    operators' six autograd classes became one over (score source, criterion)."""
+    from tools import record_loss_launches as rec
+    from mrfp_amd import _lib
+    hook = _lib.HOOK[0]
+    got = json.loads(json.dumps(rec.record()))
+    assert _lib.HOOK[0] is hook
+    with open(os.path.join(HERE, "golden", "loss_launches.json")) as f:
+        want = json.load(f)
+    assert list(got) == list(want) and len(want) == 408
+    for name in want:
+        assert got[name] == want[name], name
+    entries = {c[0] for v in want.values() for c in v["calls"]}
+    stems = {p + s + d for p in ("mrfp_", "mrfp_upsample_") for s in ("ce", "ce_w", "soft_nll") for d in ("_fwd", "_bwd")}
+    assert entries == stems | {"mrfp_ohem_target", "mrfp_upsample_ohem_target", "mrfp_bilinear_bwd"}
