@@ -350,6 +350,66 @@ int mrfp_upsample_ohem_target(const void* P, int64_t ld, const int64_t* target, 
                               int64_t H, int64_t W, int64_t C, int64_t ignore_index, float thresh, int64_t min_kept,
                               float* prob, int64_t* masked, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Focal loss and the soft Dice / Jaccard region loss (csrc/loss.hip: Focal; csrc/region.hip), the criteria a caller reaches for
+ * when mIoU is the metric.  Build-defined, DESIGN.md section 8.  z_i: the fp32 class vector of pixel i (dense logits, or the
+ * in-kernel align-corners bilinear upsample of P), p_i = softmax(z_i); a pixel is valid iff 0 <= t_i < C and t_i != ignore_index.
+ * 1 <= C <= 64 for both sources: the class vector lives in registers.
+ *
+ * Focal: l_i = -w[t_i] * (1 - p_{i,t})^gamma * log p_{i,t}, gamma >= 0; weight / wstride / mode / ws / loss exactly as mrfp_ce_w_*
+ * (mrfp_ce_w_nblocks, mrfp_ce_w_loss_floats; den_i = w[t_i]); the argument lists are those of mrfp_ce_w_* with gamma where they
+ * have smoothing.  gamma == 0 is the weighted cross entropy, bit for bit in the loss: (1 - p)^0 is the constant 1.  1 - p_t is
+ * sum_{c != t} e_c / sum_c e_c, never a difference, so a pixel whose p_t rounds to 1 has loss 0 and an all-zero gradient for
+ * every gamma.  bwd: dz_j = k * w[t] * (p_j - [j == t]) * ((1 - p_t)^gamma - gamma * p_t * (1 - p_t)^(gamma - 1) * log p_t), k as
+ * mrfp_ce_w_bwd.  The regime of gamma is a branch inside the kernels.
+ *
+ * Region: over the valid pixels of a scope group (per_image == 0: the whole batch, one group; != 0: one group per image), per class
+ *     I_c = sum_i p_{i,c} [t_i == c],   P_c = sum_i p_{i,c},   T_c = #{i : t_i == c}          (T_c an integer count)
+ *     kind MRFP_REGION_DICE:     S_c = (2 I_c + s) / (P_c + T_c + s)
+ *     kind MRFP_REGION_JACCARD:  S_c = (I_c + s) / (P_c + T_c - I_c + s)
+ *     L_g = sum_{c in K} w_c (1 - S_c) / sum_{c in K} w_c,    K = {c : T_c > 0} (present_only != 0) or every c < C
+ *     loss = the mean of L_g over the groups that count: those with sum_{c in K} w_c > 0 (K not empty).  None counts: 0.
+ * s = smooth >= 0 (present_only == 0 needs s > 0); weight: fp32 [C], NULL = ones.  The sums are those of this process's batch.
+ * ws: float [mrfp_region_ws_floats(B, HW, C)]: one partial row [3][CP] per workgroup of the (nbx, B) grid (CP = C rounded up to 8;
+ * I, P as floats, T as uint32), summed by one workgroup in double in a fixed order: no floating-point atomics, two runs are
+ * bit-identical.  out: float [mrfp_region_out_floats(B, C, per_image)], 8-byte aligned, rows = per_image ? B : 1:
+ *     out[0] the loss; out[1] = 1 / (groups that count), 0 if none; then the coefficient table float [rows][2][CP], a_c = dL_g/dI_c
+ *     and b_c = dL_g/dP_c (0 for c outside K and in a group that does not count); then the sums, double [rows][3][C] (I, P, T).
+ * bwd: for a valid pixel of group g, dz_j = k * p_j * (G_j - sum_c p_c G_c), G_c = a_c [t == c] + b_c, k = gscale[0] * out[1]
+ * (gscale NULL = 1); zeros for every other pixel and for pad channels; every row is stored.  The upsample forms work on the
+ * channel-padded scores P[B,Hi,Wi,ld] and write d(logits)[B,H,W,Cd] for mrfp_bilinear_bwd exactly as mrfp_upsample_ce_w_bwd.
+ * Nothing waits for the host: an empty K is decided inside the finalize kernel, so a call can be captured in a graph.
+ * ------------------------------------------------------------------------------------------- */
+int mrfp_focal_fwd(const void* logits, const int64_t* target, int dtype, int64_t B, int64_t HW, int64_t C,
+                   int64_t ignore_index, const float* weight, int64_t wstride, float gamma, int mode, float* ws, float* loss,
+                   void* stream);
+int mrfp_focal_bwd(const void* logits, const int64_t* target, const float* loss, const float* gscale, void* dlogits,
+                   int dtype, int64_t B, int64_t HW, int64_t C, int64_t ignore_index, const float* weight, int64_t wstride,
+                   float gamma, int mode, void* stream);
+int mrfp_upsample_focal_fwd(const void* P, int64_t ld, const int64_t* target, int dtype, int64_t B, int64_t Hi, int64_t Wi,
+                            int64_t H, int64_t W, int64_t C, int64_t ignore_index, const float* weight, int64_t wstride,
+                            float gamma, int mode, float* ws, float* loss, void* stream);
+int mrfp_upsample_focal_bwd(const void* P, int64_t ld, const int64_t* target, const float* loss, const float* gscale,
+                            void* dlogits, int64_t Cd, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
+                            int64_t C, int64_t ignore_index, const float* weight, int64_t wstride, float gamma, int mode,
+                            void* stream);
+
+typedef enum { MRFP_REGION_DICE = 0, MRFP_REGION_JACCARD = 1 } mrfp_region_kind;
+int64_t mrfp_region_nblocks(int64_t B, int64_t HW);
+int64_t mrfp_region_ws_floats(int64_t B, int64_t HW, int64_t C);
+int64_t mrfp_region_out_floats(int64_t B, int64_t C, int per_image);
+int mrfp_region_fwd(const void* logits, const int64_t* target, int dtype, int64_t B, int64_t HW, int64_t C,
+                    int64_t ignore_index, const float* weight, int kind, float smooth, int present_only, int per_image,
+                    float* ws, float* out, void* stream);
+int mrfp_region_bwd(const void* logits, const int64_t* target, const float* out, const float* gscale, void* dlogits,
+                    int dtype, int64_t B, int64_t HW, int64_t C, int64_t ignore_index, int per_image, void* stream);
+int mrfp_upsample_region_fwd(const void* P, int64_t ld, const int64_t* target, int dtype, int64_t B, int64_t Hi, int64_t Wi,
+                             int64_t H, int64_t W, int64_t C, int64_t ignore_index, const float* weight, int kind, float smooth,
+                             int present_only, int per_image, float* ws, float* out, void* stream);
+int mrfp_upsample_region_bwd(const void* P, int64_t ld, const int64_t* target, const float* out, const float* gscale,
+                             void* dlogits, int64_t Cd, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
+                             int64_t C, int64_t ignore_index, int per_image, void* stream);
+
 /* Eval: argmax over classes + 19x19 confusion histogram on the device (reference main.py:898-909,
  * metrics.py:122-126): hist[num_classes*gt + pred] += 1 for gt in [0,num_classes).  hist: int64
  * [C*C], accumulated (not cleared).  pred (optional, uint8 [npix]) receives the arg-max. */

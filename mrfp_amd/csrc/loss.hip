@@ -450,6 +450,79 @@ static int ce_w_check(const char* who, int64_t B, int64_t C, int64_t wstride, fl
     return 0;
 }
 
+// ---- focal loss (include/mrfp_hip.h: mrfp_focal_*, mrfp_upsample_focal_*) -----------------------------------------------------
+// The weighted cross entropy of a pixel times (1 - p_t)^gamma: a criterion of the skeleton, forward and backward, over both
+// sources, with WeightedCe's labels, staging, partials, finalize and modes.  q = 1 - p_t is sum_{c != t} e_c / sum_c e_c, a sum and
+// never a difference: a pixel whose p_t rounds to 1 has q == 0 exactly, and its loss and gradient are zeros for every gamma.
+// gamma == 0 takes the branch in which the modulation is the constant 1: the forward is then WeightedCe's arithmetic, term for term.
+struct Focal {
+    static constexpr int kLdsFloats = kMaxClasses + 1, kMaxClassPad = kMaxClasses;
+    static constexpr double kDenBias = 0.0;
+    const int64_t* target; int64_t ignore; const float* weight; int64_t wstride; float gamma; int mode;
+
+    __device__ __forceinline__ void stage(float* sw, int b, int C) const { ce_stage_weights(sw, weight, wstride, b, C); }
+    __device__ __forceinline__ int64_t label(int64_t tg, int) const { return tg; }
+    __device__ __forceinline__ bool valid(int64_t tg, int C) const { return !(tg == ignore || tg < 0 || tg >= C); }
+    __device__ __forceinline__ float bwd_factor(const float* __restrict__ loss, const float* __restrict__ gscale, int b) const {
+        return ce_w_bwd_factor(loss, gscale, mode, b);
+    }
+    // q^gamma for q in [0, 1], gamma > 0: 0 at q == 0
+    __device__ __forceinline__ float qpow(float q) const { return q > 0.f ? __expf(gamma * __logf(q)) : 0.f; }
+
+    template <int CP>
+    __device__ __forceinline__ void add_loss(const float (&z)[CP], int C, int64_t tg, const float* sw, float& num, float& den) const {
+        float m = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < CP; ++c) if (c < C) m = fmaxf(m, z[c]);
+        float s = 0.f, so = 0.f, zt = 0.f;
+#pragma unroll
+        for (int c = 0; c < CP; ++c)
+            if (c < C) {
+                const float e = __expf(z[c] - m);
+                s += e;
+                so += (c == (int)tg) ? 0.f : e;
+                zt = (c == (int)tg) ? z[c] : zt;
+            }
+        const float lse = m + __logf(s), wt = sw[(int)tg];
+        float v = wt * (lse - zt);
+        if (gamma != 0.f) v *= qpow(so / s);
+        num += v;
+        den += wt;
+    }
+
+    // g: the class vector in, its gradient out.  F = q^gamma + gamma p_t q^(gamma-1) (-log p_t), q^(gamma-1) as q^gamma / q; at
+    // q == 0 the factor is 0 (its limit for every gamma > 0, and every p_j - [j == t] is 0 there as well).
+    template <int CP>
+    __device__ __forceinline__ void grad(float (&g)[CP], int C, int64_t tg, const float* sw, float k) const {
+        float m = -INFINITY, zt = 0.f;
+#pragma unroll
+        for (int c = 0; c < CP; ++c)
+            if (c < C) { m = fmaxf(m, g[c]); zt = (c == (int)tg) ? g[c] : zt; }
+        float s = 0.f, so = 0.f, et = 0.f;
+#pragma unroll
+        for (int c = 0; c < CP; ++c) {
+            g[c] = c < C ? __expf(g[c] - m) : 0.f;
+            s += g[c];
+            so += (c == (int)tg) ? 0.f : g[c];
+            et = (c == (int)tg) ? g[c] : et;
+        }
+        float F = 1.f;
+        if (gamma != 0.f) {
+            const float q = so / s, qg = qpow(q), nlp = __logf(s) - (zt - m);       // -log p_t, the difference first
+            F = q > 0.f ? qg + gamma * (et / s) * (qg / q) * nlp : 0.f;
+        }
+        const float wt = sw[(int)tg] * F, A = wt / s;
+#pragma unroll
+        for (int c = 0; c < CP; ++c) g[c] = c < C ? (g[c] * A - (c == (int)tg ? wt : 0.f)) * k : 0.f;
+    }
+};
+
+static int focal_check(const char* who, int64_t B, int64_t C, int64_t wstride, float gamma, int mode) {
+    MRFP_CHECK(C >= 1 && C <= kMaxClasses, "%s: 1 <= C <= %d (C=%lld)", who, kMaxClasses, (long long)C);
+    MRFP_CHECK(gamma >= 0.f && gamma <= 3.0e38f, "%s: gamma must be a finite number >= 0 (got %g)", who, (double)gamma);
+    return ce_w_check(who, B, C, wstride, 0.f, mode);
+}
+
 // ---- per-image class weights from the label map ------------------------------------------------------------------------------
 constexpr int kHistMaxClasses = 1024;
 
@@ -567,6 +640,49 @@ int mrfp_upsample_ce_w_bwd(const void* P, int64_t ld, const int64_t* target, con
                            (const T*)P, src.ld, target, loss, gscale, (T*)dlogits, src.Cd, src.Hi, src.Wi, src.H, src.W, src.C, ignore_index,
                            weight, wstride, smoothing, mode);
     });
+}
+
+int mrfp_focal_fwd(const void* logits, const int64_t* target, int dtype, int64_t B, int64_t HW, int64_t C, int64_t ignore_index,
+                   const float* weight, int64_t wstride, float gamma, int mode, float* ws, float* loss, void* stream) {
+    const char* who = "focal_fwd";
+    MRFP_CHECK(logits && target && ws && loss && B > 0 && HW > 0, "%s: bad arguments", who);
+    if (int rc = mrfp::focal_check(who, B, C, wstride, gamma, mode)) return rc;
+    return mrfp::launch_pixel_loss_fwd(who, dtype, B, mrfp::DenseRows{logits, nullptr, HW, (int)C},
+                                       mrfp::Focal{target, ignore_index, weight, wstride, gamma, mode}, ws, loss, (hipStream_t)stream);
+}
+
+int mrfp_focal_bwd(const void* logits, const int64_t* target, const float* loss, const float* gscale, void* dlogits, int dtype,
+                   int64_t B, int64_t HW, int64_t C, int64_t ignore_index, const float* weight, int64_t wstride, float gamma, int mode,
+                   void* stream) {
+    const char* who = "focal_bwd";
+    MRFP_CHECK(logits && target && loss && dlogits && B > 0 && HW > 0, "%s: bad arguments", who);
+    if (int rc = mrfp::focal_check(who, B, C, wstride, gamma, mode)) return rc;
+    return mrfp::launch_pixel_loss_bwd(who, dtype, B, mrfp::DenseRows{logits, dlogits, HW, (int)C},
+                                       mrfp::Focal{target, ignore_index, weight, wstride, gamma, mode}, loss, gscale, (hipStream_t)stream);
+}
+
+int mrfp_upsample_focal_fwd(const void* P, int64_t ld, const int64_t* target, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H,
+                            int64_t W, int64_t C, int64_t ignore_index, const float* weight, int64_t wstride, float gamma, int mode,
+                            float* ws, float* loss, void* stream) {
+    const char* who = "upsample_focal_fwd";
+    MRFP_CHECK(P && target && ws && loss && B > 0, "%s: bad arguments", who);
+    if (int rc = mrfp::focal_check(who, B, C, wstride, gamma, mode)) return rc;
+    mrfp::BilinearRows src;
+    if (int rc = mrfp::bilinear_rows(who, P, ld, nullptr, 0, false, dtype, Hi, Wi, H, W, C, src)) return rc;
+    return mrfp::launch_pixel_loss_fwd(who, dtype, B, src, mrfp::Focal{target, ignore_index, weight, wstride, gamma, mode}, ws, loss,
+                                       (hipStream_t)stream);
+}
+
+int mrfp_upsample_focal_bwd(const void* P, int64_t ld, const int64_t* target, const float* loss, const float* gscale, void* dlogits,
+                            int64_t Cd, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W, int64_t C,
+                            int64_t ignore_index, const float* weight, int64_t wstride, float gamma, int mode, void* stream) {
+    const char* who = "upsample_focal_bwd";
+    MRFP_CHECK(P && target && loss && dlogits && B > 0, "%s: bad arguments", who);
+    if (int rc = mrfp::focal_check(who, B, C, wstride, gamma, mode)) return rc;
+    mrfp::BilinearRows src;
+    if (int rc = mrfp::bilinear_rows(who, P, ld, dlogits, Cd, false, dtype, Hi, Wi, H, W, C, src)) return rc;
+    return mrfp::launch_pixel_loss_bwd(who, dtype, B, src, mrfp::Focal{target, ignore_index, weight, wstride, gamma, mode}, loss, gscale,
+                                       (hipStream_t)stream);
 }
 
 int mrfp_label_class_weights(const int64_t* target, int64_t B, int64_t HW, int64_t C, double upper_bound, int norm, int batch,

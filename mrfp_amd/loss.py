@@ -18,6 +18,11 @@ source is not in the reference tree: include/mrfp_hip.h and DESIGN.md section 8 
 the full-resolution logits, sorts every probability and branches on a host value; here the kept set is chosen by device kernels
 with no host wait (csrc/ohem.hip: probability plane, exact radix select, masked target) and the loss is the fused cross entropy on
 the masked target.
+
+FocalLoss2d and RegionLoss2d are the two families a caller reaches for when mIoU, not pixel accuracy, is the metric: a focal term
+that down-weights easy pixels, and the soft Dice / Jaccard overlap term, a direct surrogate of the IoU harness.evaluate reports,
+almost always used as CE + lambda * Dice -- SumLoss.  Neither is in the reference tree: include/mrfp_hip.h and DESIGN.md section 8
+hold the definitions; the kernels are csrc/loss.hip (Focal) and csrc/region.hip.
 """
 from __future__ import annotations
 
@@ -26,7 +31,8 @@ from torch import nn
 
 from . import ops
 
-__all__ = ["ImageBasedCrossEntropyLoss2d", "ImgWtLossSoftNLL", "OhemCrossEntropy2d", "fused_ce_kwargs", "fused_loss"]
+__all__ = ["ImageBasedCrossEntropyLoss2d", "ImgWtLossSoftNLL", "OhemCrossEntropy2d", "FocalLoss2d", "RegionLoss2d", "SumLoss",
+           "fused_ce_kwargs", "fused_loss"]
 
 
 class ImageBasedCrossEntropyLoss2d(nn.Module):
@@ -123,13 +129,107 @@ class OhemCrossEntropy2d(nn.Module):
         return self.fused(inputs, targets)
 
 
+class FocalLoss2d(nn.Module):
+    """-w[t] (1 - p_t)^gamma log p_t over the valid pixels, reduced as nn.CrossEntropyLoss(weight, ignore_index, reduction) reduces:
+    'mean' divides by the sum of the target weights.  gamma = 0 is that cross entropy.  At most 64 classes."""
+
+    def __init__(self, gamma=2.0, weight=None, ignore_index=255, reduction="mean"):
+        super().__init__()
+        self.gamma = ops._focal_options("FocalLoss2d", gamma)
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("FocalLoss2d: reduction must be 'mean', 'sum' or 'none' (got %r)" % (reduction,))
+        self.ignore_index, self.reduction = int(ignore_index), reduction
+        # moves with the model, stays out of its state_dict
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32).detach().clone(),
+                             persistent=False)
+
+    def fused(self, logits, gts, size=None, channels=None):
+        """The loss on the kernels: of dense logits, or with `size` of the channel-padded low-resolution scores.  reduction='none'
+        has no kernel: the operator refuses it."""
+        kw = dict(gamma=self.gamma, weight=self.weight, reduction=self.reduction)
+        if size is not None:
+            return ops.upsample_focal_loss(logits, gts, size, channels, self.ignore_index, **kw)
+        return ops.focal_loss(logits, gts, self.ignore_index, **kw)
+
+    def forward(self, inputs, targets):
+        return self.fused(inputs, targets)
+
+
+class RegionLoss2d(nn.Module):
+    """The soft Dice (kind='dice') or Jaccard ('jaccard') loss of softmax(inputs) against the one-hot targets over the valid pixels:
+    the weighted mean over the classes of 1 - S_c, S_c = (2 I_c + s) / (P_c + T_c + s) or (I_c + s) / (P_c + T_c - I_c + s), over the
+    classes present in the scope (present_only) or all of them (needs smooth > 0).  The scope is the whole batch of this rank -- under
+    data parallelism the sums are per rank, like the OHEM selection -- or each image (per_image), averaged over the images that have
+    a class.  Nothing valid: 0.  At most 64 classes."""
+
+    def __init__(self, kind="dice", smooth=1.0, present_only=True, weight=None, ignore_index=255, per_image=False):
+        super().__init__()
+        _, self.smooth, self.present_only, _ = ops._region_options("RegionLoss2d", kind, smooth, present_only, None, None, None)
+        self.kind, self.ignore_index, self.per_image = kind, int(ignore_index), bool(per_image)
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32).detach().clone(),
+                             persistent=False)
+
+    def fused(self, logits, gts, size=None, channels=None):
+        """The loss on the kernels: of dense logits, or with `size` of the channel-padded low-resolution scores."""
+        kw = dict(kind=self.kind, smooth=self.smooth, present_only=self.present_only, weight=self.weight, per_image=self.per_image)
+        if size is not None:
+            return ops.upsample_region_loss(logits, gts, size, channels, self.ignore_index, **kw)
+        return ops.region_loss(logits, gts, self.ignore_index, **kw)
+
+    def forward(self, inputs, targets):
+        return self.fused(inputs, targets)
+
+
+class SumLoss(nn.Module):
+    """sum_k w_k * crit_k(inputs, targets): SumLoss((1.0, nn.CrossEntropyLoss(ignore_index=255)), (0.5, RegionLoss2d())).  Its fused
+    form is the same sum of the parts' fused forms over the same scores; it has one only if every part has."""
+
+    def __init__(self, *parts):
+        super().__init__()
+        if not parts:
+            raise ValueError("SumLoss: at least one (weight, criterion) pair")
+        for part in parts:
+            if not (isinstance(part, (tuple, list)) and len(part) == 2 and isinstance(part[1], nn.Module)):
+                raise ValueError("SumLoss: every part is a (weight, criterion module) pair (got %r)" % (part,))
+        self.weights = [float(w) for w, _ in parts]
+        self.criteria = nn.ModuleList([c for _, c in parts])
+
+    def parts(self):
+        return list(zip(self.weights, self.criteria))
+
+    def fused(self, logits, gts, size=None, channels=None):
+        """sum_k w_k * fused_loss(crit_k, ...), or None if a part has no fused form."""
+        if any(fused_ce_kwargs(c) is None for c in self.criteria):
+            return None
+        total = None
+        for w, c in self.parts():
+            term = w * fused_loss(c, logits, gts, size, channels)
+            total = term if total is None else total + term
+        return total
+
+    def forward(self, inputs, targets):
+        total = self.fused(inputs, targets)
+        if total is None:          # a part the kernels do not compute: every part as its module computes it
+            for w, c in self.parts():
+                term = w * c(inputs, targets)
+                total = term if total is None else total + term
+        return total
+
+
 def fused_ce_kwargs(criterion):
     """The keyword arguments with which ops.cross_entropy / ops.upsample_cross_entropy compute `criterion`, or None for a criterion
     they cannot (reduction='none', a foreign module): that one keeps the stock call on the full-resolution fp32 logits.  `weight` is
     a tensor, None, or -- for the per-image criterion -- a callable of the label map (fused_loss calls it).  ImgWtLossSoftNLL is not a
     cross entropy: its entry is dict(soft_nll=<its own fused call>), which fused_loss calls with (logits, gts, size, channels);
-    OhemCrossEntropy2d chooses its pixels first: dict(ohem=<its own fused call>), called the same way."""
+    OhemCrossEntropy2d chooses its pixels first: dict(ohem=<its own fused call>), called the same way; so are FocalLoss2d (dict(focal=),
+    None with reduction='none'), RegionLoss2d (dict(region=)) and SumLoss (dict(sum=), None if a part has none)."""
     c = criterion
+    if isinstance(c, FocalLoss2d):
+        return dict(focal=c.fused) if c.reduction in ("mean", "sum") else None
+    if isinstance(c, RegionLoss2d):
+        return dict(region=c.fused)
+    if isinstance(c, SumLoss):
+        return None if any(fused_ce_kwargs(p) is None for p in c.criteria) else dict(sum=c.fused)
     if isinstance(c, OhemCrossEntropy2d):
         return dict(ohem=c.fused)
     if isinstance(c, ImgWtLossSoftNLL):          # not a cross entropy: fused_loss hands the call to the criterion's own kernels
@@ -148,7 +248,7 @@ def fused_loss(criterion, logits, gts, size=None, channels=None):
     kw = fused_ce_kwargs(criterion)
     if kw is None:
         return None
-    for own in ("soft_nll", "ohem"):
+    for own in ("soft_nll", "ohem", "focal", "region", "sum"):
         if own in kw:
             return kw[own](logits, gts, size, channels)
     ignore = kw.pop("ignore_index")

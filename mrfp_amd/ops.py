@@ -951,7 +951,7 @@ def add(a, b):
 # ------------------------------------------------------------------------------------------
 # The loss operators have the two axes of the kernels under them (csrc/loss_common.hpp): where a pixel's class vector comes from
 # (_Scores: dense logits, or low-resolution scores the kernel upsamples) and which criterion reads it (_PlainCe, _WeightedCe,
-# _SoftNll).  One autograd function, _PixelLoss, serves every pair; the entry is mrfp_[upsample_]<stem>_{fwd,bwd}, and its arguments
+# _SoftNll, _Focal).  One autograd function, _PixelLoss, serves every pair (the region loss has a sibling, _RegionLoss); the entry is mrfp_[upsample_]<stem>_{fwd,bwd}, and its arguments
 # are looked up by the names include/mrfp_hip.h gives them, never placed by position.
 def _call_named(entry, env):
     """Calls `entry` with its positional arguments taken from env, a dictionary of named values to which the stream is added here; a
@@ -1346,6 +1346,170 @@ def upsample_ohem_cross_entropy(P, target, size, channels, ignore_index=255, *, 
     on the masked target ohem_target computes from the same low-resolution scores."""
     masked = ohem_target(P, target, ignore_index, thresh, min_kept, size=size, channels=channels)
     return upsample_cross_entropy(P, masked, size, channels, ignore_index, weight=weight)
+
+
+# ---- focal loss and the soft Dice / Jaccard region loss (csrc/loss.hip: Focal; csrc/region.hip; include/mrfp_hip.h and DESIGN.md
+# section 8 hold the definitions).  Focal is one more criterion record of _PixelLoss.  The region loss needs per-class sums over its
+# scope before any pixel has a gradient, so its workspace and saved tensors differ: a sibling function, _RegionLoss, again one
+# for both sources ----
+LOSS_MAX_CLASSES = 64                     # kMaxClasses: the class vector of a pixel lives in registers
+REGION_KINDS = {"dice": 0, "jaccard": 1}  # mrfp_region_kind
+
+
+def _class_limit(who, C):
+    if not 1 <= int(C) <= LOSS_MAX_CLASSES:
+        raise _lib.MrfpHipError("%s: 1 <= C <= %d: the class vector of a pixel lives in registers (C=%d)" % (who, LOSS_MAX_CLASSES, C))
+
+
+def _focal_options(who, gamma):
+    """-> gamma as a float, validated without touching the device."""
+    try:
+        g = float(gamma)
+    except (TypeError, ValueError):
+        g = float("nan")
+    if not 0.0 <= g < float("inf"):           # also false for a NaN
+        raise _lib.MrfpHipError("%s: gamma must be a finite number >= 0 (got %r)" % (who, gamma))
+    return g
+
+
+class _Focal(_WeightedCe):
+    """-w[t] (1 - p_t)^gamma log p_t with the reductions of the weighted cross entropy (mrfp_[upsample_]focal_*): a criterion record,
+    as _PlainCe.  gamma == 0 is the weighted cross entropy."""
+    stem = "focal"
+
+    def __init__(self, who, ignore_index, gamma, reduction, per_image):
+        _WeightedCe.__init__(self, who, ignore_index, 0.0, reduction, per_image)
+        self.gamma = _focal_options(who, gamma)
+
+    def check(self, src, target, weight):
+        _class_limit(self.who, src.C)
+        return _WeightedCe.check(self, src, target, weight)
+
+    def extra(self, weight):
+        return dict(ignore_index=int(self.ignore_index), weight=ptr(weight), wstride=self.wstride, gamma=self.gamma, mode=self.mode)
+
+
+def focal_loss(logits, target, ignore_index=255, *, gamma=2.0, weight=None, reduction="mean", per_image=False):
+    """logits [B,C,H,W], C <= 64; target int64 [B,H,W].  sum_i -w[t_i] (1 - p_{i,t_i})^gamma log p_{i,t_i} over the valid pixels, reduced
+    as cross_entropy reduces ('mean': over the sum of the target weights; 'sum'; per_image: the sum of the per-image means).  weight:
+    float32 [C] or [B, C] on the device.  -> fp32 scalar."""
+    return _PixelLoss.apply(logits, target, weight, None, None, _Focal("focal_loss", ignore_index, gamma, reduction, per_image))
+
+
+def upsample_focal_loss(P, target, size, channels, ignore_index=255, *, gamma=2.0, weight=None, reduction="mean", per_image=False):
+    """focal_loss of Upsample(P[:, :channels], size) without materialising the full-resolution logits.  P: channel-padded
+    low-resolution class scores [B,ld,Hi,Wi] (ld a multiple of the 16-byte chunk)."""
+    return _PixelLoss.apply(P, target, weight, (int(size[0]), int(size[1])), int(channels),
+                            _Focal("upsample_focal_loss", ignore_index, gamma, reduction, per_image))
+
+
+def _region_options(who, kind, smooth, present_only, weight, C, device):
+    """-> (kind id, smooth, present_only, weight fp32 [C] or None), validated without touching the device."""
+    if kind not in REGION_KINDS:
+        raise _lib.MrfpHipError("%s: kind must be 'dice' or 'jaccard' (got %r)" % (who, kind))
+    try:
+        s = float(smooth)
+    except (TypeError, ValueError):
+        s = float("nan")
+    if not 0.0 <= s < float("inf"):
+        raise _lib.MrfpHipError("%s: smooth must be a finite number >= 0 (got %r)" % (who, smooth))
+    present_only = bool(present_only)
+    if not present_only and s <= 0.0:
+        raise _lib.MrfpHipError("%s: present_only=False needs smooth > 0: an absent class has an empty denominator (got %r)" % (who, smooth))
+    if C is not None:
+        _class_limit(who, C)
+    if weight is not None and C is not None:
+        if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or weight.device != device or tuple(weight.shape) != (C,):
+            raise _lib.MrfpHipError("%s: weight must be a float32 tensor of shape [C] on %s (C=%d; got %s)" % (
+                who, device, C, (weight.dtype, tuple(weight.shape), weight.device) if isinstance(weight, torch.Tensor) else type(weight)))
+        weight = weight.detach().contiguous()
+    return REGION_KINDS[kind], s, present_only, weight
+
+
+class _Region:
+    """The soft Dice / Jaccard loss over per-class sums (mrfp_[upsample_]region_*): a criterion record, as _PlainCe, of _RegionLoss."""
+    stem = "region"
+
+    def __init__(self, who, ignore_index, kind="dice", smooth=1.0, present_only=True, per_image=False):
+        self.who, self.ignore_index, self.per_image = who, ignore_index, bool(per_image)
+        self.options = (kind, smooth, present_only)
+        _region_options(who, kind, smooth, present_only, None, None, None)         # what does not depend on the tensors: at once
+
+    def check(self, src, target, weight):
+        self.kind, self.smooth, self.present_only, weight = _region_options(self.who, *self.options, weight, src.C, src.x.device)
+        return _chk_target(self.who, target, torch.int64, 3, (src.B, src.H, src.W)), weight
+
+    def extra(self, weight):
+        return dict(ignore_index=int(self.ignore_index), weight=ptr(weight), kind=self.kind, smooth=self.smooth,
+                    present_only=int(self.present_only), per_image=int(self.per_image))
+
+    def rows(self, src):
+        return src.B if self.per_image else 1
+
+
+def _region_forward(src, crit, target, weight):
+    """Sums pass and finalize -> (validated target, out): out[0] the loss, out[1] the factor of the backward, the coefficient table,
+    the sums (include/mrfp_hip.h)."""
+    target, weight = crit.check(src, target, weight)
+    L, dev = _lib.lib(), src.x.device
+    ws = torch.empty(int(L.mrfp_region_ws_floats(src.B, src.H * src.W, src.C)), dtype=torch.float32, device=dev)
+    out = torch.empty(int(L.mrfp_region_out_floats(src.B, src.C, int(crit.per_image))), dtype=torch.float32, device=dev)
+    env = _loss_env(src, crit, target, weight, out)
+    env.update(ws=ptr(ws), out=ptr(out))
+    _call_named(src.prefix + crit.stem + "_fwd", env)
+    return target, out
+
+
+class _RegionLoss(torch.autograd.Function):
+    """loss = the region criterion of the class scores of (x, size, channels) at full resolution: two launches forward (sums,
+    finalize; neither waits for the host), one backward plus the bilinear backward of the fused source."""
+
+    @staticmethod
+    def forward(ctx, x, target, weight, size, channels, crit):
+        src = _Scores(_chk(x, "logits" if size is None else "P"), size, channels)
+        target, out = _region_forward(src, crit, target, weight)
+        ctx.save_for_backward(src.x, target, out)
+        ctx.size, ctx.channels, ctx.crit = size, channels, crit
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        x, target, out = ctx.saved_tensors
+        src, crit = _Scores(x, ctx.size, ctx.channels), ctx.crit
+        gs = g.detach().float().reshape(1).contiguous()
+        env = _loss_env(src, crit, target, None, out)
+        env.update(out=ptr(out), gscale=ptr(gs))
+        return src.grad(src.prefix + crit.stem + "_bwd", env), None, None, None, None, None
+
+
+def region_loss(logits, target, ignore_index=255, *, kind="dice", smooth=1.0, present_only=True, weight=None, per_image=False):
+    """The soft Dice (kind 'dice') or Jaccard ('jaccard') loss of softmax(logits) against the one-hot target over the valid pixels:
+    with I_c = sum p_c [t = c], P_c = sum p_c, T_c = #{t = c}, S_c = (2 I_c + s) / (P_c + T_c + s) (dice) or (I_c + s) / (P_c + T_c - I_c +
+    s) (jaccard), the weighted mean of 1 - S_c over the classes present in the scope (present_only) or over all (needs smooth > 0).
+    The scope is the whole batch OF THIS RANK -- under data parallelism the sums are per rank, like the OHEM selection -- or with
+    per_image each image, averaged over the images that have a class.  Nothing valid: 0, and a zero gradient.  logits [B,C,H,W], C <= 64;
+    weight: float32 [C] on the device.  -> fp32 scalar."""
+    return _RegionLoss.apply(logits, target, weight, None, None, _Region("region_loss", ignore_index, kind, smooth, present_only, per_image))
+
+
+def upsample_region_loss(P, target, size, channels, ignore_index=255, *, kind="dice", smooth=1.0, present_only=True, weight=None,
+                         per_image=False):
+    """region_loss of Upsample(P[:, :channels], size) without materialising the full-resolution logits (per-rank sums, as
+    region_loss).  P: channel-padded low-resolution class scores [B,ld,Hi,Wi] (ld a multiple of the 16-byte chunk)."""
+    return _RegionLoss.apply(P, target, weight, (int(size[0]), int(size[1])), int(channels),
+                             _Region("upsample_region_loss", ignore_index, kind, smooth, present_only, per_image))
+
+
+def region_sums(logits, target, ignore_index=255, *, size=None, channels=None, per_image=False):
+    """The sums the region loss is made of, float64 [rows, 3, C] on the device (rows = B with per_image, else 1; I_c, P_c, T_c), of
+    this rank's batch.  With `size`, logits are the channel-padded low-resolution scores.  No autograd through it."""
+    crit = _Region("region_sums", ignore_index, per_image=per_image)
+    fused = size is not None
+    src = _Scores(_chk(logits.detach(), "P" if fused else "logits"), (int(size[0]), int(size[1])) if fused else None,
+                  int(channels) if fused else None)
+    _, out = _region_forward(src, crit, target, None)
+    rows, CP = crit.rows(src), (src.C + 7) // 8 * 8
+    return out[2 + rows * 2 * CP:].view(torch.float64).view(rows, 3, src.C).clone()
 
 
 # ------------------------------------------------------------------------------------------
