@@ -625,6 +625,40 @@ int mrfp_sgd_step_checked(float* p, const float* g, float* m, int64_t n, float l
                           float weight_decay, const void* state, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Weight averaging inside the step: a fourth arena e, the same size as p, holds an exponential moving average (EMA) or the
+ * equal-weight mean (SWA) of the parameters after applied steps, updated while the fresh p is still in the step kernel's registers.
+ * The reference keeps the last iterate only (main.py:857-869): build-defined; yardstick
+ * torch.optim.swa_utils.AveragedModel over the parameters.
+ *
+ * The averaging rule.  t = 1-based count of APPLIED optimiser steps (a step the check skipped does not count).  An update happens
+ * after step t iff t >= start and (t - start) % every == 0; its index is n = (t - start) / every.
+ *   n == 0:  e = p, a bit copy of the parameters this step has just written; e is not read.
+ *   n >= 1:  e = e + c * (p - e), three separately rounded fp32 operations (sub, mul, add), which is what torch's
+ *            `e + c * (p - e)` gives bit for bit.  c is formed in double with IEEE operations and rounded to float once:
+ *              kind 1 (swa):  c = 1 / (n + 1), the running arithmetic mean;
+ *              kind 0 (ema):  d = warmup ? min(decay, (1 + n) / (10 + n)) : decay;  c = 1 - d.
+ * Every thread evaluates the rule once from by-value arguments; a step that makes no update neither reads nor writes e.
+ *
+ * mrfp_sgd_step_avg: mrfp_sgd_step's update (p and m leave it with the same bits) followed by the rule for the step count t the
+ *   host passes.  Streams 28 bytes per element against 20 when it updates with n >= 1, 24 when n == 0, 20 when it does not.
+ * mrfp_sgd_step_checked_avg: mrfp_sgd_step_checked's update with t = state.taken + taken_base read on the device, after
+ *   mrfp_grad_check has counted this step; found_inf set -> writes nothing, e included.  taken_base = (applied steps before this
+ *   state started counting) - (state.taken at that moment): a resumed run passes what its checkpoint recorded.
+ * mrfp_arena_swap: exchanges a[0..n) and b[0..n) bit for bit (NaN payloads included); the ranges must not overlap.
+ * All three: one streaming launch, 16-byte loads and stores, the capped grid of mrfp_sgd_step, no LDS, no atomics, nothing outside
+ *   [0, n) touched.
+ * Refused before any launch: null pointers (e included), n <= 0, n % 4 != 0, a misaligned arena or state, an unknown kind, decay
+ * outside (0, 1) (checked for both kinds), start < 1, every < 1, overlapping swap ranges.
+ * ------------------------------------------------------------------------------------------- */
+int mrfp_sgd_step_avg(float* p, const float* g, float* m, float* e, int64_t n, float lr, float momentum,
+                      float weight_decay, float gscale, int first, int kind, double decay, int warmup, int start,
+                      int every, int t, void* stream);
+int mrfp_sgd_step_checked_avg(float* p, const float* g, float* m, float* e, int64_t n, float lr, float momentum,
+                              float weight_decay, const void* state, int taken_base, int kind, double decay, int warmup,
+                              int start, int every, void* stream);
+int mrfp_arena_swap(float* a, float* b, int64_t n, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Group whitening passes (groups of 16 channels; reference network/sync_switchwhiten.py:20-26, 161-170:
  * in_data.mean(-1), bmm(in_data, in_data^T) per group; :217 bmm(wm, in_data); network/instance_whitening.py):
  *   mrfp_group_moments: M[b,g,i,j] = sum_p a[b,p,16g+i] * b[b,p,16g+j]  (fp32 [B,C/16,16,16]) and, when sum_a != NULL,

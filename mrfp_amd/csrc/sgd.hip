@@ -9,6 +9,10 @@
 // Checked form (no reference counterpart: the reference trains in fp32; yardstick torch.amp.GradScaler + clip_grad_norm_):
 // mrfp_grad_check reads the gradient arena once more and leaves {found_inf, grad_norm, gmul, new loss scale} in a device step
 // state, mrfp_sgd_step_checked applies the same update with gmul in place of gscale, or nothing at all.
+//
+// Averaged forms (no reference counterpart; yardstick torch.optim.swa_utils.AveragedModel): mrfp_sgd_step_avg and
+// mrfp_sgd_step_checked_avg make the same update and, while the fresh p is still in registers, fold it into a fourth arena e, an
+// exponential moving average or the running mean of the applied steps (include/mrfp_hip.h: the averaging rule).
 #include "common.hpp"
 
 namespace mrfp {
@@ -27,20 +31,32 @@ static_assert(sizeof(StepState) == 32, "step state: eight 32-bit words");
 
 constexpr int kArenaCap = 4096;            // workgroups of the streaming arena kernels (step, checked step, accumulate): 16 per CU
 
+// The update of one 16-byte vector in its three parts, shared by the four step kernels so that p and m leave all of them with the
+// same bits:  g' = g*gscale + wd*p ;  m = g' (first step) | mu*m + g' ;  p -= lr*m.
+__device__ __forceinline__ void sgd_grad(float4& gv, const float4& pv, float gscale, float wd) {
+    gv.x = gv.x * gscale + wd * pv.x; gv.y = gv.y * gscale + wd * pv.y;
+    gv.z = gv.z * gscale + wd * pv.z; gv.w = gv.w * gscale + wd * pv.w;
+}
+__device__ __forceinline__ void sgd_momentum(float4& mv, const float4& gv, float mu) {
+    mv.x = mu * mv.x + gv.x; mv.y = mu * mv.y + gv.y; mv.z = mu * mv.z + gv.z; mv.w = mu * mv.w + gv.w;
+}
+__device__ __forceinline__ void sgd_apply(float4& pv, const float4& mv, float lr) {
+    pv.x -= lr * mv.x; pv.y -= lr * mv.y; pv.z -= lr * mv.z; pv.w -= lr * mv.w;
+}
+
 __global__ __launch_bounds__(256) void sgd_kernel(float4* __restrict__ p, const float4* __restrict__ g,
                                                   float4* __restrict__ m, int64_t n4, float lr, float mu, float wd,
                                                   float gscale, int first) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         float4 pv = p[i], gv = g[i], mv;
-        gv.x = gv.x * gscale + wd * pv.x; gv.y = gv.y * gscale + wd * pv.y;
-        gv.z = gv.z * gscale + wd * pv.z; gv.w = gv.w * gscale + wd * pv.w;
+        sgd_grad(gv, pv, gscale, wd);
         if (first) {
             mv = gv;
         } else {
             mv = m[i];
-            mv.x = mu * mv.x + gv.x; mv.y = mu * mv.y + gv.y; mv.z = mu * mv.z + gv.z; mv.w = mu * mv.w + gv.w;
+            sgd_momentum(mv, gv, mu);
         }
-        pv.x -= lr * mv.x; pv.y -= lr * mv.y; pv.z -= lr * mv.z; pv.w -= lr * mv.w;
+        sgd_apply(pv, mv, lr);
         m[i] = mv;
         p[i] = pv;
     }
@@ -154,13 +170,120 @@ __global__ __launch_bounds__(256) void sgd_checked_kernel(float4* __restrict__ p
     const float gscale = st->gmul;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         float4 pv = p[i], gv = g[i], mv = m[i];
-        gv.x = gv.x * gscale + wd * pv.x; gv.y = gv.y * gscale + wd * pv.y;
-        gv.z = gv.z * gscale + wd * pv.z; gv.w = gv.w * gscale + wd * pv.w;
-        mv.x = mu * mv.x + gv.x; mv.y = mu * mv.y + gv.y; mv.z = mu * mv.z + gv.z; mv.w = mu * mv.w + gv.w;
-        pv.x -= lr * mv.x; pv.y -= lr * mv.y; pv.z -= lr * mv.z; pv.w -= lr * mv.w;
+        sgd_grad(gv, pv, gscale, wd);
+        sgd_momentum(mv, gv, mu);
+        sgd_apply(pv, mv, lr);
         m[i] = mv;
         p[i] = pv;
     }
+}
+
+// ---- weight averaging inside the step --------------------------------------------------------------------------------------------
+// The averaging rule of include/mrfp_hip.h.  t = 1-based count of applied steps; an update happens after step t iff t >= start and
+// (t - start) % every == 0, its index is n = (t - start) / every.
+struct AvgRule {
+    double decay;
+    int kind;                              // kAvgEma | kAvgSwa
+    int warmup;
+    int start;
+    int every;
+};
+constexpr int kAvgEma = 0, kAvgSwa = 1;
+constexpr int kAvgNone = 0, kAvgCopy = 1, kAvgLerp = 2;       // what step t does to e
+
+// THE definition of the schedule and of the coefficient on the device (harness.average_coefficient is the one in Python): every
+// thread evaluates it once, before its loop, from by-value arguments -- the branch on the result is uniform.  c in double with IEEE
+// operations, rounded to float once.
+__device__ __forceinline__ int average_rule(const AvgRule& r, int t, float* c) {
+    *c = 0.f;
+    if (t < r.start || (t - r.start) % r.every != 0) return kAvgNone;
+    const int n = (t - r.start) / r.every;
+    if (n == 0) return kAvgCopy;
+    double cd;
+    if (r.kind == kAvgSwa) {
+        cd = 1.0 / ((double)n + 1.0);                       // the running arithmetic mean
+    } else {
+        double d = r.decay;
+        if (r.warmup) {
+            const double w = (1.0 + (double)n) / (10.0 + (double)n);
+            d = w < d ? w : d;
+        }
+        cd = 1.0 - d;
+    }
+    *c = (float)cd;
+    return kAvgLerp;
+}
+
+// e + c*(p - e) as three separately rounded fp32 operations: what torch's `e + c * (p - e)` computes, bit for bit.
+__device__ __forceinline__ float avg_lerp(float e, float p, float c) { return __fadd_rn(e, __fmul_rn(c, __fsub_rn(p, e))); }
+
+template <int MODE>
+__device__ __forceinline__ void sgd_avg_loop(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                             float4* __restrict__ e, int64_t n4, float lr, float mu, float wd, float gscale,
+                                             int first, float c) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        float4 pv = p[i], gv = g[i], mv, ev;
+        if (MODE == kAvgLerp) ev = e[i];
+        sgd_grad(gv, pv, gscale, wd);
+        if (first) {
+            mv = gv;
+        } else {
+            mv = m[i];
+            sgd_momentum(mv, gv, mu);
+        }
+        sgd_apply(pv, mv, lr);
+        m[i] = mv;
+        p[i] = pv;
+        if (MODE == kAvgLerp) {
+            ev.x = avg_lerp(ev.x, pv.x, c); ev.y = avg_lerp(ev.y, pv.y, c);
+            ev.z = avg_lerp(ev.z, pv.z, c); ev.w = avg_lerp(ev.w, pv.w, c);
+            e[i] = ev;
+        } else if (MODE == kAvgCopy) {
+            e[i] = pv;                                      // n == 0: a bit copy of the new parameters, e is not read
+        }
+    }
+}
+
+__device__ __forceinline__ void sgd_avg_body(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                             float4* __restrict__ e, int64_t n4, float lr, float mu, float wd, float gscale,
+                                             int first, const AvgRule& rule, int t) {
+    float c;
+    const int mode = average_rule(rule, t, &c);
+    if (mode == kAvgNone) sgd_avg_loop<kAvgNone>(p, g, m, e, n4, lr, mu, wd, gscale, first, c);       // e neither read nor written
+    else if (mode == kAvgCopy) sgd_avg_loop<kAvgCopy>(p, g, m, e, n4, lr, mu, wd, gscale, first, c);
+    else sgd_avg_loop<kAvgLerp>(p, g, m, e, n4, lr, mu, wd, gscale, first, c);
+}
+
+// sgd_kernel + the averaging rule on the fresh p, in the same trip: 28 bytes per element against 20 when step t updates with
+// n >= 1 (reads p, g, m, e; writes p, m, e), 24 when n == 0, 20 when it does not update.
+__global__ __launch_bounds__(256) void sgd_avg_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                                      float4* __restrict__ e, int64_t n4, float lr, float mu, float wd,
+                                                      float gscale, int first, AvgRule rule, int t) {
+    sgd_avg_body(p, g, m, e, n4, lr, mu, wd, gscale, first, rule, t);
+}
+
+// sgd_checked_kernel + the averaging rule with t = taken + taken_base read on the device (grad_check_finalize_kernel has counted
+// this step already).  found_inf: nothing is written, e included.
+__global__ __launch_bounds__(256) void sgd_checked_avg_kernel(float4* __restrict__ p, const float4* __restrict__ g,
+                                                              float4* __restrict__ m, float4* __restrict__ e, int64_t n4, float lr,
+                                                              float mu, float wd, const StepState* __restrict__ st, int taken_base,
+                                                              AvgRule rule) {
+    if (st->found_inf) return;
+    sgd_avg_body(p, g, m, e, n4, lr, mu, wd, st->gmul, 0, rule, st->taken + taken_base);
+}
+
+// Exchanges two disjoint fp32 ranges bit for bit (16-byte loads and stores move bits: NaN payloads survive).
+__global__ __launch_bounds__(256) void arena_swap_kernel(float4* __restrict__ a, float4* __restrict__ b, int64_t n4) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 av = a[i], bv = b[i];
+        a[i] = bv;
+        b[i] = av;
+    }
+}
+
+inline int64_t arena_blocks(int64_t n) {
+    const int64_t blocks = (n / 4 + 255) / 256;
+    return blocks > kArenaCap ? kArenaCap : blocks;
 }
 
 inline int64_t grad_check_blocks(int64_t n) {
@@ -223,6 +346,59 @@ extern "C" int mrfp_sgd_step_checked(float* p, const float* g, float* m, int64_t
     if (blocks > mrfp::kArenaCap) blocks = mrfp::kArenaCap;
     hipLaunchKernelGGL(mrfp::sgd_checked_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (float4*)p,
                        (const float4*)g, (float4*)m, n / 4, lr, momentum, weight_decay, (const mrfp::StepState*)state);
+    MRFP_LAUNCH_CHECK();
+    return 0;
+}
+
+// The averaging arguments of the two averaged entry points, refused before any launch with the entry point's name in front.
+static int avg_rule_check(const char* who, int kind, double decay, int warmup, int start, int every, mrfp::AvgRule* rule) {
+    MRFP_CHECK(kind == mrfp::kAvgEma || kind == mrfp::kAvgSwa, "%s: unknown kind %d (0 = ema, 1 = swa)", who, kind);
+    MRFP_CHECK(decay > 0.0 && decay < 1.0, "%s: decay must be in (0, 1) (got %g)", who, decay);
+    MRFP_CHECK(start >= 1, "%s: start must be >= 1 (got %d)", who, start);
+    MRFP_CHECK(every >= 1, "%s: every must be >= 1 (got %d)", who, every);
+    rule->decay = decay;
+    rule->kind = kind;
+    rule->warmup = warmup != 0;
+    rule->start = start;
+    rule->every = every;
+    return 0;
+}
+
+extern "C" int mrfp_sgd_step_avg(float* p, const float* g, float* m, float* e, int64_t n, float lr, float momentum,
+                                 float weight_decay, float gscale, int first, int kind, double decay, int warmup, int start,
+                                 int every, int t, void* stream) {
+    MRFP_CHECK(p && g && m && e && n > 0 && n % 4 == 0, "sgd_step_avg: bad arguments (n must be a multiple of 4)");
+    MRFP_CHECK(mrfp::aligned16(p) && mrfp::aligned16(g) && mrfp::aligned16(m) && mrfp::aligned16(e),
+               "sgd_step_avg: arenas must be 16-byte aligned");
+    mrfp::AvgRule rule;
+    if (avg_rule_check("sgd_step_avg", kind, decay, warmup, start, every, &rule) != 0) return -1;
+    hipLaunchKernelGGL(mrfp::sgd_avg_kernel, dim3((unsigned)mrfp::arena_blocks(n)), dim3(256), 0, (hipStream_t)stream, (float4*)p,
+                       (const float4*)g, (float4*)m, (float4*)e, n / 4, lr, momentum, weight_decay, gscale, first, rule, t);
+    MRFP_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mrfp_sgd_step_checked_avg(float* p, const float* g, float* m, float* e, int64_t n, float lr, float momentum,
+                                         float weight_decay, const void* state, int taken_base, int kind, double decay, int warmup,
+                                         int start, int every, void* stream) {
+    MRFP_CHECK(p && g && m && e && state && n > 0 && n % 4 == 0, "sgd_step_checked_avg: bad arguments (n must be a multiple of 4)");
+    MRFP_CHECK(mrfp::aligned16(p) && mrfp::aligned16(g) && mrfp::aligned16(m) && mrfp::aligned16(e) && mrfp::aligned16(state),
+               "sgd_step_checked_avg: arenas and state must be 16-byte aligned");
+    mrfp::AvgRule rule;
+    if (avg_rule_check("sgd_step_checked_avg", kind, decay, warmup, start, every, &rule) != 0) return -1;
+    hipLaunchKernelGGL(mrfp::sgd_checked_avg_kernel, dim3((unsigned)mrfp::arena_blocks(n)), dim3(256), 0, (hipStream_t)stream,
+                       (float4*)p, (const float4*)g, (float4*)m, (float4*)e, n / 4, lr, momentum, weight_decay,
+                       (const mrfp::StepState*)state, taken_base, rule);
+    MRFP_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mrfp_arena_swap(float* a, float* b, int64_t n, void* stream) {
+    MRFP_CHECK(a && b && n > 0 && n % 4 == 0, "arena_swap: bad arguments (n must be a positive multiple of 4)");
+    MRFP_CHECK(mrfp::aligned16(a) && mrfp::aligned16(b), "arena_swap: a and b must be 16-byte aligned");
+    MRFP_CHECK(a + n <= b || b + n <= a, "arena_swap: the ranges overlap");
+    hipLaunchKernelGGL(mrfp::arena_swap_kernel, dim3((unsigned)mrfp::arena_blocks(n)), dim3(256), 0, (hipStream_t)stream, (float4*)a,
+                       (float4*)b, n / 4);
     MRFP_LAUNCH_CHECK();
     return 0;
 }

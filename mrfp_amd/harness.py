@@ -122,6 +122,87 @@ def _check_loss_weights(loss_weights):
     return tuple(float(w) for w in loss_weights)
 
 
+# ------------------------------------------------------------------------------------------
+# weight averaging (EMA / SWA) inside the fused step: the rule of include/mrfp_hip.h, once more in Python
+# ------------------------------------------------------------------------------------------
+AVERAGE_KINDS = {"ema": 0, "swa": 1}          # the `kind` argument of mrfp_sgd_step_avg / mrfp_sgd_step_checked_avg
+
+
+def _f32(v: float) -> float:
+    return float(torch.tensor(v, dtype=torch.float64).to(torch.float32))
+
+
+def average_coefficient(kind, n, decay=0.999, warmup=True) -> float:
+    """The coefficient c of the averaging update with index n >= 1, e = e + c * (p - e): formed in double, rounded through float32
+    once -- the value average_rule() in csrc/sgd.hip hands its loop.  swa: 1 / (n + 1), the running arithmetic mean.  ema:
+    1 - min(decay, (1 + n) / (10 + n)) with warm-up, 1 - decay without."""
+    if kind not in AVERAGE_KINDS:
+        raise ValueError("kind must be 'ema' or 'swa', got %r" % (kind,))
+    n = int(n)
+    if n < 1:
+        raise ValueError("the update with index 0 is a copy and has no coefficient; n must be >= 1, got %r" % (n,))
+    if kind == "swa":
+        c = 1.0 / (float(n) + 1.0)
+    else:
+        d = float(decay)
+        if warmup:
+            d = min(d, (1.0 + float(n)) / (10.0 + float(n)))
+        c = 1.0 - d
+    return _f32(c)
+
+
+def average_index(t, start=1, every=1):
+    """The index n of the averaging update after applied step t (1-based), None when step t makes none: an update happens iff
+    t >= start and (t - start) % every == 0, and then n = (t - start) // every."""
+    if t < start or (t - start) % every != 0:
+        return None
+    return (t - start) // every
+
+
+def averages_made(t, start=1, every=1) -> int:
+    """How many averaging updates the applied steps 1 .. t have made."""
+    return 0 if t < start else (t - start) // every + 1
+
+
+class WeightAverage:
+    """A validated, plain description of an averaged copy of the weights, kept by the fused step:
+      kind    "ema": exponential moving average, e += (1 - d) * (p - e) with d = decay, or min(decay, (1 + n) / (10 + n)) while
+              `warmup` (the early average follows the run instead of its initial weights);  "swa": the equal-weight mean of the
+              parameters after the updating steps (SWA / SWAD), `decay` and `warmup` unused.
+      start   the first applied optimiser step (1-based) that enters the average: a bit copy of the parameters.
+      every   an update every that many applied steps from `start` on.
+    ValueError on what the C side refuses: an unknown kind, decay outside (0, 1), start < 1, every < 1."""
+
+    def __init__(self, kind="ema", decay=0.999, warmup=True, start=1, every=1):
+        if not isinstance(kind, str) or kind not in AVERAGE_KINDS:
+            raise ValueError("kind must be 'ema' or 'swa', got %r" % (kind,))
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not (0.0 < float(decay) < 1.0):
+            raise ValueError("decay must be a number in (0, 1), got %r" % (decay,))
+        for name, v in (("start", start), ("every", every)):
+            if isinstance(v, bool) or not isinstance(v, int) or not (1 <= v < 2 ** 31):
+                raise ValueError("%s must be an int >= 1, got %r" % (name, v))
+        self.kind, self.decay, self.warmup, self.start, self.every = kind, float(decay), bool(warmup), start, every
+
+    def config(self):
+        return {"kind": self.kind, "decay": self.decay, "warmup": self.warmup, "start": self.start, "every": self.every}
+
+    def c_args(self):
+        """(kind, decay, warmup, start, every) as the entry points take them."""
+        return AVERAGE_KINDS[self.kind], self.decay, int(self.warmup), self.start, self.every
+
+    def __repr__(self):
+        return "WeightAverage(kind=%r, decay=%r, warmup=%r, start=%r, every=%r)" % (
+            self.kind, self.decay, self.warmup, self.start, self.every)
+
+
+def _check_average(average):
+    if average is None or isinstance(average, WeightAverage):
+        return average
+    if isinstance(average, str):
+        return WeightAverage(kind=average)           # ValueError on an unknown name
+    raise ValueError("average must be None, 'ema', 'swa' or a WeightAverage, got %r" % (average,))
+
+
 class FlatArena:
     """Trainable parameters and their gradients as views into two flat fp32 buffers (every tensor starts
     16-byte aligned).  Device-agnostic host logic: the data-parallel buckets are ranges of `flat_g`.
@@ -177,11 +258,21 @@ class FlatArena:
 
 class FlatSGD(FlatArena):
     """torch.optim.SGD(lr, momentum=0.9, weight_decay=5e-4) + LambdaLR(poly 0.9) as ONE fused HIP kernel
-    over the flat arenas (reference main.py:826-839, 863-864)."""
+    over the flat arenas (reference main.py:826-839, 863-864).
+    average: None | WeightAverage | "ema" | "swa".  With one, `flat_e` -- a fourth arena, zeroed here, because in the checked path
+    the host does not know when the first update lands -- holds the averaged weights and every step goes through
+    mrfp_sgd_step_avg / mrfp_sgd_step_checked_avg; without one flat_e is None and the step is the plain one."""
 
-    def __init__(self, model: torch.nn.Module, lr=1e-2, momentum=0.9, weight_decay=5e-4, max_iter=40000, power=0.9):
+    def __init__(self, model: torch.nn.Module, lr=1e-2, momentum=0.9, weight_decay=5e-4, max_iter=40000, power=0.9,
+                 average=None):
+        average = _check_average(average)
         super().__init__(model)
         self.flat_m = torch.zeros_like(self.flat_p)
+        self.average = average
+        self.flat_e = torch.zeros_like(self.flat_p) if average is not None else None
+        # applied steps the scaler's `taken` word has not counted (unchecked steps, steps before a resume): the averaging rule's
+        # t is taken + taken_base, formed on the device in the checked path
+        self.taken_base = 0
         self.base_lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.max_iter, self.power = max_iter, power
         self.it = 0
@@ -241,6 +332,13 @@ class FlatSGD(FlatArena):
         self.missing_state = len(self.params) - n if n else 0
         self.has_momentum = n > 0
 
+    def applied_steps(self, scaler: Optional[LossScaler] = None) -> int:
+        """t of the averaging rule: optimiser steps applied so far.  Unchecked steps are counted here on the host; checked ones by
+        the `taken` word of the scaler (the one given, else that of the checked steps so far) on the device, so with a scaler
+        this is one device -> host copy."""
+        scaler = scaler if scaler is not None else self._scaler
+        return self.taken_base + (scaler.info()["taken"] if scaler is not None else 0)
+
     def step(self, gscale: float = 1.0, scaler: Optional[LossScaler] = None, max_grad_norm: Optional[float] = None):
         """One optimiser step + scheduler step.  Without `scaler`: mrfp_sgd_step with the host-side factor `gscale`.
         With a LossScaler: mrfp_grad_check (partial sums, finalize) and mrfp_sgd_step_checked on the current stream -- the device
@@ -256,8 +354,14 @@ class FlatSGD(FlatArena):
                 raise ValueError("max_grad_norm needs a LossScaler (LossScaler(init_scale=1.0, dynamic=False) for a plain run)")
             # (after a checked step the momentum arena obeys "zero where no momentum exists": mu*0 + g' is the first-step copy)
             first = not self.has_momentum and self._scaler is None
-            call("mrfp_sgd_step", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), self.n, float(self.lr),
-                 float(self.momentum), float(self.weight_decay), float(gscale), int(first), stream())
+            if self.average is None:
+                call("mrfp_sgd_step", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), self.n, float(self.lr),
+                     float(self.momentum), float(self.weight_decay), float(gscale), int(first), stream())
+            else:
+                self.taken_base += 1                 # an unchecked step is always applied
+                call("mrfp_sgd_step_avg", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_e), self.n,
+                     float(self.lr), float(self.momentum), float(self.weight_decay), float(gscale), int(first),
+                     *self.average.c_args(), self.applied_steps(), stream())
             self.has_momentum = True
         else:
             if scaler.state.device != self.flat_p.device:
@@ -269,8 +373,13 @@ class FlatSGD(FlatArena):
             call("mrfp_grad_check", ptr(self.flat_g), self.n, float(gscale), ptr(self._check_ws), ptr(scaler.state),
                  int(scaler.dynamic), scaler.growth_factor, scaler.backoff_factor, scaler.growth_interval,
                  math.inf if max_grad_norm is None else max_grad_norm, stream())
-            call("mrfp_sgd_step_checked", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), self.n, float(self.lr),
-                 float(self.momentum), float(self.weight_decay), ptr(scaler.state), stream())
+            if self.average is None:
+                call("mrfp_sgd_step_checked", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), self.n, float(self.lr),
+                     float(self.momentum), float(self.weight_decay), ptr(scaler.state), stream())
+            else:
+                call("mrfp_sgd_step_checked_avg", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_e), self.n,
+                     float(self.lr), float(self.momentum), float(self.weight_decay), ptr(scaler.state), self.taken_base,
+                     *self.average.c_args(), stream())
             self._scaler = scaler
         # the fused kernel wrote the arena behind autograd's version counters: invalidate the derived
         # weight packs explicitly (mrfp_amd/conv.py rebuilds them on next use)
@@ -448,7 +557,7 @@ class Trainer:
     optimiser step, the all-reduce and the LR step happen once per window of k calls, on the sum of the k gradients."""
 
     def __init__(self, model, lr=1e-2, momentum=0.9, weight_decay=5e-4, max_iter=40000, bucket_mb=32.0,
-                 loss_scale=None, max_grad_norm=None, accum_steps=1, loss_weights=None):
+                 loss_scale=None, max_grad_norm=None, accum_steps=1, loss_weights=None, average=None):
         """loss_scale: scale of the backward pass for float16 activations (the per-pixel CE gradient is 1/#pixels ~ 1e-7, below
         float16's normal range).
           None / a float, no max_grad_norm: a STATIC host-side scale, default 65536 when cfg.MODEL.ACT_DTYPE is float16, else 1.
@@ -474,9 +583,16 @@ class Trainer:
         not part of one.
         loss_weights: for a model that returns a list / tuple of losses (the network/deepv3.py factories: [main, aux(, wt)]) the
         pass backpropagates sum_i w_i * loss_i, formed on the device, and step() returns that scalar; None: all ones.  A length
-        that differs from the returned list, or weights for a model that returns one loss, is a ValueError."""
+        that differs from the returned list, or weights for a model that returns one loss, is a ValueError.
+        average: None | a WeightAverage | "ema" | "swa" (= WeightAverage(kind) with its defaults): an averaged copy of the trainable
+        parameters in a fourth arena `opt.flat_e`, updated INSIDE the fused step kernel after every applied optimiser step the
+        description selects -- one update per accumulation window, none for a step or window the scaler
+        skipped (that decision stays on the device), no extra launch, no collective (every rank steps from the same all-reduced
+        bits).  averaged() evaluates with it, average_info() counts, save_checkpoint / load_checkpoint carry it.  None, the
+        default: nothing is allocated and the step launches what it launched before."""
         from .config import cfg
         max_grad_norm = _check_max_grad_norm(max_grad_norm)
+        average = _check_average(average)
         self.accum_steps, self.micro = _check_accum_steps(accum_steps), 0
         self.loss_weights = _check_loss_weights(loss_weights)
         if isinstance(loss_scale, str):
@@ -488,7 +604,8 @@ class Trainer:
             if not (float(loss_scale) > 0.0) or math.isinf(float(loss_scale)):
                 raise ValueError("loss_scale must be positive and finite, got %r" % (loss_scale,))
         self.model = model
-        self.opt = FlatSGD(model, lr, momentum, weight_decay, max_iter)
+        self.opt = FlatSGD(model, lr, momentum, weight_decay, max_iter, average=average)
+        self._in_average = False
         self.sync = GradSync(self.opt, bucket_mb)
         # (MRFP_FORCE_SYNC=1: the replica synchronisation -- parameter / buffer broadcasts, the shared toggle seed, the per-rank
         #  torch seeds -- also runs at world size 1: the rehearsal of every collective of the multi-GPU path on one GPU over RCCL)
@@ -574,7 +691,51 @@ class Trainer:
             raise _lib.MrfpHipError("step_info: this Trainer has no LossScaler (loss_scale='dynamic' or a LossScaler)")
         return self.scaler.info()
 
+    # ---- the averaged weights ---------------------------------------------------------------------------------------
+    def average_info(self):
+        """{"t": applied optimiser steps (windows) so far, "n_averaged": averaging updates they made} + the WeightAverage's fields.
+        One device -> host copy, and only when a scaler exists (its `taken` word holds the count); none otherwise."""
+        avg = self.opt.average
+        if avg is None:
+            raise _lib.MrfpHipError("average_info: this Trainer keeps no average (average='ema', 'swa' or a WeightAverage)")
+        t = self.opt.applied_steps(self.scaler)
+        return {"t": t, "n_averaged": averages_made(t, avg.start, avg.every), **avg.config()}
+
+    def _swap_average(self):
+        from . import conv
+        call("mrfp_arena_swap", ptr(self.opt.flat_p), ptr(self.opt.flat_e), self.opt.n, stream())
+        conv.invalidate_packs()                        # the arena changed behind autograd's version counters, as in FlatSGD.step
+        conv.repack_all()
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """`with trainer.averaged():` -- the model runs on the averaged weights.  On entry ONE mrfp_arena_swap exchanges flat_p with
+        flat_e and the weight packs are rebuilt; on exit, also when the body raised, the same again, so the parameters come back
+        bit for bit.  No pointer changes: parameters stay views of flat_p and captured graphs stay valid.  Inside, evaluate,
+        evaluate_tta, validate, predict (with or without fold=True) and model.state_dict() see the averaged weights;
+        trainer.step raises.  Only the trainable parameters are averaged: buffers (the BatchNorm running statistics) and frozen
+        parameters (the HRFP branch) are the live model's -- after SWA, run update_bn() inside the block before evaluating.
+        Raises before any update has happened (the arena would be zeros) and on the CPU."""
+        if self.opt.average is None:
+            raise _lib.MrfpHipError("averaged: this Trainer keeps no average (average='ema', 'swa' or a WeightAverage)")
+        if self._in_average:
+            raise _lib.MrfpHipError("averaged: already inside averaged()")
+        if self.opt.flat_p.device.type != "cuda":
+            raise _lib.MrfpHipError("averaged needs the arenas on the GPU: the HIP path has no CPU fallback")
+        if self.average_info()["n_averaged"] == 0:
+            raise _lib.MrfpHipError("averaged: no averaging update has happened yet (applied steps %d, start %d)"
+                                    % (self.opt.applied_steps(self.scaler), self.opt.average.start))
+        self._swap_average()
+        self._in_average = True
+        try:
+            yield self
+        finally:
+            self._swap_average()
+            self._in_average = False
+
     def step(self, img, label):
+        if self._in_average:
+            raise _lib.MrfpHipError("Trainer.step inside averaged(): the parameter arena holds the averaged weights")
         if self.graph:
             return self._graph_step(img, label)
         loss = self._fwd_bwd(img, label)
@@ -738,6 +899,45 @@ def _eval_mode(model, fold):
     finally:
         for m, f in flags:
             m.training = f
+
+
+def update_bn(model, batches):
+    """What torch.optim.swa_utils.update_bn does, for this project's calling convention: the BatchNorm running statistics of
+    averaged weights belong to no set of weights that ever ran, so they are re-estimated before evaluation.  For every
+    HipBatchNorm2d (subclasses included) with running statistics: running_mean <- 0, running_var <- 1, num_batches_tracked and the
+    host-side pending count <- 0; then `model(img, label, training=True)` under torch.no_grad() for each (img, label) of `batches`
+    with the module's momentum set to 1 / (j + 1) for batch j (0-based) -- the cumulative mean of the batch statistics, as
+    momentum=None gives in torch.  `momentum` and the training flags of every module are put back on the way out, also when a
+    forward raises; num_batches_tracked ends at the number of batches.  The forwards are training forwards in every other respect:
+    perturbations and the HRFP re-initialisation are drawn from model.rng as in training, and dropout is live.  Typical use:
+    `with trainer.averaged(): update_bn(model, loader); evaluate(model, val)` -- note that the re-estimated buffers stay in the
+    model after the block (buffers are not averaged and not swapped).  -> the number of modules updated."""
+    from .network.mynn import HipBatchNorm2d
+    bns = [m for m in model.modules()
+           if isinstance(m, HipBatchNorm2d) and m.track_running_stats and m.running_mean is not None]
+    if not bns:
+        return 0
+    momenta = [m.momentum for m in bns]
+    flags = [(m, m.training) for m in model.modules()]
+    try:
+        with torch.no_grad():
+            for m in bns:
+                m.running_mean.zero_()
+                m.running_var.fill_(1.0)
+                if m.num_batches_tracked is not None:
+                    m.num_batches_tracked.zero_()
+                m._nbt_pending = 0
+            model.train()
+            for j, (img, label) in enumerate(batches):
+                for m in bns:
+                    m.momentum = 1.0 / (j + 1)
+                model(img, label, training=True)
+    finally:
+        for m, mom in zip(bns, momenta):
+            m.momentum = mom
+        for m, f in flags:
+            m.training = f
+    return len(bns)
 
 
 @torch.no_grad()
@@ -964,22 +1164,66 @@ def evaluate_tta(model, batches, num_classes=19, scales=(1.0,), flip=False, wind
 def save_checkpoint(path, model, epoch, optimizer=None):
     """{'epoch', 'state_dict', 'optimizer'} as reference main.py:867-869 writes it, with the `module.` prefix
     nn.DataParallel gives the keys.  `optimizer`: a FlatSGD / Trainer (its torch.optim.SGD-layout state_dict() is
-    stored), a torch optimizer, or an already-built state dict."""
-    sd = {"module." + k: v.detach().cpu() for k, v in model.state_dict().items()}
+    stored), a torch optimizer, or an already-built state dict.  A Trainer that keeps a weight average adds an 'average' entry of
+    plain numbers, strings and tensors: kind, decay, warmup, start, every, t (applied optimiser steps), n_averaged, and
+    `state_dict` -- the model's full state dict, `module.`-prefixed like the main one, with the trainable tensors cut from the
+    averaged arena (no swap; buffers and frozen parameters are the live model's), which loads straight into a model for
+    deployment.  With n_averaged == 0 those tensors are the zeros the arena was created with."""
+    msd = model.state_dict()
+    sd = {"module." + k: v.detach().cpu() for k, v in msd.items()}
     ck = {"epoch": epoch, "state_dict": sd}
     if optimizer is not None:
         opt = getattr(optimizer, "opt", optimizer)                  # Trainer -> its FlatSGD
         ck["optimizer"] = opt.state_dict() if hasattr(opt, "state_dict") else opt
         if getattr(optimizer, "scaler", None) is not None:          # a Trainer with a LossScaler: GradScaler's dict of plain numbers
             ck["scaler"] = optimizer.scaler.state_dict()
+        if getattr(opt, "average", None) is not None and isinstance(optimizer, Trainer):
+            ck["average"] = _average_entry(optimizer, model, msd)
     torch.save(ck, path)
+
+
+def _average_entry(trainer, model, msd):
+    opt = trainer.opt
+    if trainer._in_average:
+        raise _lib.MrfpHipError("save_checkpoint inside averaged(): the arenas are exchanged; save outside the block")
+    slot = {id(p): (o, p.numel()) for p, o in zip(opt.params, opt.offsets)}
+    cut = {name: slot[id(p)] for name, p in model.named_parameters(remove_duplicate=False) if id(p) in slot}
+    sd = {}
+    for k, v in msd.items():
+        if k in cut:
+            o, numel = cut[k]
+            v = opt.flat_e[o:o + numel].view(v.shape)
+        sd["module." + k] = v.detach().clone().cpu()
+    return {**trainer.average_info(), "state_dict": sd}
+
+
+def _load_average(trainer, entry):
+    """The averaged arena and the step count t of a checkpoint's 'average' entry into a Trainer that keeps an average (its own
+    description stays: kind / decay / start / every of the file are informative).  The scaler's `taken` word is not part of its
+    state dict, so taken_base takes up the difference: t = taken + taken_base holds again, on every rank alike."""
+    opt = trainer.opt
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in entry["state_dict"].items()}
+    slot = {id(p): (o, p.numel()) for p, o in zip(opt.params, opt.offsets)}
+    opt.flat_e.zero_()
+    for name, p in trainer.model.named_parameters():
+        if id(p) not in slot:
+            continue
+        if name not in sd:
+            raise _lib.MrfpHipError("checkpoint 'average' entry has no tensor for %s" % name)
+        o, numel = slot[id(p)]
+        if sd[name].numel() != numel:
+            raise _lib.MrfpHipError("checkpoint 'average' entry: %s has %d values, the parameter %d" % (name, sd[name].numel(), numel))
+        opt.flat_e[o:o + numel].copy_(sd[name].reshape(-1).to(opt.flat_e.device, torch.float32))
+    taken = trainer.scaler.info()["taken"] if trainer.scaler is not None else 0
+    opt.taken_base = int(entry["t"]) - taken
 
 
 def load_checkpoint(path_or_dict, model, strict=True, optimizer=None, trust_pickle=False):
     """Loads a reference checkpoint (keys with or without the `module.` prefix) into the HIP model and, when
     `optimizer` (FlatSGD / Trainer) is given and the checkpoint has an 'optimizer' entry, the momentum buffers and the
     schedule position (reference main.py:884-886 + the 'optimizer' entry of main.py:867); a 'scaler' entry is restored when
-    `optimizer` is a Trainer with a LossScaler, and files without one load as before.  The reference's format
+    `optimizer` is a Trainer with a LossScaler, and an 'average' entry (the averaged arena and its step count) when it is a
+    Trainer that keeps a weight average; files without them load as before.  The reference's format
     ({'epoch', 'state_dict', 'optimizer'} of tensors, numbers, lists and dicts) loads under torch's safe unpickler;
     `trust_pickle=True` opts into arbitrary pickles for files of known origin only."""
     ck = (torch.load(path_or_dict, map_location="cpu", weights_only=not trust_pickle)
@@ -994,4 +1238,7 @@ def load_checkpoint(path_or_dict, model, strict=True, optimizer=None, trust_pick
         getattr(optimizer, "opt", optimizer).load_state_dict(ck["optimizer"])
     if getattr(optimizer, "scaler", None) is not None and isinstance(ck, dict) and ck.get("scaler") is not None:
         optimizer.scaler.load_state_dict(ck["scaler"])
+    if (isinstance(optimizer, Trainer) and optimizer.opt.average is not None and isinstance(ck, dict)
+            and ck.get("average") is not None):
+        _load_average(optimizer, ck["average"])
     return ck.get("epoch", None) if isinstance(ck, dict) else None, missing
