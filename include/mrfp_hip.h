@@ -701,6 +701,20 @@ int mrfp_fourier_mix(const void* x, void* y, const int64_t* perm, void* S, void*
                      const void* twH, const void* twW, int dtype, int64_t B, int64_t H, int64_t W, int64_t C,
                      float radius, float lam, int high, void* stream);
 
+/* Host-only: which kernel family pass `pass` of mrfp_fourier_mix(dtype, H, W, C, radius, high) runs in THIS process (the
+ * launchers ask the same function, and it reads the MRFP_FFT_* A/B switches as they do), or < 0 where the call is refused.
+ * pass: 0 rows forward, 1 columns (+ mix), 2 rows inverse; on the generic path 2 is the inverse column (+ mix) pass and 3 the
+ * inverse row pass (the other routes have no pass 3: < 0).
+ * kb, tu, nh (each may be NULL; 0 where it does not apply): of the matrix-core row passes, the 16-deep k blocks
+ * ((2 Ws + 15) / 16), the pixel tiles of 16 per LDS segment (forward) or per item (inverse), and the 32-channel halves per item
+ * (inverse only). */
+#define MRFP_FOURIER_ROUTE_GENERIC 0  /* radix-2 / radix-3 Stockham passes, any length 2^a 3^b */
+#define MRFP_FOURIER_ROUTE_TWOSTEP 1  /* two-step register transform, one channel per transform */
+#define MRFP_FOURIER_ROUTE_PAIR 2     /* band-limited row pass on channel pairs */
+#define MRFP_FOURIER_ROUTE_DIRECT 3   /* band-limited inverse row pass as a direct trigonometric sum */
+#define MRFP_FOURIER_ROUTE_MFMA 4     /* band-limited row pass as a split-bf16 matrix product */
+int mrfp_fourier_route(int dtype, int64_t H, int64_t W, int64_t C, float radius, int high, int pass, int* kb, int* tu, int* nh);
+
 /* ---------------------------------------------------------------------------------------------
  * The training input pipeline (transform_tr), bit-exact with the PIL calls of the reference (main.py:409-419
  * transform_tr: dataloaders.py:139-150 flip, 398-435 RandomSizeAndCrop = img.resize(BICUBIC) / mask.resize(NEAREST),

@@ -746,21 +746,30 @@ static int launch_inv_mfma_tu(const FftP& p, hipStream_t st) {
     MRFP_LAUNCH_CHECK();
     return 0;
 }
-template <int KB>
-static int launch_inv_mfma(const FftP& p, hipStream_t st) {
-    const int ntile = p.W >> 4;          // pixel tiles per line; an item takes TU of them, TU | ntile (no predicated tile: every
-    if (p.C % 64 == 0) {                 // load and store of an item is straight-line code)
-        if (ntile % 6 == 0) return launch_inv_mfma_tu<KB, 6, 2>(p, st);
-        if (ntile % 4 == 0) return launch_inv_mfma_tu<KB, 4, 2>(p, st);
-        if (ntile % 3 == 0) return launch_inv_mfma_tu<KB, 3, 2>(p, st);
-        if (ntile % 2 == 0) return launch_inv_mfma_tu<KB, 2, 2>(p, st);
-        return launch_inv_mfma_tu<KB, 1, 2>(p, st);
+// pixel tiles per item of the inverse pass: TU | W / 16 (no predicated tile: every load and store of an item is straight-line code).
+// Every planned line length has W / 16 in {2, 3, 4, 6, 8, 12, 16, 24, 32}, so one of these divides it (0: none, the pass is not taken)
+static int inv_tu(int W) {
+    const int ntile = W >> 4;
+    for (int tu : {6, 4, 3, 2})
+        if (ntile % tu == 0) return tu;
+    return 0;
+}
+template <int KB, int NH>
+static int launch_inv_mfma_nh(const FftP& p, int tu, hipStream_t st) {
+    switch (tu) {
+        case 6: return launch_inv_mfma_tu<KB, 6, NH>(p, st);
+        case 4: return launch_inv_mfma_tu<KB, 4, NH>(p, st);
+        case 3: return launch_inv_mfma_tu<KB, 3, NH>(p, st);
+        case 2:          // (two tiles are W = 32: at most 16 stored bins on the band-limited path, never a third k block)
+            if constexpr (KB < 3) return launch_inv_mfma_tu<KB, 2, NH>(p, st);
+            break;
     }
-    if (ntile % 6 == 0) return launch_inv_mfma_tu<KB, 6, 1>(p, st);
-    if (ntile % 4 == 0) return launch_inv_mfma_tu<KB, 4, 1>(p, st);
-    if (ntile % 3 == 0) return launch_inv_mfma_tu<KB, 3, 1>(p, st);
-    if (ntile % 2 == 0) return launch_inv_mfma_tu<KB, 2, 1>(p, st);
-    return launch_inv_mfma_tu<KB, 1, 1>(p, st);
+    set_error("fourier_mix: no matrix-core inverse row pass with %d pixel tiles per item", tu);
+    return -1;
+}
+template <int KB>
+static int launch_inv_mfma(const FftP& p, int tu, int nh, hipStream_t st) {
+    return nh == 2 ? launch_inv_mfma_nh<KB, 2>(p, tu, st) : launch_inv_mfma_nh<KB, 1>(p, tu, st);
 }
 
 // ---- band-limited forward row pass on the matrix cores (bf16 activations) --------------------------------------------
@@ -877,11 +886,10 @@ static int fwd_lds_tu(int kb, int W, int tu) { return 2 * kb * (W >> 4) * 512 + 
 // the largest segment that divides the line and fits the 160 KB of a CU next to the table (0: none)
 static int fwd_tu(int kb, int W) {
     const int ntile = W >> 4;
-    for (int tu : {12, 8, 6, 4, 3, 2, 1})
+    for (int tu : {12, 8, 6, 4, 3, 2})         // (W / 16 of a planned length is never odd and prime to 3: no one-tile segments)
         if (ntile % tu == 0 && fwd_lds_tu(kb, W, tu) <= 160 * 1024) return tu;
     return 0;
 }
-static int fwd_lds(int kb, int W) { return fwd_lds_tu(kb, W, fwd_tu(kb, W)); }
 
 template <int KB, int TU>
 static int launch_fwd_mfma_tu(const FftP& p, hipStream_t st) {
@@ -889,7 +897,7 @@ static int launch_fwd_mfma_tu(const FftP& p, hipStream_t st) {
     const int items = p.B * p.H * (p.C >> 5);
     int grid = (items + NW - 1) / NW;
     if (grid > 256) grid = 256;                                              // one workgroup per CU (LDS), persistent over its items
-    const int lds = fwd_lds(KB, p.W);
+    const int lds = fwd_lds_tu(KB, p.W, TU);
     auto kern = &dft_rows_fwd_mfma_kernel<KB, TU>;
     if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kFwdThreads), lds, st, p, items);
@@ -897,16 +905,19 @@ static int launch_fwd_mfma_tu(const FftP& p, hipStream_t st) {
     return 0;
 }
 template <int KB>
-static int launch_fwd_mfma(const FftP& p, hipStream_t st) {
-    switch (fwd_tu(KB, p.W)) {
+static int launch_fwd_mfma(const FftP& p, int tu, hipStream_t st) {
+    switch (tu) {
         case 12: return launch_fwd_mfma_tu<KB, 12>(p, st);
         case 8: return launch_fwd_mfma_tu<KB, 8>(p, st);
         case 6: return launch_fwd_mfma_tu<KB, 6>(p, st);
         case 4: return launch_fwd_mfma_tu<KB, 4>(p, st);
         case 3: return launch_fwd_mfma_tu<KB, 3>(p, st);
-        case 2: return launch_fwd_mfma_tu<KB, 2>(p, st);
+        case 2:          // (two tiles are W = 32: at most 16 stored bins on the band-limited path, never a third k block)
+            if constexpr (KB < 3) return launch_fwd_mfma_tu<KB, 2>(p, st);
+            break;
     }
-    return launch_fwd_mfma_tu<KB, 1>(p, st);
+    set_error("fourier_mix: no matrix-core forward row pass with %d pixel tiles per segment", tu);
+    return -1;
 }
 
 template <int N1, int N2>
@@ -1008,24 +1019,70 @@ static int launch_two(K kern, const FftP& p, int nlines, int nt, int lds, hipStr
     return 0;
 }
 
+static bool has_fast_plan(int n) {
+    return n == 32 || n == 48 || n == 64 || n == 96 || n == 128 || n == 192 || n == 256 || n == 384 || n == 512;
+}
+
+static int fft_generic() {
+    static const int generic = env_switch("MRFP_FFT_GENERIC", 0);
+    return generic;
+}
+static int fft_full() {          // MRFP_FFT_FULL=1: full half spectrum even for a low band (A/B against the band-limited path)
+    static const int full = env_switch("MRFP_FFT_FULL", 0);
+    return full;
+}
+// bins along W that S / S3 / ratio hold.  Low band on the register path: the ratio differs from 1 only for
+// kw <= radius, so only those columns of the spectrum are ever formed (y = x + irfft2(F*(ratio-1))).
+static int stored_bins(int64_t H, int64_t W, float radius, int high) {
+    const int Wh = (int)(W / 2 + 1);
+    if (high || fft_generic() || fft_full() || !has_fast_plan((int)H) || !has_fast_plan((int)W) || !(radius >= 0.f)) return Wh;
+    const float fl = floorf(radius);
+    return fl + 1.f < (float)Wh ? (int)fl + 1 : Wh;
+}
+
+// ---- the route of a pass: ONE host function, asked by the launchers below and by mrfp_fourier_route ------------------------------
+// Which kernel family a pass of mrfp_fourier_mix runs (the MRFP_FOURIER_ROUTE_* values of include/mrfp_hip.h), with the instance
+// parameters of the matrix-core passes.  Pure host arithmetic on (dtype, H, W, C, stored bins) and the A/B switches of the process.
+struct Route {
+    int kind;            // MRFP_FOURIER_ROUTE_*
+    int kb, tu, nh;      // matrix-core passes: 16-deep k blocks, pixel tiles per segment / item, 32-channel halves per item (else 0)
+};
+// pass: 0 rows forward, 1 columns (+ mix), 2 rows inverse on the register path / columns inverse (+ mix) on the generic path, 3 rows
+// inverse of the generic path
+static Route pass_route(int dtype, int H, int W, int C, int Ws, int pass) {
+    Route r = {MRFP_FOURIER_ROUTE_GENERIC, 0, 0, 0};
+    if (fft_generic() || !has_fast_plan(H) || !has_fast_plan(W)) return r;      // the four Stockham passes
+    r.kind = MRFP_FOURIER_ROUTE_TWOSTEP;
+    const bool delta = Ws < W / 2 + 1;                                           // band-limited: only the row passes have other kernels
+    if (!delta || pass == 1) return r;
+    if (dtype == MRFP_BF16 && C % 32 == 0 && W % 16 == 0 && 2 * Ws <= 48 && fft_mfma()) {
+        const int kb = (2 * Ws + 15) / 16;
+        if (pass == 0 && fwd_tu(kb, W) > 0) return Route{MRFP_FOURIER_ROUTE_MFMA, kb, fwd_tu(kb, W), 0};
+        if (pass == 2 && !fft_nodirect() && inv_tu(W) > 0) return Route{MRFP_FOURIER_ROUTE_MFMA, kb, inv_tu(W), C % 64 == 0 ? 2 : 1};
+    }
+    if (pass == 2 && C % kDirCh == 0 && Ws <= 64 && !fft_nopair() && !fft_nodirect()) r.kind = MRFP_FOURIER_ROUTE_DIRECT;
+    else if (C % (2 * kCB) == 0 && !fft_nopair()) r.kind = MRFP_FOURIER_ROUTE_PAIR;
+    return r;
+}
+template <typename T> constexpr int dtype_of() {
+    return std::is_same<T, bf16>::value ? MRFP_BF16 : std::is_same<T, f16>::value ? MRFP_F16 : MRFP_F32;
+}
+
 // pass: 0 rows forward, 1 columns + mix, 2 rows inverse
 template <typename T, int N1, int N2>
 static int launch_fast_pass(FftP p, int pass, const float2* tw, hipStream_t st) {
     using TS = TwoStep<N1, N2>;
     p.N = TS::N;
     p.tw = tw;
+    const Route rt = pass_route(dtype_of<T>(), p.H, p.W, p.C, p.Ws, pass);
     if constexpr (std::is_same<T, bf16>::value) {
-        if (p.delta && pass == 0 && p.C % 32 == 0 && p.W % 16 == 0 && 2 * p.Ws <= 48 && fft_mfma() &&
-            fwd_tu((2 * p.Ws + 15) / 16, p.W) > 0) {
-            const int kb = (2 * p.Ws + 15) / 16;                // band-limited forward row pass on the matrix cores
-            return kb == 1 ? launch_fwd_mfma<1>(p, st) : kb == 2 ? launch_fwd_mfma<2>(p, st) : launch_fwd_mfma<3>(p, st);
-        }
-        if (p.delta && pass == 2 && p.C % 32 == 0 && p.W % 16 == 0 && 2 * p.Ws <= 48 && fft_mfma() && !fft_nodirect()) {
-            const int kb = (2 * p.Ws + 15) / 16;                // band-limited inverse row pass on the matrix cores
-            return kb == 1 ? launch_inv_mfma<1>(p, st) : kb == 2 ? launch_inv_mfma<2>(p, st) : launch_inv_mfma<3>(p, st);
-        }
+        if (rt.kind == MRFP_FOURIER_ROUTE_MFMA && pass == 0)    // band-limited forward row pass on the matrix cores
+            return rt.kb == 1 ? launch_fwd_mfma<1>(p, rt.tu, st) : rt.kb == 2 ? launch_fwd_mfma<2>(p, rt.tu, st) : launch_fwd_mfma<3>(p, rt.tu, st);
+        if (rt.kind == MRFP_FOURIER_ROUTE_MFMA)                 // band-limited inverse row pass on the matrix cores
+            return rt.kb == 1 ? launch_inv_mfma<1>(p, rt.tu, rt.nh, st) : rt.kb == 2 ? launch_inv_mfma<2>(p, rt.tu, rt.nh, st)
+                                                                                     : launch_inv_mfma<3>(p, rt.tu, rt.nh, st);
     }
-    if (p.delta && pass == 2 && p.C % kDirCh == 0 && p.Ws <= 64 && !fft_nopair() && !fft_nodirect()) {
+    if (rt.kind == MRFP_FOURIER_ROUTE_DIRECT) {
         // band-limited inverse row pass as a direct trigonometric sum
         constexpr int PPT = 8 / (int)sizeof(T);            // 16-byte activation accesses
         p.N = dir_lines();
@@ -1040,7 +1097,7 @@ static int launch_fast_pass(FftP p, int pass, const float2* tw, hipStream_t st) 
         MRFP_LAUNCH_CHECK();
         return 0;
     }
-    if (p.delta && p.C % (2 * kCB) == 0 && pass != 1 && !fft_nopair()) {     // band-limited row passes on channel pairs
+    if (rt.kind == MRFP_FOURIER_ROUTE_PAIR) {                                 // band-limited row passes on channel pairs
         const FftP& q = p;
         const unsigned grid = (unsigned)(((p.B * p.H + 7) / 8) * 8 * (p.C / (2 * kCB)));
         if (pass == 0) {
@@ -1079,30 +1136,9 @@ static int fast_pass(const FftP& p, int n, int pass, const float2* tw, hipStream
     set_error("fourier_mix: no two-step plan for length %d", n);
     return -1;
 }
-static bool has_fast_plan(int n) {
-    return n == 32 || n == 48 || n == 64 || n == 96 || n == 128 || n == 192 || n == 256 || n == 384 || n == 512;
-}
-
-static int fft_generic() {
-    static const int generic = env_switch("MRFP_FFT_GENERIC", 0);
-    return generic;
-}
-static int fft_full() {          // MRFP_FFT_FULL=1: full half spectrum even for a low band (A/B against the band-limited path)
-    static const int full = env_switch("MRFP_FFT_FULL", 0);
-    return full;
-}
-// bins along W that S / S3 / ratio hold.  Low band on the register path: the ratio differs from 1 only for
-// kw <= radius, so only those columns of the spectrum are ever formed (y = x + irfft2(F*(ratio-1))).
-static int stored_bins(int64_t H, int64_t W, float radius, int high) {
-    const int Wh = (int)(W / 2 + 1);
-    if (high || fft_generic() || fft_full() || !has_fast_plan((int)H) || !has_fast_plan((int)W) || !(radius >= 0.f)) return Wh;
-    const float fl = floorf(radius);
-    return fl + 1.f < (float)Wh ? (int)fl + 1 : Wh;
-}
-
 template <typename T>
 static int run_mix(FftP p, const float2* twH, const float2* twW, hipStream_t st) {
-    if (!fft_generic() && has_fast_plan(p.H) && has_fast_plan(p.W)) {
+    if (pass_route(dtype_of<T>(), p.H, p.W, p.C, p.Ws, 0).kind != MRFP_FOURIER_ROUTE_GENERIC) {
         int rc;
         if ((rc = fast_pass<T>(p, p.W, 0, twW, st))) return rc;
         if ((rc = fast_pass<T>(p, p.H, 1, twH, st))) return rc;
@@ -1126,6 +1162,25 @@ int64_t mrfp_fourier_spectrum_bytes(int64_t B, int64_t H, int64_t W, int64_t C) 
 int64_t mrfp_fourier_stored_bins(int64_t H, int64_t W, float radius, int high) {
     if (H < 2 || W < 2) return 0;
     return stored_bins(H, W, radius, high);
+}
+
+int mrfp_fourier_route(int dtype, int64_t H, int64_t W, int64_t C, float radius, int high, int pass, int* kb, int* tu, int* nh) {
+    if (kb) *kb = 0;
+    if (tu) *tu = 0;
+    if (nh) *nh = 0;
+    // what mrfp_fourier_mix refuses has no route
+    if (!dtype_known(dtype) || H < 2 || W < 2 || H > 512 || W > 512 || W % 2 != 0 || C <= 0 || C % kCB != 0 || pass < 0 || pass > 3) return -1;
+    const Route r = pass_route(dtype, (int)H, (int)W, (int)C, stored_bins(H, W, radius, high), pass);
+    if (r.kind == MRFP_FOURIER_ROUTE_GENERIC) {
+        int radix[kMaxStages], ns;
+        if (!factor((int)W, radix, ns) || !factor((int)H, radix, ns)) return -1;    // a launch of the call refuses the length
+    } else if (pass == 3) {
+        return -1;                                                                  // the register path has three passes
+    }
+    if (kb) *kb = r.kb;
+    if (tu) *tu = r.tu;
+    if (nh) *nh = r.nh;
+    return r.kind;
 }
 
 int mrfp_fourier_mix(const void* x, void* y, const int64_t* perm, void* S, void* S3, float* ratio, int load_ratio,

@@ -110,6 +110,13 @@ def test_fourier_and_whitening_host_queries(cdll):
     assert sb(192, 192, 500.0, 0) == 97 and sb(32, 48, 30.0, 0) == 25
     assert sb(8, 8, 2.0, 0) == 5 and sb(12, 18, 3.0, 0) == 10   # no register plan for these lengths: generic path
     assert cdll.mrfp_fourier_spectrum_bytes(2, 8, 8, 16) == 2 * 8 * 5 * 16 * 8
+    # mrfp_fourier_route: the kernel family of a pass (0 generic, 1 two-step, 2 pair, 3 direct, 4 matrix cores; < 0: refused), as the
+    # launchers choose it; tests/test_fourier_model_cpu.py walks the whole table
+    rt = lambda dtype, H, W, C, r, high, p: cdll.mrfp_fourier_route(dtype, H, W, C, r, high, p, None, None, None)
+    assert [rt(0, 192, 192, 128, 16.0, 0, p) for p in range(4)] == [2, 1, 3, -1]
+    assert [rt(1, 192, 192, 128, 16.0, 0, p) for p in range(4)] == [4, 1, 4, -1]
+    assert [rt(1, 192, 192, 128, 16.0, 1, p) for p in range(3)] == [1, 1, 1] and [rt(2, 12, 18, 16, 3.0, 0, p) for p in range(4)] == [0] * 4
+    assert rt(0, 10, 14, 16, 2.0, 0, 0) < 0 and rt(99, 192, 192, 128, 16.0, 0, 0) < 0 and rt(0, 192, 192, 8, 16.0, 0, 0) < 0
     ws = cdll.mrfp_group_moments_ws_bytes
     assert ws(16, 192 * 192, 256) > 0 and ws(16, 192 * 192, 256) % (64 * 68 * 4) == 0
     assert ws(2, 100, 24) == 0 and ws(2, 100, 2048) == 0    # C % 16 != 0, C > 1024: unsupported

@@ -9,6 +9,43 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
+GENERIC, TWOSTEP, PAIR, DIRECT, MFMA = range(5)          # MRFP_FOURIER_ROUTE_* (include/mrfp_hip.h)
+
+
+def routes(dtype, shape, radius, high):
+    """((family, kb, tu, nh) of passes 0, 1, 2 as mrfp_fourier_route reports them, stored bins along W)."""
+    import ctypes
+    from mrfp_amd import _lib
+    B, C, H, W = shape
+    out = []
+    for p in range(3):
+        kb, tu, nh = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        k = _lib.lib().mrfp_fourier_route(_lib._DT[dtype], H, W, C, float(radius), int(high), p, ctypes.byref(kb), ctypes.byref(tu), ctypes.byref(nh))
+        out.append((k, kb.value, tu.value, nh.value))
+    return out, int(_lib.lib().mrfp_fourier_stored_bins(H, W, float(radius), int(high)))
+
+
+# what the comments of the case list below say about the kernels a case reaches, as assertions: {(shape, radius): check(dtype, routes, stored bins)}
+_two_step = lambda dt, r, ws: all(k[0] != GENERIC for k in r) and r[1][0] == TWOSTEP
+_direct = lambda dt, r, ws: r[2][0] == (MFMA if dt == torch.bfloat16 else DIRECT) and r[0][0] == (MFMA if dt == torch.bfloat16 else PAIR)
+CLAIMS = {
+    # two-step register path: every planned line length
+    ((2, 16, 192, 192), 16.0): _two_step, ((2, 32, 128, 256), 20.0): _two_step, ((1, 16, 384, 512), 16.0): _two_step,
+    ((2, 16, 32, 48), 5.0): _two_step, ((3, 16, 256, 64), 16.0): _two_step,
+    # band-limited low-band path: floor(radius) + 1 stored columns; a radius past the last column: the whole half spectrum
+    ((2, 16, 64, 64), 0.0): lambda dt, r, ws: ws == 1 and _two_step(dt, r, ws),
+    ((3, 32, 64, 128), 3.5): lambda dt, r, ws: ws == 4 and r[0][0] == (MFMA if dt == torch.bfloat16 else PAIR),
+    ((2, 16, 32, 48), 30.0): lambda dt, r, ws: ws == 25 and all(k[0] == TWOSTEP for k in r),
+    ((2, 48, 128, 96), 24.0): lambda dt, r, ws: ws == 25 and all(k[0] == TWOSTEP for k in r),
+    # 64-channel tiles: the inverse row pass as a direct trigonometric sum (bf16: both row passes on the matrix cores instead)
+    ((2, 64, 96, 192), 16.0): _direct, ((2, 128, 64, 128), 5.5): _direct, ((1, 64, 32, 48), 3.0): _direct, ((2, 64, 48, 32), 0.0): _direct,
+    # bf16 on the matrix cores: two k blocks, 32-channel items, a line longer than one LDS segment (W / 16 = 24 tiles in segments of 8)
+    ((2, 64, 64, 96), 10.0): lambda dt, r, ws: dt != torch.bfloat16 or (r[0][:2] == (MFMA, 2) and r[2][:2] == (MFMA, 2)),
+    ((2, 96, 96, 96), 12.0): lambda dt, r, ws: dt != torch.bfloat16 or (r[0][0] == MFMA and r[2] == (MFMA, 2, 6, 1)),
+    ((1, 32, 48, 384), 16.0): lambda dt, r, ws: dt != torch.bfloat16 or (r[0] == (MFMA, 3, 8, 0) and r[2][0] == MFMA),
+}
+
+
 def relerr(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return ((a - b).abs().max() / b.abs().max().clamp_min(1e-20)).item()
@@ -36,6 +73,9 @@ def relerr(a, b):
 def test_fourier_amplitude_mix(dtype, shape, radius, lam, high):
     from mrfp_amd import ops
     B, C, H, W = shape
+    if (shape, radius) in CLAIMS:
+        r, ws = routes(dtype, shape, radius, high)
+        assert CLAIMS[shape, radius](dtype, r, ws), (r, ws)
     g = torch.Generator().manual_seed(H * W + C)
     x = torch.randn(*shape, generator=g) + 0.3
     if dtype == torch.bfloat16:
@@ -61,6 +101,8 @@ def test_bf16_matrix_core_row_passes_stay_within_two_output_ulps(shape, radius):
     prints both; the loose norm-relative bound of the parametrised test above would not see a lost low-order part)."""
     from mrfp_amd import ops
     B, C, H, W = shape
+    r, _ = routes(torch.bfloat16, shape, radius, False)
+    assert r[0][0] == MFMA and r[2][0] == MFMA, r
     g = torch.Generator().manual_seed(7 * H + W)
     x = (torch.randn(*shape, generator=g) * 3 + 1).to(DEV, torch.bfloat16).contiguous(memory_format=torch.channels_last)
     perm = torch.roll(torch.arange(B), 1)
@@ -89,6 +131,7 @@ def test_identity_when_partner_is_self():
 def test_unsupported_length_fails_loudly():
     from mrfp_amd import _lib, ops
     x = torch.randn(1, 16, 10, 14).to(DEV).contiguous(memory_format=torch.channels_last)   # 14 = 2*7
+    assert _lib.lib().mrfp_fourier_route(0, 10, 14, 16, 2.0, 0, 0, None, None, None) < 0
     with pytest.raises(_lib.MrfpHipError):
         ops.fourier_amplitude_mix(x, torch.arange(1), 2.0)
 
