@@ -16,13 +16,12 @@ from typing import Any, NamedTuple, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import call, dt, ptr, stream
 from .ops import CL, GRAD_DEFERRED, _chk, channel_sums, empty_cl, grad_sink, notify_grad, wgrad_workspace, zeros_cl
 from .ops import _inside_autograd_engine as _in_backward
 from .skipgrad import ALIAS, GATE, LOWRANK, AliasCell, alias_cell, gateable, mask_possible, ungate, unlowrank
 
-_PACKS = {}      # id(weight Parameter) -> {key: _Pack}; entry dropped when the Parameter dies
 FUSE_STATS = [_os.environ.get("MRFP_FUSE_STATS", "1") != "0"]   # conv epilogues emit BatchNorm partial statistics for bias-free convolutions
 
 
@@ -40,11 +39,6 @@ class ConvStats(NamedTuple):
 
 WSTATS = [_os.environ.get("MRFP_WSTATS", "1") != "0"]
 WSTATS_HITS = [0]
-_EPOCH = [0]     # bumped by writers that bypass autograd's version counters (the fused SGD kernel)
-
-
-def invalidate_packs():
-    _EPOCH[0] += 1
 
 
 def _epc(dtype) -> int:
@@ -56,52 +50,213 @@ def _round_up(n, m):
     return (n + m - 1) // m * m
 
 
+def _pad_to_chunk(x):
+    """x with its channel count padded to a 16-byte chunk, by copy (e.g. a raw 3-channel image)"""
+    C, Cp = x.shape[1], _round_up(x.shape[1], _epc(x.dtype))
+    if Cp == C:
+        return x
+    xp = zeros_cl(x.shape[0], Cp, x.shape[2], x.shape[3], x.dtype, x.device)
+    xp[:, :C] = x
+    return xp
+
+
+# ---- weight packs ---------------------------------------------------------------------------------------------------------------
+# A pack is fresh while its version stamp equals the one that _plain_version / _fold_version build now.
+_PACKS = {}      # id(weight Parameter) -> _WeightPacks; entry dropped when the Parameter dies
+_EPOCH = [0]     # bumped by writers that bypass autograd's version counters (the fused SGD kernel)
+_BATCH = {}      # (tag, dtype) -> the cached job table of a batched re-pack (_batched_repack)
+_REPACK_LISTS = {}       # tag -> the (weights, biases) of the last repack_weights() call
+_new_key = tuple.__new__         # (a named key built at the cost of a bare tuple: get_pack's hit path runs ~250 times per step)
+_PlainKey = collections.namedtuple("_PlainKey", "dtype Cphys Nphys weight bias")          # weight, bias: data pointers (no bias: 0)
+_FoldKey = collections.namedtuple("_FoldKey", "dtype Cphys Nphys depthwise tensors")     # tensors: the pointers of _fold_tensors (or 0)
+# the packs of one weight: plain {_PlainKey: _Pack} (get_pack: forward + dgrad) and folded {_FoldKey: _Pack} (get_folded_pack), apart
+_WeightPacks = collections.namedtuple("_WeightPacks", "plain folded")
+_NO_PACKS = _WeightPacks({}, {})         # of a weight without a cache entry: read, never written
+_PACK_JOB = ([("w", "<u8"), ("wf", "<u8"), ("wd", "<u8"), ("dims", "<i4", (6,))], 48)           # PackJob of csrc/conv_pack.hip
+_FOLD_JOB = ([("ptrs", "<u8", (8,)), ("eps", "<f4"), ("dims", "<i4", (7,))], 96)                # FoldJob
+
+
 class _Pack:
-    __slots__ = ("version", "wf", "wd", "bias", "key", "wref")
+    __slots__ = ("key", "wref", "version", "wf", "wd", "bias")
+
+    def __init__(self, key, weight):
+        self.key, self.wref = key, weakref.ref(weight)
+        self.version = self.wf = self.wd = self.bias = None          # (the buffers: get_pack / _fold_slot, right away)
+
+
+def _packs_of(weight, create=False):
+    """The packs of this weight: made on first use (create), dropped when the Parameter dies."""
+    rec = _PACKS.get(id(weight), _NO_PACKS)
+    if rec is _NO_PACKS and create:
+        rec = _PACKS[id(weight)] = _WeightPacks({}, {})
+        weakref.finalize(weight, _PACKS.pop, id(weight), None)
+    return rec
+
+
+def invalidate_packs():
+    _EPOCH[0] += 1
+
+
+def _plain_version(weight, bias):
+    return (weight._version, bias._version if bias is not None else 0, _EPOCH[0])
+
+
+def _capturing(device) -> bool:
+    """Under hipGraph capture (harness.Trainer.enable_graph) a pack kernel is only recorded, not run: a pack written under capture
+    must stay "stale" for eager code, and the recorded kernel re-packs on every replay.  So who packs stamps only when this is false."""
+    return device.type == "cuda" and torch.cuda.is_current_stream_capturing()
 
 
 def get_pack(weight: torch.Tensor, bias: Optional[torch.Tensor], dtype, Cphys: int, Nphys: int) -> _Pack:
-    N, C, R, S = weight.shape
-    key = (dtype, Cphys, Nphys, weight.data_ptr(), bias.data_ptr() if bias is not None else 0)
-    ver = (weight._version, bias._version if bias is not None else 0, _EPOCH[0])
-    per_w = _PACKS.get(id(weight))
-    if per_w is None:
-        per_w = {}
-        _PACKS[id(weight)] = per_w
-        weakref.finalize(weight, _PACKS.pop, id(weight), None)
-    pk = per_w.get(key)
+    key = _new_key(_PlainKey, (dtype, Cphys, Nphys, weight.data_ptr(), bias.data_ptr() if bias is not None else 0))
+    ver = _plain_version(weight, bias)
+    packs = _packs_of(weight, True).plain
+    pk = packs.get(key)
     if pk is not None and pk.version == ver:
         return pk
+    N, C, R, S = weight.shape
     dev = weight.device
     w32 = weight.detach()
     if w32.dtype != torch.float32 or not w32.is_contiguous():
         w32 = w32.float().contiguous()
     if pk is None:
-        pk = _Pack()
+        pk = _Pack(key, weight)
         pk.wf = torch.empty(Nphys * R * S * Cphys, dtype=dtype, device=dev)
         # dgrad pack [Cphys][R][S][Nphys]: the rows of pad input channels (c >= C) stay zero, so a dgrad launch over a
         # channel-padded input writes exact zeros into the pad channels of dx
         pk.wd = (torch.zeros(Cphys * R * S * Nphys, dtype=dtype, device=dev) if Cphys != C
                  else torch.empty(C * R * S * Nphys, dtype=dtype, device=dev))
-        pk.bias = None
-        pk.version = None
-        pk.wref = weakref.ref(weight)
     call("mrfp_pack_weight", ptr(w32), ptr(pk.wf), ptr(pk.wd), _lib._DT[dtype], N, C, R, S, Nphys, Cphys, stream())
     if bias is not None:
         if pk.bias is None:                      # allocated once (pad entries stay zero), refreshed in place
             pk.bias = torch.zeros(Nphys, dtype=torch.float32, device=dev)
         pk.bias[:N].copy_(bias.detach())
-    # under hipGraph capture (harness.Trainer.enable_graph) the pack kernel is only recorded, not run: the cached pack
-    # must stay "stale" for eager code, and the recorded kernel re-packs on every replay
-    if not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+    if not _capturing(dev):
         pk.version = ver
-    per_w[key] = pk
+    packs[key] = pk
     return pk
+
+
+def _job_table(rows, record):
+    """rows = [(the fields of one job record, its work items)], record = (numpy fields, bytes per record) -> the records as a host
+    byte tensor, the int64 prefix table of the work items as a host tensor, and their total: the operands of a batched launch."""
+    import numpy as np
+    rec = np.zeros(len(rows), dtype=np.dtype(record[0]))
+    assert rec.itemsize == record[1]
+    prefix = np.zeros(len(rows) + 1, dtype=np.int64)
+    for i, (fields, work) in enumerate(rows):
+        rec[i] = fields
+        prefix[i + 1] = prefix[i] + work
+    return torch.from_numpy(rec.view(np.uint8).copy()), torch.from_numpy(prefix), int(prefix[-1])
+
+
+def _packable(pk, w, with_bias=False):
+    return ((with_bias or pk.bias is None) and w.dtype == torch.float32 and w.is_contiguous()
+            and w.shape[2] * w.shape[3] <= 9)        # the brick kernel holds up to 3x3 taps; the 7x7 stem packs lazily
+
+
+def _batched_repack(todo, tag, biases=None, launch=True):
+    """ONE mrfp_pack_weights_batched launch per dtype for the (plain pack, weight) pairs in `todo`; the job table is cached
+    per (tag, dtype) and rebuilt only when the set of packs changes."""
+    by_dtype = {}
+    for pk, w in todo:
+        by_dtype.setdefault(pk.key.dtype, []).append((pk, w))
+    for dtype, items in by_dtype.items():
+        sig = tuple((id(pk), w.data_ptr(), pk.wf.data_ptr(), pk.wd.data_ptr()) for pk, w in items)
+        dev = items[0][1].device
+        st = _BATCH.get((tag, dtype))
+        if st is None or st["sig"] != sig:
+            rows = []
+            for pk, w in items:
+                N, C, R, S = w.shape
+                Nphys, Cphys = pk.key.Nphys, pk.key.Cphys
+                bc = 64 if R * S == 1 else 8                                           # input channels per brick (conv.hip)
+                rows.append(((w.data_ptr(), pk.wf.data_ptr(), pk.wd.data_ptr(), (N, C, R, S, Nphys, Cphys)),
+                             ((Nphys + 63) // 64) * ((Cphys + bc - 1) // bc)))
+            # (pinned staging + asynchronous copies: legal while a hipGraph is being captured too -- the first capture pass of
+            #  Trainer.enable_graph() is the first time the HRFP packs exist when the re-initialisation runs; the host copies stay
+            #  alive in the table entry for the graph's memcpy nodes)
+            hj, hp, total = _job_table(rows, _PACK_JOB)
+            if dev.type == "cuda":
+                hj, hp = hj.pin_memory(), hp.pin_memory()
+            st = _BATCH[(tag, dtype)] = {"sig": sig, "host": (hj, hp), "jobs": hj.to(dev, non_blocking=True),
+                                         "prefix": hp.to(dev, non_blocking=True), "total": total, "n": len(items)}
+        if not launch:
+            continue
+        call("mrfp_pack_weights_batched", ptr(st["jobs"]), ptr(st["prefix"]), st["n"], st["total"], _lib._DT[dtype], stream())
+        capturing = _capturing(dev)
+        for pk, w in items:
+            b = biases.get(id(w)) if biases else None
+            if b is not None and pk.bias is not None:           # packs with a bias (the HRFP convolutions): refresh the fp32 copy
+                pk.bias[:w.shape[0]].copy_(b.detach())
+            if not capturing:
+                pk.version = _plain_version(w, b)
+
+
+def repack_all():
+    """Re-packs, in ONE launch, every cached bias-free pack whose fp32 master changed (called by the harness right after
+    the fused SGD kernel rewrote the parameter arena; 124 launches of ~7 us per step otherwise).  Packs with a bias
+    (final2) keep the lazy per-layer path; the frozen HRFP weights, re-drawn at the start of a forward, go through
+    repack_weights(); folded inference packs are rebuilt lazily (get_folded_pack)."""
+    todo = []
+    for rec in _PACKS.values():
+        for pk in rec.plain.values():
+            w = pk.wref()
+            if w is not None and w.requires_grad and _packable(pk, w):
+                todo.append((pk, w))
+    _batched_repack(todo, "trainable")
+
+
+def _repack_selection(weights, biases):
+    """-> the plain packs of `weights` that a batched launch refreshes, as (pack, weight) pairs, and id(weight) -> its bias"""
+    todo = []
+    bmap = {id(w): b for w, b in zip(weights, biases)} if biases is not None else {}
+    for w in weights:
+        b = bmap.get(id(w))
+        for pk in _packs_of(w).plain.values():
+            if _packable(pk, w, with_bias=b is not None) and (pk.bias is None) == (b is None) \
+                    and pk.key.bias == (b.data_ptr() if b is not None else 0):
+                todo.append((pk, w))
+    return todo, bmap
+
+
+def repack_weights(weights, tag="list", biases=None):
+    """The same for an explicit list of weights that were just rewritten (the HRFP branch's convolutions after their
+    re-initialisation: reference deepv3.py:290-299 re-draws them at the start of a forward; 28 pack launches per step
+    otherwise).  `biases`: the bias Parameter of each weight (or None) -- a pack with a bias gets its fp32 copy refreshed here too.
+    Weights without a cached pack yet are left to the lazy path."""
+    _REPACK_LISTS[tag] = ([weakref.ref(w) for w in weights], [weakref.ref(b) if b is not None else None for b in biases]
+                          if biases is not None else None)
+    todo, bmap = _repack_selection(weights, biases)
+    # the masters were just rewritten -- possibly through a flat arena they are views of (deepv3._hrfp_arena), which does not bump
+    # the parameters' own version counters: every cached pack of these weights that the batched launch does NOT refresh (another
+    # padding, a 7x7 filter, a bias mismatch, a folded pack) is marked stale here and rebuilt lazily at its next use (ADVICE r4)
+    sel = {id(pk) for pk, _ in todo}
+    for w in weights:
+        for pk in (*_packs_of(w).plain.values(), *_packs_of(w).folded.values()):
+            if id(pk) not in sel:
+                pk.version = None
+    _batched_repack(todo, tag, bmap)
+
+
+def prebuild_repack_tables():
+    """Builds (without launching) the job tables of every repack_weights() list seen so far, for the packs that exist NOW: called
+    by harness.Trainer between the eager warm-up pass of a hipGraph capture and the capture itself -- in the very first step the
+    packs of the HRFP convolutions come into being AFTER the re-initialisation ran, so the capture pass would be the first to
+    need the table, and a host -> device copy cannot be captured."""
+    for tag, (wrefs, brefs) in list(_REPACK_LISTS.items()):
+        weights = [r() for r in wrefs]
+        if any(w is None for w in weights):          # the model is gone
+            del _REPACK_LISTS[tag]
+            continue
+        biases = [r() if r is not None else None for r in brefs] if brefs is not None else None
+        todo, bmap = _repack_selection(weights, biases)
+        _batched_repack(todo, tag, bmap, launch=False)
 
 
 # ---- folded inference packs (mrfp_amd/inference.py) -----------------------------------------------------------------
 # conv -> eval-mode BatchNorm as ONE convolution: forward pack round(w * A[n]) from the fp32 master, fp32 bias S (mrfp_pack_weight_folded).
-# The packs live in the per-weight cache above under keys that start with "fold".  They are stale when the weight, the convolution's
+# The packs live in the folded dictionary of their weight's cache entry.  They are stale when the weight, the convolution's
 # bias or any of the four BatchNorm tensors changed: their autograd version counters (optimizer.step of torch, load_state_dict,
 # any in-place torch operator), _EPOCH (invalidate_packs(): the fused SGD kernel, checkpoint loads, broadcasts) and
 # ops.RUNNING_STATS_EPOCH -- bumped by every training-mode BatchNorm forward, whose kernel updates the running statistics through raw
@@ -115,79 +270,59 @@ def _fold_tensors(weight, conv_bias, norm):
 
 
 def _fold_key(weight, conv_bias, norm, dtype, Cphys, Nphys, depthwise):
-    return ("fold", dtype, Cphys, Nphys, bool(depthwise)) + tuple(t.data_ptr() if t is not None else 0
-                                                                  for t in _fold_tensors(weight, conv_bias, norm))
+    return _FoldKey(dtype, Cphys, Nphys, bool(depthwise), tuple(t.data_ptr() if t is not None else 0 for t in _fold_tensors(weight, conv_bias, norm)))
 
 
 def _fold_version(weight, conv_bias, norm):
-    from . import ops
     return tuple(t._version if t is not None else 0 for t in _fold_tensors(weight, conv_bias, norm)) + \
         (float(norm.eps), _EPOCH[0], ops.RUNNING_STATS_EPOCH[0])
 
 
-def _fold_f32(t, what):
-    if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-        raise _lib.MrfpHipError("folded inference: %s must be a contiguous fp32 tensor (got %s)" % (what, t.dtype))
-    return t
-
-
 def _fold_slot(weight, key):
-    per_w = _PACKS.get(id(weight))
-    if per_w is None:
-        per_w = {}
-        _PACKS[id(weight)] = per_w
-        weakref.finalize(weight, _PACKS.pop, id(weight), None)
-    pk = per_w.get(key)
+    packs = _packs_of(weight, True).folded
+    pk = packs.get(key)
     if pk is None:
-        dtype, Cphys, Nphys, depthwise = key[1:5]
         N, _, R, S = weight.shape
-        pk = _Pack()
-        pk.wf = torch.empty(Nphys * R * S * Cphys, dtype=torch.float32 if depthwise else dtype, device=weight.device)
-        pk.wd = None
-        pk.bias = torch.empty(Nphys, dtype=torch.float32, device=weight.device)
-        pk.version = None
-        pk.wref = weakref.ref(weight)
-        pk.key = key
-        per_w[key] = pk
+        pk = packs[key] = _Pack(key, weight)
+        pk.wf = torch.empty(key.Nphys * R * S * key.Cphys, dtype=torch.float32 if key.depthwise else key.dtype, device=weight.device)
+        pk.bias = torch.empty(key.Nphys, dtype=torch.float32, device=weight.device)
     return pk
 
 
-def _fold_job(weight, conv_bias, norm, key, pk):
-    """(pointers, eps, dims) of one fold job -- the FoldJob record of csrc/conv_pack.hip"""
-    dtype, Cphys, Nphys, depthwise = key[1:5]
+# One fold job: eight pointers in the order of the FoldJob record of csrc/conv_pack.hip (None: no such tensor), eps, and the dims
+# (N, C, R, S, Nphys, Cphys, depthwise), of which the first six are the single entry point's
+_FoldJob = collections.namedtuple("_FoldJob", "weight wf conv_bias gamma beta mean var shift eps dims")
+
+
+def _fold_job(weight, conv_bias, norm, pk) -> _FoldJob:
     N, C, R, S = weight.shape
     for t, what in zip(_fold_tensors(weight, conv_bias, norm), ("weight", "conv bias", "norm weight", "norm bias", "running_mean", "running_var")):
-        _fold_f32(t, what)
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.MrfpHipError("folded inference: %s must be a contiguous fp32 tensor (got %s)" % (what, t.dtype))
     if norm.running_mean is None or norm.running_var is None:
         raise _lib.MrfpHipError("folded inference: the BatchNorm has no running statistics")
-    ptrs = (weight.data_ptr(), pk.wf.data_ptr(), ptr(conv_bias) or 0, ptr(norm.weight) or 0, ptr(norm.bias) or 0,
-            norm.running_mean.data_ptr(), norm.running_var.data_ptr(), pk.bias.data_ptr())
-    dims = (N, 1, R, S, Nphys, 1, 1) if depthwise else (N, C, R, S, Nphys, Cphys, 0)
-    return ptrs, float(norm.eps), dims
+    dims = (N, 1, R, S, pk.key.Nphys, 1, 1) if pk.key.depthwise else (N, C, R, S, pk.key.Nphys, pk.key.Cphys, 0)
+    return _FoldJob(ptr(weight), ptr(pk.wf), ptr(conv_bias), ptr(norm.weight), ptr(norm.bias), ptr(norm.running_mean),
+                    ptr(norm.running_var), ptr(pk.bias), float(norm.eps), dims)
 
 
 def fold_packs_batched(items):
     """ONE mrfp_pack_weights_folded_batched launch per pack dtype for `items` = [(weight, conv_bias, norm, key)]."""
-    import numpy as np
     by_dtype = {}
     for it in items:
-        by_dtype.setdefault(it[3][1], []).append(it)
-    rec_t = np.dtype([("ptrs", "<u8", (8,)), ("eps", "<f4"), ("dims", "<i4", (7,))])
-    assert rec_t.itemsize == 96
+        by_dtype.setdefault(it[3].dtype, []).append(it)
     for dtype, its in by_dtype.items():
-        rec = np.zeros(len(its), dtype=rec_t)
-        prefix = np.zeros(len(its) + 1, dtype=np.int64)
-        pks = []
-        for i, (w, cb, norm, key) in enumerate(its):
+        rows, pks = [], []
+        for w, cb, norm, key in its:
             pk = _fold_slot(w, key)
-            ptrs, eps, dims = _fold_job(w, cb, norm, key, pk)
-            rec[i]["ptrs"], rec[i]["eps"], rec[i]["dims"] = ptrs, eps, dims
-            prefix[i + 1] = prefix[i] + dims[4] * dims[2] * dims[3] * dims[5] + dims[4]
+            job = _fold_job(w, cb, norm, pk)
+            N, C, R, S, Nphys, Cphys, _ = job.dims
+            rows.append(((tuple(p or 0 for p in job[:8]), job.eps, job.dims), Nphys * R * S * Cphys + Nphys))
             pks.append(pk)
+        hj, hp, total = _job_table(rows, _FOLD_JOB)
         dev = its[0][0].device
-        jobs = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
-        pre = torch.from_numpy(prefix).to(dev)
-        call("mrfp_pack_weights_folded_batched", ptr(jobs), ptr(pre), len(its), int(prefix[-1]), _lib._DT[dtype], stream())
+        jobs, pre = hj.to(dev), hp.to(dev)
+        call("mrfp_pack_weights_folded_batched", ptr(jobs), ptr(pre), len(its), total, _lib._DT[dtype], stream())
         FOLD_PACK_LAUNCHES[0] += 1
         for (w, cb, norm, key), pk in zip(its, pks):
             pk.version = _fold_version(w, cb, norm)
@@ -215,17 +350,14 @@ def _refold_set(weight, dtype):
                 continue
             depthwise = c.groups != 1
             N, C = w.shape[0], w.shape[1]
-            keys = [k for k in _PACKS.get(id(w), {}) if k[0] == "fold"]
+            packs = _packs_of(w).folded
             std = _fold_key(w, cb, n, dtype, 1 if depthwise else _round_up(C, epc), N if depthwise else _round_up(N, epc), depthwise)
-            if std not in keys:
-                keys.append(std)
             ver = _fold_version(w, cb, n)
-            for k in keys:
-                pk = _PACKS.get(id(w), {}).get(k)
-                if k[5:] == std[5:] and (pk is None or pk.version != ver):
+            for k in list(packs) if std in packs else [*packs, std]:
+                pk = packs.get(k)
+                if k.tensors == std.tensors and (pk is None or pk.version != ver):
                     items.append((w, cb, n, k))
-        if items:
-            fold_packs_batched(items)
+        fold_packs_batched(items)
         return True
     return False
 
@@ -233,22 +365,19 @@ def _refold_set(weight, dtype):
 def get_folded_pack(weight, conv_bias, norm, dtype, Cphys, Nphys, depthwise=False) -> _Pack:
     key = _fold_key(weight, conv_bias, norm, dtype, Cphys, Nphys, depthwise)
     ver = _fold_version(weight, conv_bias, norm)
-    pk = _PACKS.get(id(weight), {}).get(key)
+    pk = _packs_of(weight).folded.get(key)
     if pk is not None and pk.version == ver:
         return pk
-    capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
+    capturing = _capturing(weight.device)
     if not capturing and _refold_set(weight, dtype):
-        pk = _PACKS.get(id(weight), {}).get(key)
+        pk = _packs_of(weight).folded.get(key)
         if pk is not None and pk.version == ver:
             return pk
     pk = _fold_slot(weight, key)
-    ptrs, eps, dims = _fold_job(weight, conv_bias, norm, key, pk)
-    if depthwise:         # (the single entry writes the pack in `dtype`: a depthwise fp32 [C][9] pack is an fp32 job)
-        call("mrfp_pack_weight_folded", ptrs[0], ptrs[1], ptrs[2] or None, ptrs[3] or None, ptrs[4] or None, ptrs[5], ptrs[6], eps,
-             ptrs[7], _lib.F32, dims[0], 1, dims[2], dims[3], dims[4], 1, stream())
-    else:
-        call("mrfp_pack_weight_folded", ptrs[0], ptrs[1], ptrs[2] or None, ptrs[3] or None, ptrs[4] or None, ptrs[5], ptrs[6], eps,
-             ptrs[7], _lib._DT[dtype], *dims[:6], stream())
+    job = _fold_job(weight, conv_bias, norm, pk)
+    # (the single entry writes the pack in the dtype it is given: a depthwise fp32 [C][9] pack is an fp32 job)
+    call("mrfp_pack_weight_folded", job.weight, job.wf, job.conv_bias, job.gamma, job.beta, job.mean, job.var, job.eps, job.shift,
+         _lib.F32 if depthwise else _lib._DT[dtype], *job.dims[:6], stream())
     FOLD_PACK_LAUNCHES[0] += 1
     if not capturing:
         pk.version = ver
@@ -258,27 +387,21 @@ def get_folded_pack(weight, conv_bias, norm, dtype, Cphys, Nphys, depthwise=Fals
 def conv2d_folded(x, conv, norm, act=0, res=None):
     """act(BN_eval(conv(x)) (+ res)) as ONE mrfp_conv_fwd_act launch (no normalisation launch).  No autograd: the caller
     (network.mynn.conv_norm) only comes here with gradients disabled.  act: 0 none, 1 ReLU, 2 ReLU6."""
-    from .ops import _chk as chk
     if torch.is_grad_enabled():
         raise _lib.MrfpHipError("conv2d_folded: the folded form has no backward (call it under torch.no_grad())")
     weight, bias = conv.weight, conv.bias
-    x = chk(x)
+    x = _pad_to_chunk(_chk(x))
     st = conv.stride[0]
     ph, pw = conv.padding
     dl = conv.dilation[0]
     N, C, R, S = weight.shape
-    epc = _epc(x.dtype)
-    if x.shape[1] % epc != 0:
-        xp = zeros_cl(x.shape[0], _round_up(x.shape[1], epc), x.shape[2], x.shape[3], x.dtype, x.device)
-        xp[:, :x.shape[1]] = x
-        x = xp
     if x.shape[1] < C:
         raise _lib.MrfpHipError("conv2d_folded: input has %d channels, weight expects %d" % (x.shape[1], C))
     B, Cphys, H, W = x.shape
-    Nphys = _round_up(N, epc)
+    Nphys = _round_up(N, _epc(x.dtype))
     Ho, Wo = _out_size(H, R, st, ph, dl), _out_size(W, S, st, pw, dl)
     if res is not None:
-        res = chk(res, "res")
+        res = _chk(res, "res")
         if tuple(res.shape) != (B, Nphys, Ho, Wo) or res.dtype != x.dtype:
             raise _lib.MrfpHipError("conv2d_folded: the residual %s / %s does not match the output (%d, %d, %d, %d) / %s"
                                     % (tuple(res.shape), res.dtype, B, Nphys, Ho, Wo, x.dtype))
@@ -294,7 +417,6 @@ def conv2d_folded(x, conv, norm, act=0, res=None):
 
 def depthwise_conv2d_folded(x, conv, norm, act=0):
     """The depthwise 3x3 form of conv2d_folded (mrfp_dwconv_fwd_act over the scaled fp32 taps)."""
-    from .ops import _chk as chk
     if torch.is_grad_enabled():
         raise _lib.MrfpHipError("depthwise_conv2d_folded: the folded form has no backward")
     weight = conv.weight
@@ -303,14 +425,12 @@ def depthwise_conv2d_folded(x, conv, norm, act=0):
     if tuple(weight.shape[1:]) != (1, 3, 3) or st[0] != st[1] or st[0] not in (1, 2) or dl[0] != dl[1] or tuple(pd) != tuple(dl):
         raise _lib.MrfpHipError("depthwise_conv2d_folded: weight %s stride %s padding %s dilation %s is not a depthwise 3x3 with "
                                 "padding = dilation and stride 1 or 2" % (tuple(weight.shape), st, pd, dl))
-    x = chk(x)
+    x = _chk(x)
     Cp = _round_up(C, _epc(x.dtype))
+    if x.shape[1] == C:
+        x = _pad_to_chunk(x)
     if x.shape[1] != Cp:
-        if x.shape[1] != C:
-            raise _lib.MrfpHipError("depthwise_conv2d_folded: input has %d channels, weight expects %d" % (x.shape[1], C))
-        xp = zeros_cl(x.shape[0], Cp, x.shape[2], x.shape[3], x.dtype, x.device)
-        xp[:, :C] = x
-        x = xp
+        raise _lib.MrfpHipError("depthwise_conv2d_folded: input has %d channels, weight expects %d" % (x.shape[1], C))
     B, _, H, W = x.shape
     Ho, Wo = (H - 1) // st[0] + 1, (W - 1) // st[0] + 1
     pk = get_folded_pack(weight, conv.bias, norm, x.dtype, 1, C, depthwise=True)
@@ -319,127 +439,6 @@ def depthwise_conv2d_folded(x, conv, norm, act=0):
     if Cp != C:
         y = y[:, :C].contiguous(memory_format=CL)
     return y
-
-
-_BATCH = {}
-
-
-def _packable(pk, w, with_bias=False):
-    return (w is not None and (with_bias or pk.bias is None) and w.dtype == torch.float32 and w.is_contiguous()
-            and w.shape[2] * w.shape[3] <= 9)        # the brick kernel holds up to 3x3 taps; the 7x7 stem packs lazily
-
-
-def _batched_repack(todo, tag, biases=None, launch=True):
-    """ONE mrfp_pack_weights_batched launch per dtype for the (key, pack, weight) triples in `todo`; the job table is cached
-    per (tag, dtype) and rebuilt only when the set of packs changes."""
-    import numpy as np
-    by_dtype = {}
-    for key, pk, w in todo:
-        by_dtype.setdefault(key[0], []).append((key, pk, w))
-    for dtype, items in by_dtype.items():
-        sig = tuple((id(pk), w.data_ptr(), pk.wf.data_ptr(), pk.wd.data_ptr()) for _, pk, w in items)
-        st = _BATCH.get((tag, dtype))
-        if st is None or st["sig"] != sig:
-            rec = np.zeros(len(items), dtype=np.dtype([("w", "<u8"), ("wf", "<u8"), ("wd", "<u8"), ("dims", "<i4", (6,))]))
-            prefix = np.zeros(len(items) + 1, dtype=np.int64)
-            for i, (key, pk, w) in enumerate(items):
-                N, C, R, S = w.shape
-                _, Cphys, Nphys = key[0], key[1], key[2]
-                rec[i]["w"], rec[i]["wf"], rec[i]["wd"] = w.data_ptr(), pk.wf.data_ptr(), pk.wd.data_ptr()
-                rec[i]["dims"] = (N, C, R, S, Nphys, Cphys)
-                bc = 64 if R * S == 1 else 8                                           # input channels per brick (conv.hip)
-                prefix[i + 1] = prefix[i] + ((Nphys + 63) // 64) * ((Cphys + bc - 1) // bc)
-            dev = items[0][2].device
-            # (pinned staging + asynchronous copies: legal while a hipGraph is being captured too -- the first capture pass of
-            #  Trainer.enable_graph() is the first time the HRFP packs exist when the re-initialisation runs; the host copies stay
-            #  alive in the table entry for the graph's memcpy nodes)
-            hj, hp = torch.from_numpy(rec.view(np.uint8).copy()), torch.from_numpy(prefix)
-            if dev.type == "cuda":
-                hj, hp = hj.pin_memory(), hp.pin_memory()
-            st = {"sig": sig, "host": (hj, hp), "jobs": hj.to(dev, non_blocking=True),
-                  "prefix": hp.to(dev, non_blocking=True), "total": int(prefix[-1]), "n": len(items)}
-            _BATCH[(tag, dtype)] = st
-        if not launch:
-            continue
-        call("mrfp_pack_weights_batched", ptr(st["jobs"]), ptr(st["prefix"]), st["n"], st["total"], _lib._DT[dtype], stream())
-        capturing = torch.cuda.is_current_stream_capturing()
-        for key, pk, w in items:
-            b = biases.get(id(w)) if biases else None
-            if b is not None and pk.bias is not None:           # packs with a bias (the HRFP convolutions): refresh the fp32 copy
-                pk.bias[:w.shape[0]].copy_(b.detach())
-            if not capturing:
-                pk.version = (w._version, b._version if b is not None else 0, _EPOCH[0])
-
-
-def repack_all():
-    """Re-packs, in ONE launch, every cached bias-free pack whose fp32 master changed (called by the harness right after
-    the fused SGD kernel rewrote the parameter arena; 124 launches of ~7 us per step otherwise).  Packs with a bias
-    (final2) keep the lazy per-layer path; the frozen HRFP weights, re-drawn at the start of a forward, go through
-    repack_weights()."""
-    todo = []
-    for per_w in _PACKS.values():
-        for key, pk in per_w.items():
-            if key[0] == "fold":                 # folded inference packs: rebuilt lazily (get_folded_pack)
-                continue
-            w = pk.wref() if getattr(pk, "wref", None) is not None else None
-            if w is None or not w.requires_grad or not _packable(pk, w):
-                continue
-            todo.append((key, pk, w))
-    if todo:
-        _batched_repack(todo, "trainable")
-
-
-def repack_weights(weights, tag="list", biases=None):
-    """The same for an explicit list of weights that were just rewritten (the HRFP branch's convolutions after their
-    re-initialisation: reference deepv3.py:290-299 re-draws them at the start of a forward; 28 pack launches per step
-    otherwise).  `biases`: the bias Parameter of each weight (or None) -- a pack with a bias gets its fp32 copy refreshed here too.
-    Weights without a cached pack yet are left to the lazy path."""
-    _REPACK_LISTS[tag] = ([weakref.ref(w) for w in weights], [weakref.ref(b) if b is not None else None for b in biases]
-                          if biases is not None else None)
-    todo, bmap = _repack_selection(weights, biases)
-    # the masters were just rewritten -- possibly through a flat arena they are views of (deepv3._hrfp_arena), which does not bump
-    # the parameters' own version counters: every cached pack of these weights that the batched launch does NOT refresh (another
-    # dtype / padding, a 7x7 filter, a bias mismatch) is marked stale here and rebuilt lazily at its next use (ADVICE r4)
-    sel = {id(pk) for _, pk, _ in todo}
-    for w in weights:
-        for pk in _PACKS.get(id(w), {}).values():
-            if id(pk) not in sel:
-                pk.version = None
-    if todo:
-        _batched_repack(todo, tag, bmap)
-
-
-_REPACK_LISTS = {}       # tag -> the (weights, biases) of the last repack_weights() call
-
-
-def prebuild_repack_tables():
-    """Builds (without launching) the job tables of every repack_weights() list seen so far, for the packs that exist NOW: called
-    by harness.Trainer between the eager warm-up pass of a hipGraph capture and the capture itself -- in the very first step the
-    packs of the HRFP convolutions come into being AFTER the re-initialisation ran, so the capture pass would be the first to
-    need the table, and a host -> device copy cannot be captured."""
-    for tag, (wrefs, brefs) in list(_REPACK_LISTS.items()):
-        weights = [r() for r in wrefs]
-        if any(w is None for w in weights):          # the model is gone
-            del _REPACK_LISTS[tag]
-            continue
-        biases = [r() if r is not None else None for r in brefs] if brefs is not None else None
-        todo, bmap = _repack_selection(weights, biases)
-        if todo:
-            _batched_repack(todo, tag, bmap, launch=False)
-
-
-def _repack_selection(weights, biases):
-    todo = []
-    bmap = {id(w): b for w, b in zip(weights, biases)} if biases is not None else {}
-    for w in weights:
-        for key, pk in _PACKS.get(id(w), {}).items():
-            if key[0] == "fold":
-                continue
-            has_b = bmap.get(id(w)) is not None
-            if pk.wf is not None and _packable(pk, w, with_bias=has_b) and (pk.bias is None) == (not has_b) \
-                    and key[4] == (bmap[id(w)].data_ptr() if has_b else 0):
-                todo.append((key, pk, w))
-    return todo, bmap
 
 
 def _out_size(H, R, stride, pad, dil):
@@ -883,10 +882,7 @@ def conv2d(x, weight, bias, stride, padding, dilation, phys_out: Optional[int] =
     dl = dilation[0] if isinstance(dilation, (tuple, list)) else int(dilation)
     N, C = weight.shape[0], weight.shape[1]
     epc = _epc(x.dtype)
-    if x.shape[1] % epc != 0:                        # e.g. a raw 3-channel image: pad (copy) to a chunk
-        xp = zeros_cl(x.shape[0], _round_up(x.shape[1], epc), x.shape[2], x.shape[3], x.dtype, x.device)
-        xp[:, :x.shape[1]] = x
-        x = xp
+    x = _pad_to_chunk(x)
     if x.shape[1] < C:
         raise _lib.MrfpHipError("conv2d: input has %d channels, weight expects %d" % (x.shape[1], C))
     if groups != 1 or (C == 1 and x.shape[1] > epc):

@@ -731,10 +731,10 @@ def test_batched_weight_pack_equals_the_per_layer_pack(dtype):
             pk.wd.fill_(7.0)                                      # (pad input-channel rows of wd are zero by allocation and never written)
         else:
             pk.wd.view(Cphys, -1)[:C].fill_(7.0)
-        todo.append(((dtype, Cphys, Nphys, w.data_ptr(), 0), pk, w))
+        todo.append((pk, w))
     conv._batched_repack(todo, "test_pack_%s" % dtype)
     torch.cuda.synchronize()
-    for (case, (_, pk, _), (wf, wd)) in zip(cases, todo, ref):
+    for (case, (pk, _), (wf, wd)) in zip(cases, todo, ref):
         assert torch.equal(pk.wf, wf), ("wf", case)
         assert torch.equal(pk.wd, wd), ("wd", case)
 

@@ -181,8 +181,8 @@ def test_fold_pack_is_the_fp32_product_rounded_once(dtype, with_bias):
         assert not torch.equal(twice, wA.to(dtype))
 
 
-def test_fold_pack_batched_equals_single_and_depthwise_is_unrounded():
-    from mrfp_amd import conv as conv_mod
+def _fold_pairs():
+    """(conv, norm) x 3: 24 -> 40 3x3, depthwise 40 3x3, 40 -> 16 1x1 with a bias"""
     from mrfp_amd.network import mynn
     g = torch.Generator().manual_seed(9)
     mods = []
@@ -195,6 +195,12 @@ def test_fold_pack_batched_equals_single_and_depthwise_is_unrounded():
             n.weight.copy_(torch.randn(cout, generator=g))
             n.bias.copy_(torch.randn(cout, generator=g))
         mods.append((c, n))
+    return mods
+
+
+def test_fold_pack_batched_equals_single_and_depthwise_is_unrounded():
+    from mrfp_amd import conv as conv_mod
+    mods = _fold_pairs()
     items = []
     for c, n in mods:
         dw = c.groups != 1
@@ -203,7 +209,7 @@ def test_fold_pack_batched_equals_single_and_depthwise_is_unrounded():
         items.append((c.weight, c.bias, n, key))
     conv_mod.fold_packs_batched(items)
     for (c, n), it in zip(mods, items):
-        pk = conv_mod._PACKS[id(c.weight)][it[3]]
+        pk = conv_mod._packs_of(c.weight).folded[it[3]]
         wA, S = _host_fold(c.weight.detach().cpu(), c.bias.detach().cpu() if c.bias is not None else None, n.weight.detach().cpu(),
                            n.bias.detach().cpu(), n.running_mean.cpu(), n.running_var.cpu(), n.eps)
         ref = wA.permute(0, 2, 3, 1).contiguous()
@@ -212,6 +218,55 @@ def test_fold_pack_batched_equals_single_and_depthwise_is_unrounded():
         else:
             assert torch.equal(_bits(pk.wf.cpu().view_as(ref)), _bits(ref.to(torch.bfloat16)))
         assert _ulp_close(pk.bias.cpu(), S)
+
+
+def test_a_stale_member_refolds_its_whole_registered_set_in_one_launch():
+    """conv.get_folded_pack on a member of a registered set (conv.register_fold_set): ONE mrfp_pack_weights_folded_batched over
+    every stale pack of the set -- three jobs here -- and no single launch; the other members then hit.  The same again after a
+    bump of ops.RUNNING_STATS_EPOCH, whichever member is asked first.  A weight in no set takes one mrfp_pack_weight_folded.
+    The set's packs equal those of three single launches bit for bit."""
+    from mrfp_amd import _lib, ops
+    from mrfp_amd import conv as conv_mod
+    from mrfp_amd._lib import call, ptr, stream
+    from mrfp_amd.inference import _FoldSet
+    T = torch.bfloat16
+    pairs = _FoldSet(_fold_pairs())
+    lone = _fold_pairs()[0]
+    conv_mod.register_fold_set(pairs)
+
+    def get(c, n):
+        dw = c.groups != 1
+        N, C = c.weight.shape[0], c.weight.shape[1]
+        assert N % 8 == 0 and (dw or C % 8 == 0)          # the set's standard geometry is the one asked for here
+        return conv_mod.get_folded_pack(c.weight, c.bias, n, T, 1 if dw else C, N, depthwise=dw)
+
+    launches = []
+    prev = _lib.HOOK[0]
+    _lib.HOOK[0] = lambda name, args: launches.append((name, args)) if name.startswith("mrfp_pack_weight") else None
+    try:
+        get(*pairs[0])
+        assert [n for n, _ in launches] == ["mrfp_pack_weights_folded_batched"] and launches[0][1][2] == 3, launches
+        packs = [get(c, n) for c, n in pairs]
+        assert len(launches) == 1, launches
+        ops.RUNNING_STATS_EPOCH[0] += 1
+        get(*pairs[2])
+        assert [n for n, _ in launches[1:]] == ["mrfp_pack_weights_folded_batched"] and launches[1][1][2] == 3, launches
+        assert [get(c, n) for c, n in pairs] == packs and len(launches) == 2, launches
+        get(*lone)
+        assert [n for n, _ in launches[2:]] == ["mrfp_pack_weight_folded"], launches
+        get(*lone)
+        assert len(launches) == 3, launches
+    finally:
+        _lib.HOOK[0] = prev
+    for (c, n), pk in zip(pairs, packs):
+        dw = c.groups != 1
+        N, C, R, S = c.weight.shape
+        wf = torch.full_like(pk.wf, 3.0)
+        bias = torch.full_like(pk.bias, 3.0)
+        call("mrfp_pack_weight_folded", ptr(c.weight), ptr(wf), ptr(c.bias), ptr(n.weight), ptr(n.bias), ptr(n.running_mean),
+             ptr(n.running_var), float(n.eps), ptr(bias), _lib.F32 if dw else _lib._DT[T], N, C, R, S, N, C, stream())
+        assert pk.wf.dtype == (torch.float32 if dw else T)
+        assert torch.equal(_bits(pk.wf), _bits(wf)) and torch.equal(_bits(pk.bias), _bits(bias)), tuple(c.weight.shape)
 
 
 # ---- models ----------------------------------------------------------------------------------------------------------------
