@@ -779,6 +779,23 @@ int mrfp_label_encode_i64(const void* src_u8, const void* lut, int64_t* dst_i64,
 int mrfp_eval_assemble(const void* img, const void* lab, const int32_t* ytab, const int32_t* xtab, int64_t Hs, int64_t Ws,
                        int64_t Hl, int64_t Wl, int pad_x, int pad_y, int x1, int y1, int64_t Hc, int64_t Wc, int pad_label,
                        const void* lut, float* out_img, int64_t* out_lab, void* stream);
+/* Class-uniform sampling, the producer half (reference config.py:53-64 CLASS_UNIFORM_PCT; the published form loops
+ * `for tile: for class: scipy.ndimage.center_of_mass` over label PNGs on the host -- its source is not in the reference tree, so the
+ * rule below is the definition).  lab: uint8 [B,H,W] on the device, any alignment.
+ *   v = table ? table[lab] : lab (table: 256 bytes on the device, the id -> train id step); a pixel belongs to class c iff v == c and
+ *   c < C (255 and ids >= C belong to nothing).  Tiles are tile x tile with origin (tx * tile, ty * tile).  partial == 0: only whole
+ *   tiles, H / tile by W / tile of them -- the ragged right and bottom strips are never read (the published behaviour); partial != 0:
+ *   ceil tiles, the ragged ones count (this build's extension).  mrfp_tile_count(size, tile, partial) is that count along one axis
+ *   (host only; -1 for tile < 1 or size < 0).
+ *   sums int64 [B][nty][ntx][C][3] = n, sum(x - x0), sum(y - y0) over the class's pixels in the tile; cent int32 [B][nty][ntx][C][2] =
+ *   cx, cy in image coordinates, cx = x0 + floor(sum(x - x0) / n), cy likewise -- int(center_of_mass(patch == c)) + offset of the
+ *   published form -- and -1, -1 where n == 0.  Both are written in full: the entry clears what it accumulates into.
+ * Three launches (clear, accumulate, divide), integers only (LDS counters, then 64-bit integer atomic adds, which commute: two runs
+ * give the same bits), no host wait.  Refused on the host, by name: C outside 1..256, tile outside 1..65536, H or W >= 2^31,
+ * B * nty * ntx * C >= 2^31, no tile (partial == 0 and H < tile or W < tile). */
+int64_t mrfp_tile_count(int64_t size, int64_t tile, int partial);
+int mrfp_tile_class_sums(const uint8_t* lab, const uint8_t* table, int64_t B, int64_t H, int64_t W, int64_t C, int64_t tile,
+                         int partial, int64_t* sums, int32_t* cent, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Frequency filters of the input pipeline (reference dataloaders.py:24-45 HPF, 59-79 LPF, 47-57 PHOT: np.fft.fftn over the

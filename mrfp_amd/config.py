@@ -48,6 +48,10 @@ cfg.EPOCH = 0
 cfg.BATCH_WEIGHTING = False
 cfg.BORDER_WINDOW = 1
 cfg.STRICTBORDERCLASS = None
+# class-uniform sampling (reference config.py:53-54; input_pipeline.ClassUniformSampler / ClassCentroids read them): the share of an
+# epoch that is drawn class by class around tile centroids (0: a plain permutation), and the tile edge the centroids are taken over.
+cfg.CLASS_UNIFORM_PCT = 0.0
+cfg.CLASS_UNIFORM_TILE = 1024
 cfg.MODEL = AttrDict()
 cfg.MODEL.BN = "hip-batchnorm"
 # set lazily by network.mynn (the HIP BatchNorm2d subclass); the reference default is

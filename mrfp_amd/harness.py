@@ -16,8 +16,10 @@ from __future__ import annotations
 import contextlib
 import math
 import os
+import random
 from typing import List, Optional
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -1025,6 +1027,38 @@ def eval_batches(samples, transform, encoder=None):
     for img_u8, lab_u8 in samples:
         img, lab = transform(img_u8, lab_u8, encoder)
         yield img.unsqueeze(0), lab.unsqueeze(0)
+
+
+def train_batches(samples, transform, batch_size, items=None, encoder=None, rng=random, np_rng=np.random, drop_last=True):
+    """The training sibling of eval_batches: samples[i] -> (uint8 [H,W,3] image, uint8 [H,W] label map) on the device; yields
+    (img [B,3,T,T] float32, label [B,T,T] int64), T = transform.crop_size (a transform with square crops: TrainTransform,
+    ScaleCropTransform), every sample written by `transform` into its slot of the batch (out_img / out_lab).  items: the epoch of input_pipeline.ClassUniformSampler, [(index, centroid | None, class_id | None)],
+    or None for samples 0 .. len - 1 in order; an item with a centroid is drawn with transform.draw(..., centroid=) (TrainTransform),
+    one without exactly as before.  encoder: a LabelEncoder, applied to the label map first (mrfp_label_lut_u8), as the reference's
+    __getitem__ encodes before it transforms.  rng / np_rng: the streams the draws consume.  drop_last: a trailing batch of fewer
+    than batch_size samples is dropped, else yielded short."""
+    from .input_pipeline import _out_slot
+    batch_size, T = int(batch_size), int(transform.crop_size)
+    if batch_size < 1:
+        raise ValueError("train_batches: batch_size must be >= 1, got %r" % (batch_size,))
+    if items is None:
+        items = [(i, None, None) for i in range(len(samples))]
+    for lo in range(0, len(items), batch_size):
+        chunk = items[lo:lo + batch_size]
+        if len(chunk) < batch_size and drop_last:
+            return
+        img = lab = None
+        for j, (index, centroid, _cls) in enumerate(chunk):
+            img_u8, lab_u8 = samples[index]
+            if img is None:
+                img = _out_slot(None, (len(chunk), 3, T, T), torch.float32, img_u8.device, "img")
+                lab = _out_slot(None, (len(chunk), T, T), torch.int64, img_u8.device, "label")
+            if encoder is not None:
+                lab_u8 = encoder(lab_u8)
+            h, w = lab_u8.shape
+            d = transform.draw(w, h, rng, np_rng) if centroid is None else transform.draw(w, h, rng, np_rng, centroid=centroid)
+            transform(img_u8, lab_u8, d, out_img=img[j], out_lab=lab[j])
+        yield img, lab
 
 
 # ------------------------------------------------------------------------------------------

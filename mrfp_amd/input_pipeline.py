@@ -135,6 +135,7 @@ class Draw:
     pad: Tuple[int, int]               # (pad_w, pad_h) of ImageOps.expand on every side
     crop: Tuple[int, int]              # (x1, y1) in the padded image
     blur: Optional[float]              # GaussianBlur radius when its gate fired
+    centroid: Optional[Tuple[int, int]] = None     # (c_x, c_y) the crop step was given (mirrored, scaled), None: a plain crop
 
 
 def _draw_jitter(rng, np_rng, j) -> Optional[list]:
@@ -249,14 +250,24 @@ class TrainTransform:
 
     JITTER = dict(brightness=0.5, hue=0.3, contrast=0.2, saturation=0.2)      # main.py:412
 
-    def draw(self, w: int, h: int, rng=_random, np_rng=np.random) -> Draw:
+    def draw(self, w: int, h: int, rng=_random, np_rng=np.random, centroid=None) -> Draw:
         """Consumes python's `random` stream in the reference's order (dataloaders.py:145, 655, 421, 327-331, 172-174) and,
         when the ColorJitter gate fires, numpy's global stream as get_params does (:622-643: four uniform factors, then
-        np.random.shuffle of the four transforms)."""
+        np.random.shuffle of the four transforms).
+        centroid = (c_x, c_y), a point of the w x h source the crop has to cover (class-uniform sampling):
+        RandomSizeAndCrop scales it as it scales the size, [int(c * scale_amt) for c in centroid] (:424-425), and RandomCrop draws
+        x1 = randint(c_x - t, c_x), y1 = randint(c_y - t, c_y), each clipped to the padded image (:313-322) -- two randint calls
+        whenever the crop is not the early return, also where the plain path draws none.  Kept as the reference has it: the
+        centroid is NOT moved by ImageOps.expand's padding, and the interval is [c - t, c], so x1 <= c_x <= x1 + t (closed).
+        This build's own rule: transform_tr flips before it crops and hands no centroid on, so when the flip fired the crop step
+        gets w - 1 - c_x."""
         flip = rng.random() < 0.5
         jitter = _draw_jitter(rng, np_rng, self.JITTER)
         scale_amt = 1.0 * rng.uniform(self.scale_min, self.scale_max)
         sw, sh = int(w * scale_amt), int(h * scale_amt)
+        if centroid is not None:
+            c_x, c_y = centroid
+            centroid = tuple(int(c * scale_amt) for c in ((w - 1 - c_x if flip else c_x), c_y))
         t = self.crop_size
         pad_w = pad_h = 0
         x1 = y1 = 0
@@ -264,10 +275,14 @@ class TrainTransform:
             pad_h = (t - sh) // 2 + 1 if t > sh else 0
             pad_w = (t - sw) // 2 + 1 if t > sw else 0
             W2, H2 = sw + 2 * pad_w, sh + 2 * pad_h
-            x1 = 0 if W2 == t else rng.randint(0, W2 - t)
-            y1 = 0 if H2 == t else rng.randint(0, H2 - t)
+            if centroid is not None:
+                x1 = min(W2 - t, max(0, rng.randint(centroid[0] - t, centroid[0])))
+                y1 = min(H2 - t, max(0, rng.randint(centroid[1] - t, centroid[1])))
+            else:
+                x1 = 0 if W2 == t else rng.randint(0, W2 - t)
+                y1 = 0 if H2 == t else rng.randint(0, H2 - t)
         blur = _draw_blur(rng)
-        return Draw(flip, jitter, (sw, sh), (pad_w, pad_h), (x1, y1), blur)
+        return Draw(flip, jitter, (sw, sh), (pad_w, pad_h), (x1, y1), blur, centroid)
 
     def _tables(self, dev, H, W, sh, sw):
         key = (str(dev), H, W, sh, sw)
@@ -925,3 +940,122 @@ class ResizeHeightCenterCropPad:
         call("mrfp_eval_assemble", ptr(cur), ptr(lab_u8), ptr(ty), ptr(tx), t, ncol, H, W, pad_x, 0, x1, 0, t, t, self.ignore_index,
              ptr(table), ptr(out_img), ptr(out_lab), stream())
         return out_img, out_lab
+
+
+# ---- class-uniform sampling (reference config.py:53-64 CLASS_UNIFORM_PCT; csrc/sample.hip) ----------------
+# The reference carries the consumer half -- RandomCrop / RandomSizeAndCrop take a centroid (dataloaders.py:280-337, 407-434;
+# TrainTransform.draw(centroid=) above) -- and not the producer (`uniform.py` of the DeepLabV3+ lineage): the rule of
+# mrfp_tile_class_sums (include/mrfp_hip.h) and of ClassUniformSampler.epoch is therefore build-defined.
+def _label_table(table, dev) -> Optional[torch.Tensor]:
+    if table is None:
+        return None
+    if isinstance(table, LabelEncoder):
+        return table.device_table(dev)
+    if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.uint8 and tuple(table.shape) == (256,)
+            and table.is_contiguous()):
+        raise _lib.MrfpHipError("tile_class_centroids: table must be a LabelEncoder or its 256-entry uint8 CUDA tensor")
+    return table
+
+
+def tile_class_centroids(lab_u8: torch.Tensor, num_classes: int, tile: int = 1024, table=None, partial_tiles: bool = False):
+    """Per image tile and class: pixel count, coordinate sums and integer centroid, in one pass over uint8 label maps on the device.
+    lab_u8: uint8 CUDA [H,W] or [B,H,W]; table: a LabelEncoder or its 256-entry uint8 device tensor, applied as the labels are read (the
+    published id2trainid step).  -> (sums int64 [B,nty,ntx,C,3] = n, sum(x - x0), sum(y - y0); cent int32 [B,nty,ntx,C,2] = cx, cy in
+    image coordinates, -1, -1 where the class has no pixel in the tile).  partial_tiles=False is the published rule (whole tiles only: the
+    ragged right and bottom strips are never looked at, an image smaller than a tile is refused); True counts the ragged tiles too."""
+    if not (isinstance(lab_u8, torch.Tensor) and lab_u8.is_cuda and lab_u8.dtype == torch.uint8 and lab_u8.dim() in (2, 3)
+            and lab_u8.numel() > 0):
+        raise _lib.MrfpHipError("tile_class_centroids: lab_u8 must be a non-empty uint8 CUDA tensor [H,W] or [B,H,W] (there is no CPU "
+                                "path), got %s" % ("%s %s %s" % (lab_u8.dtype, tuple(lab_u8.shape), lab_u8.device)
+                                                   if isinstance(lab_u8, torch.Tensor) else type(lab_u8).__name__))
+    C, tile, partial = int(num_classes), int(tile), int(bool(partial_tiles))
+    lab_u8 = lab_u8.contiguous()
+    B = 1 if lab_u8.dim() == 2 else lab_u8.shape[0]
+    H, W = lab_u8.shape[-2], lab_u8.shape[-1]
+    dev = lab_u8.device
+    table = _label_table(table, dev)
+    count = _lib.lib().mrfp_tile_count
+    nty, ntx = max(int(count(H, tile, partial)), 0), max(int(count(W, tile, partial)), 0)      # (the entry refuses what is wrong, by name)
+    sums = _out_slot(None, (B, nty, ntx, max(C, 0), 3), torch.int64, dev, "sums")
+    cent = _out_slot(None, (B, nty, ntx, max(C, 0), 2), torch.int32, dev, "cent")
+    call("mrfp_tile_class_sums", ptr(lab_u8), ptr(table), B, H, W, C, tile, partial, ptr(sums), ptr(cent), stream())
+    return sums, cent
+
+
+class ClassCentroids:
+    """The centroid table of a training set: by_class[c] = [(image_index, (cx, cy)), ...], one entry per (image, tile) in which class c
+    occurs, in (image, tile-row, tile-column) order.  tile=None reads cfg.CLASS_UNIFORM_TILE when maps are added; encoder: the
+    LabelEncoder the raw label ids go through first.  This is preprocessing, once per training set, not the training step:
+    add() makes one device -> host copy of the small centroid table per call."""
+
+    def __init__(self, num_classes: int, tile: Optional[int] = None, partial_tiles: bool = False, encoder: Optional[LabelEncoder] = None):
+        self.num_classes, self.tile, self.partial_tiles, self.encoder = int(num_classes), tile, bool(partial_tiles), encoder
+        if not 1 <= self.num_classes <= 256:
+            raise ValueError("ClassCentroids: num_classes must be in 1..256, got %r" % (num_classes,))
+        self.by_class = [[] for _ in range(self.num_classes)]
+
+    def add(self, first_index: int, lab_u8: torch.Tensor):
+        """One label map [H,W], or a batch [B,H,W] of equal-sized ones that are images first_index .. first_index + B - 1."""
+        from .config import cfg
+        tile = cfg.CLASS_UNIFORM_TILE if self.tile is None else self.tile
+        _, cent = tile_class_centroids(lab_u8, self.num_classes, tile, self.encoder, self.partial_tiles)
+        host = cent.cpu().numpy()                            # [B,nty,ntx,C,2]
+        b, ty, tx, c = np.nonzero(host[..., 0] >= 0)         # row-major: (image, tile-row, tile-column) order within a class
+        for bi, yi, xi, ci in zip(b.tolist(), ty.tolist(), tx.tolist(), c.tolist()):
+            cx, cy = host[bi, yi, xi, ci].tolist()
+            self.by_class[ci].append((int(first_index) + bi, (cx, cy)))
+
+    def state_dict(self):
+        """Plain lists and ints (JSON-able, as the published form caches its centroid files)."""
+        return {"num_classes": self.num_classes, "tile": self.tile, "partial_tiles": self.partial_tiles,
+                "by_class": [[[i, [cx, cy]] for i, (cx, cy) in lst] for lst in self.by_class]}
+
+    def load_state_dict(self, sd):
+        if int(sd["num_classes"]) != self.num_classes or len(sd["by_class"]) != self.num_classes:
+            raise ValueError("ClassCentroids: the state holds %r classes, this table %d" % (sd["num_classes"], self.num_classes))
+        self.tile, self.partial_tiles = sd["tile"], bool(sd["partial_tiles"])
+        self.by_class = [[(int(i), (int(c[0]), int(c[1]))) for i, c in lst] for lst in sd["by_class"]]
+
+
+class ClassUniformSampler:
+    """An epoch that draws every class equally often (cfg.CLASS_UNIFORM_PCT; build-defined).
+    per_class = int(n_images * pct / C), n_rand = n_images - per_class * C.  pick(alist, k): idx = arange(len); np_rng.shuffle(idx);
+    [alist[idx[i % len]] for i in range(k)] -- a short list wraps around.  epoch(): pick(range(n_images), n_rand) as
+    (index, None, None), then for c ascending pick(by_class[c], per_class) as (index, centroid, c) for every class that has an entry
+    (a class that is nowhere adds nothing: the epoch is shorter), then one np_rng.shuffle(items) when `shuffle`.  pct = 0 is a
+    permutation of the images.  centroids: a ClassCentroids or its by_class list; pct=None reads cfg.CLASS_UNIFORM_PCT per epoch."""
+
+    def __init__(self, n_images: int, centroids, pct: Optional[float] = None):
+        self.n_images = int(n_images)
+        self.by_class = centroids.by_class if isinstance(centroids, ClassCentroids) else list(centroids)
+        if self.n_images < 1 or not self.by_class:
+            raise ValueError("ClassUniformSampler: n_images >= 1 and at least one class expected")
+        if pct is not None and not 0.0 <= float(pct) <= 1.0:
+            raise ValueError("ClassUniformSampler: pct must be in [0, 1], got %r" % (pct,))
+        self.pct = pct
+
+    @staticmethod
+    def pick(alist, k: int, np_rng=np.random):
+        idx = np.arange(len(alist))
+        np_rng.shuffle(idx)
+        return [alist[int(idx[i % len(alist)])] for i in range(k)]
+
+    def epoch(self, np_rng=np.random, shuffle: bool = True):
+        """-> [(index, centroid | None, class_id | None), ...]"""
+        from .config import cfg
+        pct = float(cfg.CLASS_UNIFORM_PCT if self.pct is None else self.pct)
+        C = len(self.by_class)
+        per_class = int(self.n_images * pct / C)
+        n_rand = self.n_images - per_class * C
+        items = [(i, None, None) for i in self.pick(range(self.n_images), n_rand, np_rng)]
+        for c, entries in enumerate(self.by_class):
+            if entries:
+                items += [(i, cen, c) for i, cen in self.pick(entries, per_class, np_rng)]
+        if shuffle:
+            np_rng.shuffle(items)
+        return items
+
+    @staticmethod
+    def shard(items, rank: int, world: int):
+        """items[rank::world], cut to len(items) // world: every rank builds the same epoch from the same seed and takes its share."""
+        return items[rank::world][:len(items) // world]
