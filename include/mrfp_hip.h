@@ -410,6 +410,78 @@ int mrfp_upsample_region_bwd(const void* P, int64_t ld, const int64_t* target, c
                              void* dlogits, int64_t Cd, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
                              int64_t C, int64_t ignore_index, int per_image, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Stable segmented radix sort of (key, payload) pairs (csrc/sort.hip), the public primitive beside mrfp_select_kth: the pairs of
+ * keys_in / payload_in (uint32 each, n of them, n < 2^31) sorted ascending by the low `bits` key bits (1..32; higher bits travel with
+ * the key and are ignored), pairs with equal keys in their input order, independently inside each of S segments: segment s is items
+ * [offsets[s], offsets[s + 1]); offsets: int64 [S + 1] on the device, non-decreasing, offsets[0] = 0 and offsets[S] = n (NULL: S = 1,
+ * the whole array; zero-length segments are fine; offsets are clamped to [0, n] and every store is bounds-checked, so a wrong array
+ * gives a wrong order and never a store outside the buffers).  Least-significant-digit first, 8 bits per pass, ceil(bits / 8)
+ * passes of three launches (per-tile digit histogram, scan, scatter); one workgroup ranks mrfp_sort_tile_items() consecutive items
+ * per pass, a scan workgroup walks the tiles of a segment mrfp_sort_scan_sweep() at a time.  No workgroup waits for another inside
+ * a launch, counts are integers (two runs place every pair identically), every loop is bounded by n and S, grids are capped at 2048
+ * workgroups.  The passes alternate between the outputs and ws (mrfp_sort_pairs_ws_bytes(n, S) bytes, 16-byte aligned; < 0: refused
+ * size) so that the last one writes the outputs; the inputs are not written, and keys_out / payload_out may BE the inputs when the
+ * number of passes is even.
+ * ------------------------------------------------------------------------------------------- */
+int64_t mrfp_sort_tile_items(void);
+int64_t mrfp_sort_scan_sweep(void);
+int64_t mrfp_sort_pairs_ws_bytes(int64_t n, int64_t S);
+int mrfp_sort_pairs(const void* keys_in, const void* payload_in, void* keys_out, void* payload_out, int64_t n,
+                    const int64_t* offsets, int64_t S, int bits, void* ws, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Lovasz-Softmax loss (Berman, Triki, Blaschko, CVPR 2018; csrc/lovasz.hip), the convex surrogate of the Jaccard index.  Not in the
+ * reference tree: build-defined, DESIGN.md section 8.  Sources, z_i, p_i = softmax(z_i) (fp32) and validity as for the region loss;
+ * 1 <= C <= 64, B * H * W < 2^31.  Scope: the valid pixels of this process's batch (per_image == 0) or of each image (!= 0).  Per scope
+ * and class c:  f_i = [t_i == c],  e_i = |f_i - p_{i,c}|,  G = sum_i f_i.  Order the scope's pixels by e descending, ties by ascending
+ * flat pixel index b * HW + p (a stable sort: the tie rule is part of the definition, it makes the gradient reproducible).  With F_i /
+ * B_i the foreground / background pixels before pixel i in that order:
+ *     J_i = 1 - (G - F_i - f_i) / (G + B_i + 1 - f_i),   J_i^- = 1 - (G - F_i) / (G + B_i)  (0 for the first pixel),   g_i = J_i - J_i^- >= 0
+ *     loss_c = sum_i e_i g_i          (Berman's dot(errors_sorted, lovasz_grad(fg_sorted)); it does not depend on the order of ties)
+ * evaluated as g_i = 1 / (G + B_i) for f_i = 1 and (G - F_i) / ((G + B_i)(G + B_i + 1)) for f_i = 0 (1 for the first pixel of a class with
+ * G = 0): the same numbers without a difference of two values near 1.
+ * The scope's loss is the mean of loss_c over the classes with G > 0 (all_classes == 0) or over all C (an absent class then adds the
+ * largest p_c of the scope); a scope with no valid pixel has no counted class.  loss = the mean over the scopes that have a counted
+ * class (the region loss's rule; the published per-image helper averages all-ignored images in as 0); none: 0.
+ * bwd, g a constant: with a_i[c] = (1 - 2 f_i) g_i / (classes counted in the scope), 0 for a class that is not counted,
+ *     dz_i[j] = k p_i[j] (a_i[j] - sum_c a_i[c] p_i[c]),   k = gscale[0] * out[1] (gscale NULL = 1);
+ * zeros for every other pixel and for pad channels; every row is stored.  The upsample forms work on the channel-padded scores
+ * P[B,Hi,Wi,ld] and write d(logits)[B,H,W,Cd] for mrfp_bilinear_bwd exactly as mrfp_upsample_region_bwd.
+ *
+ * fwd: classes in groups of mrfp_lovasz_group_classes() (fewer where group * B * H * W would reach 2^31).  Per group: a keys pass over
+ * the source (key 0x3F800000 - bits(e), 0x3FFFFFFF for an ignored pixel: behind every valid one; payload 2 * flat index + f),
+ * mrfp_sort_pairs on 30 bits with one segment per (class, scope), a three-launch integer scan of the foreground bits in sorted order
+ * (per-tile count; per-segment scan, whose total is G; the third completes it inside the coefficient pass), and the coefficient
+ * pass: g_i, e_i g_i into one fp32 partial per tile, (1 - 2 f_i) g_i scattered through the payload into the coefficient plane.  One
+ * workgroup then sums the partials in double in a fixed order and decides class presence on the device.  No floating-point atomics,
+ * no workgroup waits for another, nothing waits for the host: two runs are bit-identical and fwd + bwd can be captured in a graph.
+ * ws: mrfp_lovasz_ws_bytes(B, HW, C, per_image) bytes (< 0: refused size), 16-byte aligned; bounded by the group size, not by C:
+ * about 16 B * group per pixel.  out: float [mrfp_lovasz_out_floats(B, HW, C, per_image)], rows = per_image ? B : 1, CP = C rounded
+ * up to 8:  out[0] the loss; out[1] = 1 / (scopes that count), 0 if none; the factor table float [rows][CP], 1 / (classes counted) for
+ * a counted class of a scope that counts, else 0; then the coefficient plane float [C][B * HW], class-major, (1 - 2 f_i) g_i at every
+ * valid pixel (elsewhere unwritten, and never read): the one per-pixel-per-class tensor kept for the backward.
+ *
+ * mrfp_lovasz_errors: the planes e as the keys pass computes them, float [C][B][H][W], 2.0 at an invalid pixel -- what a test takes the
+ * device's own order from.  scores / ld / Hi / Wi: the channel-padded low-resolution scores, or with Hi == Wi == 0 dense logits
+ * [B,H,W,C] (ld unused).
+ * ------------------------------------------------------------------------------------------- */
+int64_t mrfp_lovasz_group_classes(void);
+int64_t mrfp_lovasz_ws_bytes(int64_t B, int64_t HW, int64_t C, int per_image);
+int64_t mrfp_lovasz_out_floats(int64_t B, int64_t HW, int64_t C, int per_image);
+int mrfp_lovasz_fwd(const void* logits, const int64_t* target, int dtype, int64_t B, int64_t HW, int64_t C,
+                    int64_t ignore_index, int all_classes, int per_image, void* ws, float* out, void* stream);
+int mrfp_lovasz_bwd(const void* logits, const int64_t* target, const float* out, const float* gscale, void* dlogits,
+                    int dtype, int64_t B, int64_t HW, int64_t C, int64_t ignore_index, int per_image, void* stream);
+int mrfp_upsample_lovasz_fwd(const void* P, int64_t ld, const int64_t* target, int dtype, int64_t B, int64_t Hi, int64_t Wi,
+                             int64_t H, int64_t W, int64_t C, int64_t ignore_index, int all_classes, int per_image, void* ws,
+                             float* out, void* stream);
+int mrfp_upsample_lovasz_bwd(const void* P, int64_t ld, const int64_t* target, const float* out, const float* gscale,
+                             void* dlogits, int64_t Cd, int dtype, int64_t B, int64_t Hi, int64_t Wi, int64_t H, int64_t W,
+                             int64_t C, int64_t ignore_index, int per_image, void* stream);
+int mrfp_lovasz_errors(const void* scores, int64_t ld, const int64_t* target, int dtype, int64_t B, int64_t Hi, int64_t Wi,
+                       int64_t H, int64_t W, int64_t C, int64_t ignore_index, float* errors, void* stream);
+
 /* Eval: argmax over classes + 19x19 confusion histogram on the device (reference main.py:898-909,
  * metrics.py:122-126): hist[num_classes*gt + pred] += 1 for gt in [0,num_classes).  hist: int64
  * [C*C], accumulated (not cleared).  pred (optional, uint8 [npix]) receives the arg-max. */

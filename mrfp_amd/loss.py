@@ -23,6 +23,11 @@ FocalLoss2d and RegionLoss2d are the two families a caller reaches for when mIoU
 that down-weights easy pixels, and the soft Dice / Jaccard overlap term, a direct surrogate of the IoU harness.evaluate reports,
 almost always used as CE + lambda * Dice -- SumLoss.  Neither is in the reference tree: include/mrfp_hip.h and DESIGN.md section 8
 hold the definitions; the kernels are csrc/loss.hip (Focal) and csrc/region.hip.
+
+LovaszSoftmax2d is the third: the Lovasz-Softmax loss (Berman, Triki, Blaschko, CVPR 2018), the convex surrogate of the Jaccard
+index, usually trained as CE + lambda * Lovasz -- SumLoss again.  Not in the reference tree either; the published form soft-maxes the
+full-resolution logits and runs one torch.sort and one cumulative sum per class on them; here the ranking is a stable segmented
+radix sort on the device (csrc/sort.hip, csrc/lovasz.hip) and the fused form never writes the full-resolution logits.
 """
 from __future__ import annotations
 
@@ -31,8 +36,8 @@ from torch import nn
 
 from . import ops
 
-__all__ = ["ImageBasedCrossEntropyLoss2d", "ImgWtLossSoftNLL", "OhemCrossEntropy2d", "FocalLoss2d", "RegionLoss2d", "SumLoss",
-           "fused_ce_kwargs", "fused_loss"]
+__all__ = ["ImageBasedCrossEntropyLoss2d", "ImgWtLossSoftNLL", "OhemCrossEntropy2d", "FocalLoss2d", "RegionLoss2d",
+           "LovaszSoftmax2d", "SumLoss", "fused_ce_kwargs", "fused_loss"]
 
 
 class ImageBasedCrossEntropyLoss2d(nn.Module):
@@ -180,6 +185,30 @@ class RegionLoss2d(nn.Module):
         return self.fused(inputs, targets)
 
 
+class LovaszSoftmax2d(nn.Module):
+    """The Lovasz-Softmax loss of softmax(inputs) against the targets over the valid pixels: per class the errors |[t == c] - p_c| of the
+    scope's pixels, sorted descending (ties by ascending pixel index: the order, and so the gradient, is reproducible), weighted by the
+    Lovasz gradient of the Jaccard loss; the mean over the classes present in the scope (classes='present') or over all ('all').  The
+    scope is the whole batch of this rank -- under data parallelism the order is per rank, like the OHEM selection -- or each image
+    (per_image), averaged over the images that have a counted class (the published helper also averages all-ignored images in, as 0).
+    Nothing valid: 0.  At most 64 classes, B * H * W < 2^31."""
+
+    def __init__(self, classes="present", per_image=False, ignore_index=255):
+        super().__init__()
+        ops._lovasz_options("LovaszSoftmax2d", classes)
+        self.classes, self.per_image, self.ignore_index = classes, bool(per_image), int(ignore_index)
+
+    def fused(self, logits, gts, size=None, channels=None):
+        """The loss on the kernels: of dense logits, or with `size` of the channel-padded low-resolution scores."""
+        kw = dict(classes=self.classes, per_image=self.per_image)
+        if size is not None:
+            return ops.upsample_lovasz_softmax(logits, gts, size, channels, self.ignore_index, **kw)
+        return ops.lovasz_softmax(logits, gts, self.ignore_index, **kw)
+
+    def forward(self, inputs, targets):
+        return self.fused(inputs, targets)
+
+
 class SumLoss(nn.Module):
     """sum_k w_k * crit_k(inputs, targets): SumLoss((1.0, nn.CrossEntropyLoss(ignore_index=255)), (0.5, RegionLoss2d())).  Its fused
     form is the same sum of the parts' fused forms over the same scores; it has one only if every part has."""
@@ -222,12 +251,14 @@ def fused_ce_kwargs(criterion):
     a tensor, None, or -- for the per-image criterion -- a callable of the label map (fused_loss calls it).  ImgWtLossSoftNLL is not a
     cross entropy: its entry is dict(soft_nll=<its own fused call>), which fused_loss calls with (logits, gts, size, channels);
     OhemCrossEntropy2d chooses its pixels first: dict(ohem=<its own fused call>), called the same way; so are FocalLoss2d (dict(focal=),
-    None with reduction='none'), RegionLoss2d (dict(region=)) and SumLoss (dict(sum=), None if a part has none)."""
+    None with reduction='none'), RegionLoss2d (dict(region=)), LovaszSoftmax2d (dict(lovasz=)) and SumLoss (dict(sum=), None if a part has none)."""
     c = criterion
     if isinstance(c, FocalLoss2d):
         return dict(focal=c.fused) if c.reduction in ("mean", "sum") else None
     if isinstance(c, RegionLoss2d):
         return dict(region=c.fused)
+    if isinstance(c, LovaszSoftmax2d):
+        return dict(lovasz=c.fused)
     if isinstance(c, SumLoss):
         return None if any(fused_ce_kwargs(p) is None for p in c.criteria) else dict(sum=c.fused)
     if isinstance(c, OhemCrossEntropy2d):
@@ -248,7 +279,7 @@ def fused_loss(criterion, logits, gts, size=None, channels=None):
     kw = fused_ce_kwargs(criterion)
     if kw is None:
         return None
-    for own in ("soft_nll", "ohem", "focal", "region", "sum"):
+    for own in ("soft_nll", "ohem", "focal", "region", "lovasz", "sum"):
         if own in kw:
             return kw[own](logits, gts, size, channels)
     ignore = kw.pop("ignore_index")

@@ -951,7 +951,7 @@ def add(a, b):
 # ------------------------------------------------------------------------------------------
 # The loss operators have the two axes of the kernels under them (csrc/loss_common.hpp): where a pixel's class vector comes from
 # (_Scores: dense logits, or low-resolution scores the kernel upsamples) and which criterion reads it (_PlainCe, _WeightedCe,
-# _SoftNll, _Focal).  One autograd function, _PixelLoss, serves every pair (the region loss has a sibling, _RegionLoss); the entry is mrfp_[upsample_]<stem>_{fwd,bwd}, and its arguments
+# _SoftNll, _Focal).  One autograd function, _PixelLoss, serves every pair (the region and Lovasz losses have a sibling, _RegionLoss); the entry is mrfp_[upsample_]<stem>_{fwd,bwd}, and its arguments
 # are looked up by the names include/mrfp_hip.h gives them, never placed by position.
 def _call_named(entry, env):
     """Calls `entry` with its positional arguments taken from env, a dictionary of named values to which the stream is added here; a
@@ -1446,14 +1446,20 @@ class _Region:
     def rows(self, src):
         return src.B if self.per_image else 1
 
+    def sizes(self, L, src):
+        """(workspace floats, out floats)"""
+        return L.mrfp_region_ws_floats(src.B, src.H * src.W, src.C), L.mrfp_region_out_floats(src.B, src.C, int(self.per_image))
+
 
 def _region_forward(src, crit, target, weight):
-    """Sums pass and finalize -> (validated target, out): out[0] the loss, out[1] the factor of the backward, the coefficient table,
-    the sums (include/mrfp_hip.h)."""
+    """The forward entry of a criterion over a scope (_Region: sums pass and finalize; _Lovasz: keys, sort, scan, coefficients per class
+    group and finalize) -> (validated target, out): out[0] the loss, out[1] the factor of the backward, then what the backward of the
+    criterion reads (include/mrfp_hip.h)."""
     target, weight = crit.check(src, target, weight)
     L, dev = _lib.lib(), src.x.device
-    ws = torch.empty(int(L.mrfp_region_ws_floats(src.B, src.H * src.W, src.C)), dtype=torch.float32, device=dev)
-    out = torch.empty(int(L.mrfp_region_out_floats(src.B, src.C, int(crit.per_image))), dtype=torch.float32, device=dev)
+    nws, nout = crit.sizes(L, src)
+    ws = torch.empty(int(nws), dtype=torch.float32, device=dev)
+    out = torch.empty(int(nout), dtype=torch.float32, device=dev)
     env = _loss_env(src, crit, target, weight, out)
     env.update(ws=ptr(ws), out=ptr(out))
     _call_named(src.prefix + crit.stem + "_fwd", env)
@@ -1510,6 +1516,130 @@ def region_sums(logits, target, ignore_index=255, *, size=None, channels=None, p
     _, out = _region_forward(src, crit, target, None)
     rows, CP = crit.rows(src), (src.C + 7) // 8 * 8
     return out[2 + rows * 2 * CP:].view(torch.float64).view(rows, 3, src.C).clone()
+
+
+# ---- the Lovasz-Softmax loss and the stable segmented radix sort under it (csrc/lovasz.hip, csrc/sort.hip; include/mrfp_hip.h and
+# DESIGN.md section 8 hold the definition).  The gradient of a pixel depends on the rank of its error among the pixels of the scope:
+# the loss is an operator of its own, not a kind of region_loss; its criterion record runs on _RegionLoss, whose forward asks the
+# record for the workspace and the saved `out` (here: loss, factor table, coefficient plane) ----
+LOVASZ_CLASSES = {"present": 0, "all": 1}   # all_classes
+LOVASZ_SENTINEL = 2.0                       # lovasz_errors at an invalid pixel
+LOVASZ_MAX_PIXELS = 2 ** 31                 # B * H * W below this: the payload holds 2 * flat index + the foreground bit
+
+
+def _lovasz_options(who, classes):
+    if not isinstance(classes, str) or classes not in LOVASZ_CLASSES:
+        raise _lib.MrfpHipError("%s: classes must be 'present' or 'all' (got %r; an explicit class list is not built)" % (who, classes))
+    return LOVASZ_CLASSES[classes]
+
+
+def _lovasz_limits(who, src):
+    _class_limit(who, src.C)
+    if not 0 < src.B * src.H * src.W < LOVASZ_MAX_PIXELS or src.B > 65535:
+        raise _lib.MrfpHipError("%s: 1 <= B <= 65535 and B * H * W < 2^31: a pixel's rank and index are 31-bit (B=%d, H=%d, W=%d)" % (
+            who, src.B, src.H, src.W))
+
+
+class _Lovasz:
+    """The Lovasz-Softmax loss (mrfp_[upsample_]lovasz_*): a criterion record, as _Region, of _RegionLoss."""
+    stem = "lovasz"
+
+    def __init__(self, who, ignore_index, classes="present", per_image=False):
+        self.who, self.ignore_index, self.per_image = who, ignore_index, bool(per_image)
+        self.all_classes = _lovasz_options(who, classes)           # what does not depend on the tensors: at once
+
+    def check(self, src, target, weight):
+        _lovasz_limits(self.who, src)
+        return _chk_target(self.who, target, torch.int64, 3, (src.B, src.H, src.W)), None
+
+    def extra(self, weight):
+        return dict(ignore_index=int(self.ignore_index), all_classes=self.all_classes, per_image=int(self.per_image))
+
+    def sizes(self, L, src):
+        B, HW, C, per = src.B, src.H * src.W, src.C, int(self.per_image)
+        return (int(L.mrfp_lovasz_ws_bytes(B, HW, C, per)) + 3) // 4, L.mrfp_lovasz_out_floats(B, HW, C, per)
+
+
+def lovasz_softmax(logits, target, ignore_index=255, *, classes="present", per_image=False):
+    """The Lovasz-Softmax loss (Berman et al., CVPR 2018) of softmax(logits) against the target over the valid pixels.  Per scope and class
+    c: e_i = |[t_i == c] - p_i[c]|; the scope's pixels ordered by e descending, ties by ascending flat pixel index (a stable sort: the
+    tie rule is part of the definition); loss_c = sum_i e_i g_i with g the Lovasz gradient of the Jaccard loss along that order, a
+    constant for the backward.  classes 'present': the mean over the classes that occur in the scope; 'all': over all C.  The scope
+    is the whole batch OF THIS RANK -- under data parallelism the order is per rank, like the OHEM selection -- or with per_image each
+    image, averaged over the images that have a counted class.  Nothing valid: 0, and a zero gradient.  logits [B,C,H,W], C <= 64,
+    B * H * W < 2^31.  -> fp32 scalar."""
+    return _RegionLoss.apply(logits, target, None, None, None, _Lovasz("lovasz_softmax", ignore_index, classes, per_image))
+
+
+def upsample_lovasz_softmax(P, target, size, channels, ignore_index=255, *, classes="present", per_image=False):
+    """lovasz_softmax of Upsample(P[:, :channels], size) without materialising the full-resolution logits (what is kept per pixel and
+    class is the fp32 coefficient plane the backward reads).  P: channel-padded low-resolution class scores [B,ld,Hi,Wi] (ld a multiple
+    of the 16-byte chunk)."""
+    return _RegionLoss.apply(P, target, None, (int(size[0]), int(size[1])), int(channels),
+                             _Lovasz("upsample_lovasz_softmax", ignore_index, classes, per_image))
+
+
+def lovasz_errors(logits, target, ignore_index=255, *, size=None, channels=None):
+    """The error planes e = |[t == c] - softmax(z)[c]| exactly as the loss's keys pass computes them: float32 [C,B,H,W] on the device,
+    LOVASZ_SENTINEL at an invalid pixel.  With `size`, logits are the channel-padded low-resolution scores.  A stable sort of a plane by
+    (-e, flat index) is the device's own order.  No autograd through it."""
+    who = "lovasz_errors"
+    fused = size is not None
+    src = _Scores(_chk(logits.detach(), "P" if fused else "logits"), (int(size[0]), int(size[1])) if fused else None,
+                  int(channels) if fused else None)
+    _lovasz_limits(who, src)
+    target = _chk_target(who, target, torch.int64, 3, (src.B, src.H, src.W))
+    # (filled, not torch.empty: tests/test_poison_gpu.py holds the table of functions that obtain uninitialised memory, and this
+    # one is a diagnostic off the training path)
+    err = torch.full((src.C, src.B, src.H, src.W), LOVASZ_SENTINEL, dtype=torch.float32, device=src.x.device)
+    call("mrfp_lovasz_errors", ptr(src.x), src.ld if fused else 0, ptr(target), dt(src.x), src.B, src.Hi if fused else 0,
+         src.Wi if fused else 0, src.H, src.W, src.C, int(ignore_index), ptr(err), stream())
+    return err
+
+
+def _chk_u32(who, name, t, n=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.MrfpHipError("%s: %s must be a GPU tensor: the HIP path has no CPU fallback" % (who, name))
+    if t.dtype != torch.int32 or t.dim() != 1 or (n is not None and t.numel() != n):
+        raise _lib.MrfpHipError("%s: %s must be a 1-dimensional int32 tensor%s (got %s %s)" % (
+            who, name, "" if n is None else " of %d elements" % n, t.dtype, tuple(t.shape)))
+    return t.detach().contiguous()
+
+
+def sort_pairs(keys, payload, offsets=None, bits=32):
+    """(keys, payload) sorted by key, ascending and STABLE (equal keys keep their order), on the device (mrfp_sort_pairs: a
+    least-significant-digit radix sort, three launches per 8 key bits, no host wait).  keys, payload: int32 GPU tensors [n] whose bits
+    are read as unsigned; bits: how many low key bits take part (the rest travels along).  offsets: int64 GPU tensor [S + 1],
+    non-decreasing from 0 to n: the pairs are sorted inside each segment [offsets[s], offsets[s + 1]) independently.  -> new tensors."""
+    who = "sort_pairs"
+    bits = int(bits)
+    if not 1 <= bits <= 32:
+        raise _lib.MrfpHipError("%s: 1 <= bits <= 32 (got %d)" % (who, bits))
+    keys = _chk_u32(who, "keys", keys)
+    n = keys.numel()
+    payload = _chk_u32(who, "payload", payload, n)
+    if n >= 2 ** 31:
+        raise _lib.MrfpHipError("%s: n < 2^31 (n=%d)" % (who, n))
+    S = 1
+    if offsets is not None:
+        if not isinstance(offsets, torch.Tensor) or not offsets.is_cuda or offsets.dtype != torch.int64 or offsets.dim() != 1 \
+                or offsets.numel() < 2:
+            raise _lib.MrfpHipError("%s: offsets must be a 1-dimensional int64 GPU tensor of S + 1 >= 2 elements" % who)
+        offsets = offsets.contiguous()
+        S = offsets.numel() - 1
+    # the outputs start as copies and the workspace filled (see lovasz_errors): with an odd number of passes the entry reads the copies
+    # and writes them last; with an even number it sorts them in place
+    ko, po = keys.clone(), payload.clone()
+    if n == 0:
+        return ko, po
+    nws = int(_lib.lib().mrfp_sort_pairs_ws_bytes(n, S))
+    if nws < 0:
+        raise _lib.MrfpHipError("%s: unsupported size (n=%d, S=%d)" % (who, n, S))
+    ws = torch.zeros((nws + 3) // 4, dtype=torch.int32, device=keys.device)
+    even = ((bits + 7) // 8) % 2 == 0
+    call("mrfp_sort_pairs", ptr(ko if even else keys), ptr(po if even else payload), ptr(ko), ptr(po), n, ptr(offsets), S, bits, ptr(ws),
+         stream())
+    return ko, po
 
 
 # ------------------------------------------------------------------------------------------
