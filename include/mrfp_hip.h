@@ -482,6 +482,60 @@ int mrfp_upsample_lovasz_bwd(const void* P, int64_t ld, const int64_t* target, c
 int mrfp_lovasz_errors(const void* scores, int64_t ld, const int64_t* target, int dtype, int64_t B, int64_t Hi, int64_t Wi,
                        int64_t H, int64_t W, int64_t C, int64_t ignore_index, float* errors, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Two-view consistency losses (csrc/consist.hip): the criteria that compare the class scores of TWO forward passes -- the perturbed and
+ * the unperturbed view of MRFP, a student and a mean teacher, a small model distilled from a large one.  Not in the reference tree:
+ * build-defined, DESIGN.md section 8.  Per full-resolution pixel two fp32 class vectors: z^s, the student (it takes the gradient), and
+ * z^t, the teacher.  Both views are dense logits [B,H,W,C] (mrfp_consist_*) or both are channel-padded low-resolution scores
+ * P[B,Hi,Wi,ld] upsampled inside the kernel, align-corners bilinear, as every fused loss here (mrfp_upsample_consist_*); the two
+ * fused views may differ in ld, Hi, Wi (a teacher with another output stride).  One dtype, one C, one (H, W).
+ * 1 <= C <= mrfp_consist_max_classes() = 64: the student's class vector lives in registers, the teacher's is walked in 16-byte chunks.
+ * valid: int64 [B][HW], a pixel is counted iff 0 <= valid < C (the family's rule: the ground truth can be passed as it is); NULL:
+ * every pixel is counted.  N_counted = the counted pixels of this process's batch.
+ * With p = softmax(z^s / T), q = softmax(z^t / T), m = (p + q) / 2, T = temperature > 0:
+ *     MRFP_CONSIST_KL:    l = T^2 sum_c q_c (log q_c - log p_c);   loss = sum_counted l / N_counted.
+ *                         The teacher is a constant: d loss / d z^s_j = (T / N_counted) (p_j - q_j).
+ *     MRFP_CONSIST_JS:    l = T^2 (KL(p || m) / 2 + KL(q || m) / 2), the same mean.  With u_j = (log p_j - log m_j) / 2:
+ *                         d loss / d z^s_j = (T / N_counted) p_j (u_j - sum_c p_c u_c), and the same with p and q exchanged for z^t.
+ *                         The gradient goes to every view whose dlogits pointer is not NULL; the rows of a NULL view are not written.
+ *     MRFP_CONSIST_HARD:  k = argmax_c z^t_c, the first maximum; conf = softmax(z^t)_k AT T = 1 (the temperature does not enter
+ *                         this kind); the pixel is kept iff it is counted and conf >= threshold, 0 <= threshold <= 1;
+ *                         l = -log softmax(z^s)_k;  loss = sum_kept l / D, D = N_kept (normalize MRFP_CONSIST_KEPT) or N_counted
+ *                         (MRFP_CONSIST_VALID: the loss weighted by the confident share).  The teacher is a constant:
+ *                         d loss / d z^s_j = (softmax(z^s)_j - [j == k]) / D at a kept pixel.
+ * D == 0 (nothing counted, or no pixel confident): loss 0 and all-zero gradient rows, not NaN.
+ * Arithmetic: fp32 per pixel in log-sum-exp form -- log p_c = z^s_c / T - lse_s, q_c log q_c as q_c (z^t_c / T - lse_t), log m_c from
+ * the two log-probabilities -- so confident, disagreeing views (logits +-80) give finite losses and gradients.
+ * ws: float [mrfp_consist_ws_floats(B, HW)], one partial of four words per workgroup of the (nbx, B) grid (mrfp_consist_nblocks):
+ * the fp32 sum of l / T^2, N_counted and N_kept as uint32; one workgroup adds them in double / 64-bit integers in a fixed order.  No
+ * floating-point atomics, nothing waits for the host: two runs are bit-identical and a call can be captured in a graph.
+ * loss: float [mrfp_consist_loss_floats() = 6], 8-byte aligned: loss[0] the loss; loss[1] the backward's factor, T / D (kl, js) or 1 / D
+ * (hard), 0 where D == 0; then int64 N_counted, int64 N_kept (kl, js: N_kept == N_counted).
+ * bwd: every gradient is multiplied by gscale[0] (NULL = 1); a view with a dlogits pointer gets one row per pixel, zeros where the
+ * pixel is not counted or not kept and in the pad channels.  dlogits_t must be NULL for kl and hard.  The upsample form writes
+ * d(logits)[B,H,W,Cd], Cd = C rounded up to a 16-byte chunk, for mrfp_bilinear_bwd exactly as mrfp_upsample_region_bwd (one row
+ * pitch for both views; each view's own mrfp_bilinear_bwd takes its rows down to its Hi x Wi x ld).
+ * ------------------------------------------------------------------------------------------- */
+typedef enum { MRFP_CONSIST_KL = 0, MRFP_CONSIST_JS = 1, MRFP_CONSIST_HARD = 2 } mrfp_consist_kind;
+typedef enum { MRFP_CONSIST_KEPT = 0, MRFP_CONSIST_VALID = 1 } mrfp_consist_normalize;
+int64_t mrfp_consist_max_classes(void);
+int64_t mrfp_consist_nblocks(int64_t B, int64_t HW);
+int64_t mrfp_consist_ws_floats(int64_t B, int64_t HW);
+int64_t mrfp_consist_loss_floats(void);
+int mrfp_consist_fwd(const void* logits_s, const void* logits_t, const int64_t* valid, int dtype, int64_t B, int64_t HW, int64_t C,
+                     int kind, float temperature, float threshold, int normalize, float* ws, float* loss, void* stream);
+int mrfp_consist_bwd(const void* logits_s, const void* logits_t, const int64_t* valid, const float* loss, const float* gscale,
+                     void* dlogits_s, void* dlogits_t, int dtype, int64_t B, int64_t HW, int64_t C, int kind, float temperature,
+                     float threshold, void* stream);
+int mrfp_upsample_consist_fwd(const void* P_s, int64_t ld_s, int64_t Hi_s, int64_t Wi_s, const void* P_t, int64_t ld_t,
+                              int64_t Hi_t, int64_t Wi_t, const int64_t* valid, int dtype, int64_t B, int64_t H, int64_t W,
+                              int64_t C, int kind, float temperature, float threshold, int normalize, float* ws, float* loss,
+                              void* stream);
+int mrfp_upsample_consist_bwd(const void* P_s, int64_t ld_s, int64_t Hi_s, int64_t Wi_s, const void* P_t, int64_t ld_t,
+                              int64_t Hi_t, int64_t Wi_t, const int64_t* valid, const float* loss, const float* gscale,
+                              void* dlogits_s, void* dlogits_t, int64_t Cd, int dtype, int64_t B, int64_t H, int64_t W, int64_t C,
+                              int kind, float temperature, float threshold, void* stream);
+
 /* Eval: argmax over classes + 19x19 confusion histogram on the device (reference main.py:898-909,
  * metrics.py:122-126): hist[num_classes*gt + pred] += 1 for gt in [0,num_classes).  hist: int64
  * [C*C], accumulated (not cleared).  pred (optional, uint8 [npix]) receives the arg-max. */

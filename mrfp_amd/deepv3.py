@@ -22,7 +22,7 @@ from torch import nn
 from . import ops
 from .config import cfg
 from .conv import wgrad_boundary
-from .loss import fused_ce_kwargs, fused_loss
+from .loss import ScoreMap, fused_ce_kwargs, fused_loss, refuse_two_view_criterion
 from .network import Resnet
 from .network.mynn import (HipBatchNorm2d, HipConv2d, HipInstanceNorm2d, Norm2d, Upsample, conv_norm, initialize_weights,
                            initialize_weights_kaimingnormal_forOC)
@@ -182,6 +182,21 @@ class _AtrousSpatialPyramidPoolingModule(nn.Module):
 
 
 class _DeepLabBase(nn.Module):
+    # keep_scores = True: a training forward leaves self.last_scores = loss.ScoreMap(dec2, size, classes), the autograd-attached
+    # low-resolution class scores the fused loss read, for a second criterion over them (loss.ConsistencyLoss2d through
+    # harness.ConsistencyStep).  False, the default: nothing is retained.
+    keep_scores = False
+    last_scores = None
+
+    def __setattr__(self, name, value):
+        if name in ("criterion", "criterion_aux"):
+            refuse_two_view_criterion("%s(%s=)" % (type(self).__name__, name), value)
+        super().__setattr__(name, value)
+
+    def _keep(self, dec2, size, nc, training):
+        if self.keep_scores and training:
+            self.last_scores = ScoreMap(dec2, size, nc)
+
     def _build_trunk_and_head(self, num_classes, trunk, wt_layer):
         if trunk == "wider_resnet38_a2" and self._allow_101:
             return self._build_wrn_trunk_and_head(num_classes)
@@ -301,6 +316,7 @@ class _DeepLabBase(nn.Module):
             if training:
                 raise ValueError("low_res is an eval-path option (training=False)")
             return dec2
+        self._keep(dec2, size, nc, training)
         if training and cfg.MODEL.FUSE_UPSAMPLE_CE and fused_ce_kwargs(self.criterion) is not None:
             return fused_loss(self.criterion, dec2, gts, size, nc)
         main_out = ops.upsample_bilinear(dec2, size, channels=nc)
@@ -319,6 +335,7 @@ class _DeepLabBase(nn.Module):
         pitch = (nc + 31) // 32 * 32
         p_low, p_half = conv.shared_conv1x1_pair(dec1, oc_dec, f2.weight, f2.bias, pitch)
         dec2 = ops.upsample_bilinear(p_low, (oc_dec.shape[2], oc_dec.shape[3]), addend=p_half)
+        self._keep(dec2, size, nc, training)
         if training and cfg.MODEL.FUSE_UPSAMPLE_CE and fused_ce_kwargs(self.criterion) is not None:
             return fused_loss(self.criterion, dec2, gts, size, nc)
         main_out = ops.upsample_bilinear(dec2, size, channels=nc)

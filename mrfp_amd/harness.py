@@ -559,7 +559,7 @@ class Trainer:
     optimiser step, the all-reduce and the LR step happen once per window of k calls, on the sum of the k gradients."""
 
     def __init__(self, model, lr=1e-2, momentum=0.9, weight_decay=5e-4, max_iter=40000, bucket_mb=32.0,
-                 loss_scale=None, max_grad_norm=None, accum_steps=1, loss_weights=None, average=None):
+                 loss_scale=None, max_grad_norm=None, accum_steps=1, loss_weights=None, average=None, loss_fn=None):
         """loss_scale: scale of the backward pass for float16 activations (the per-pixel CE gradient is 1/#pixels ~ 1e-7, below
         float16's normal range).
           None / a float, no max_grad_norm: a STATIC host-side scale, default 65536 when cfg.MODEL.ACT_DTYPE is float16, else 1.
@@ -591,8 +591,14 @@ class Trainer:
         description selects -- one update per accumulation window, none for a step or window the scaler
         skipped (that decision stays on the device), no extra launch, no collective (every rank steps from the same all-reduced
         bits).  averaged() evaluates with it, average_info() counts, save_checkpoint / load_checkpoint carry it.  None, the
-        default: nothing is allocated and the step launches what it launched before."""
+        default: nothing is allocated and the step launches what it launched before.
+        loss_fn: None | a callable (model, img, label) -> loss | list of losses that the pass runs in place of
+        model(img, label, training=True) -- a step with more than one forward (ConsistencyStep: the supervised forward, a teacher's
+        forward, a consistency term).  loss_weights applies to what it returns.  Eager only: enable_graph() refuses it."""
         from .config import cfg
+        if loss_fn is not None and not callable(loss_fn):
+            raise ValueError("loss_fn must be None or a callable (model, img, label) -> loss | list, got %r" % (loss_fn,))
+        self.loss_fn = loss_fn
         max_grad_norm = _check_max_grad_norm(max_grad_norm)
         average = _check_average(average)
         self.accum_steps, self.micro = _check_accum_steps(accum_steps), 0
@@ -635,7 +641,10 @@ class Trainer:
         self.sync.begin(reduce=last, accum=last and self.accum_steps > 1)
         ok = False
         try:
-            loss = self._total_loss(self.model(img, label, training=True))
+            if self.loss_fn is not None:
+                loss = self._total_loss(self.loss_fn(self.model, img, label))
+            else:
+                loss = self._total_loss(self.model(img, label, training=True))
             if self.scaler is not None:
                 loss.backward(self.scaler.scale_tensor)      # a device address: a replayed graph reads the scale of its own step
             elif self.loss_scale != 1.0:
@@ -756,6 +765,9 @@ class Trainer:
     # accumulate launch and the decision whether to step stay eager.
     # Single-process only: the overlapped all-reduce of GradSync is driven by Python hooks.
     def enable_graph(self):
+        if self.loss_fn is not None:
+            # (the capture fixes ONE toggle draw per step and one forward; a second forward inside it is out of scope)
+            raise _lib.MrfpHipError("Trainer graph mode captures model(img, label, training=True): a Trainer with a loss_fn runs eagerly")
         if self.sync.enabled:
             raise _lib.MrfpHipError("Trainer graph mode is single-process (the overlapped all-reduce is hook-driven)")
         self.graph = True
@@ -829,6 +841,57 @@ class Trainer:
                 m._nbt_pending += 1
         self._end_pass(1.0)                               # eager, after the replay: accumulate, or close the window and step
         return static_loss
+
+
+class ConsistencyStep:
+    """A Trainer loss_fn: the supervised step plus a consistency term between the model's scores and a teacher's.
+        step = ConsistencyStep(loss.ConsistencyLoss2d("kl", temperature=2.0), weight=0.5, teacher=teacher_model)
+        Trainer(model, loss_fn=step, ...)
+    Per call: (1) model(img, label, training=True) with keep_scores, so the head leaves model.last_scores, the autograd-attached
+    low-resolution scores its fused loss read; (2) under no_grad, teacher(img, training=False, low_res=True), the teacher's padded
+    low-resolution scores (another output stride or pitch is fine); (3) criterion(student scores, teacher scores, valid) on the fused
+    kernels, valid = the labels (valid_from_labels: ignored pixels do not count) or None.  Returns [*supervised, weight * consistency]:
+    Trainer(loss_weights=) still applies, with one more entry.
+    teacher=None: the model's OWN unperturbed view, model(img, training=False, low_res=True) -- MRFPPlus only, whose perturbations
+    are switched by the `training` argument while the module stays in train() mode.  Its BatchNorm layers therefore normalise that
+    view with batch statistics and update their running statistics from it too: every step feeds them one perturbed and one
+    unperturbed batch.  A separate teacher module should be in eval() mode (network/deepv3.py factories require it for low_res);
+    it is never written: no parameter, no buffer.  `model` may be a wrapper: the first submodule with keep_scores is used."""
+
+    def __init__(self, criterion, weight=1.0, teacher=None, valid_from_labels=True):
+        from .loss import ConsistencyLoss2d
+        if not isinstance(criterion, ConsistencyLoss2d):
+            raise TypeError("ConsistencyStep: criterion must be a loss.ConsistencyLoss2d, got %r" % (type(criterion),))
+        if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not math.isfinite(float(weight)):
+            raise ValueError("ConsistencyStep: weight must be a finite number, got %r" % (weight,))
+        self.criterion, self.weight, self.teacher, self.valid_from_labels = criterion, float(weight), teacher, bool(valid_from_labels)
+
+    @staticmethod
+    def _scored(model):
+        for m in model.modules():
+            if hasattr(m, "keep_scores") and hasattr(m, "_head"):
+                return m
+        raise TypeError("ConsistencyStep: the model has no head that keeps its scores (deepv3._DeepLabBase.keep_scores)")
+
+    def __call__(self, model, img, label):
+        from .deepv3 import MRFPPlus
+        net = self._scored(model)
+        if self.teacher is None and not isinstance(net, MRFPPlus):
+            raise TypeError("ConsistencyStep(teacher=None) takes the model's own unperturbed view, which only MRFPPlus has "
+                            "(its perturbations follow the `training` argument): give %s a teacher module" % type(net).__name__)
+        was = net.keep_scores
+        net.keep_scores = True
+        try:
+            sup = model(img, label, training=True)
+        finally:
+            net.keep_scores = was
+        student, net.last_scores = net.last_scores, None
+        with torch.no_grad():
+            P = (net if self.teacher is None else self.teacher)(img, training=False, low_res=True)
+        from .loss import ScoreMap
+        cons = self.criterion(student, ScoreMap(P, student.size, student.channels), label if self.valid_from_labels else None)
+        sup = list(sup) if isinstance(sup, (list, tuple)) else [sup]
+        return sup + [cons if self.weight == 1.0 else self.weight * cons]
 
 
 def graph_topology(g):

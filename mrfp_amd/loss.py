@@ -28,6 +28,12 @@ LovaszSoftmax2d is the third: the Lovasz-Softmax loss (Berman, Triki, Blaschko, 
 index, usually trained as CE + lambda * Lovasz -- SumLoss again.  Not in the reference tree either; the published form soft-maxes the
 full-resolution logits and runs one torch.sort and one cumulative sum per class on them; here the ranking is a stable segmented
 radix sort on the device (csrc/sort.hip, csrc/lovasz.hip) and the fused form never writes the full-resolution logits.
+
+ConsistencyLoss2d compares the class scores of TWO forward passes instead of scores with a label map: KL against a teacher at a
+temperature, the Jensen-Shannon divergence of two views, or the pseudo-label cross entropy with a confidence threshold -- the
+regulariser of MRFP's perturbed against its unperturbed view, self-training against the averaged weights, distillation into a smaller
+model.  Not in the reference tree: include/mrfp_hip.h and DESIGN.md section 8 hold the definitions; the kernels are csrc/consist.hip.
+It is NOT an (inputs, targets) criterion: a model refuses it as `criterion`, harness.ConsistencyStep is the callable that runs it.
 """
 from __future__ import annotations
 
@@ -37,7 +43,7 @@ from torch import nn
 from . import ops
 
 __all__ = ["ImageBasedCrossEntropyLoss2d", "ImgWtLossSoftNLL", "OhemCrossEntropy2d", "FocalLoss2d", "RegionLoss2d",
-           "LovaszSoftmax2d", "SumLoss", "fused_ce_kwargs", "fused_loss"]
+           "LovaszSoftmax2d", "SumLoss", "ScoreMap", "ConsistencyLoss2d", "fused_ce_kwargs", "fused_loss"]
 
 
 class ImageBasedCrossEntropyLoss2d(nn.Module):
@@ -245,6 +251,56 @@ class SumLoss(nn.Module):
         return total
 
 
+class ScoreMap:
+    """Fused class scores: P, the channel-padded low-resolution buffer [B,ld,Hi,Wi] of a model's head (autograd-attached where the
+    model trains), to be upsampled to `size` = (H, W) inside the loss kernel, its first `channels` planes the classes."""
+    __slots__ = ("P", "size", "channels")
+
+    def __init__(self, P, size, channels):
+        self.P, self.size, self.channels = P, (int(size[0]), int(size[1])), int(channels)
+
+    def detach(self):
+        return ScoreMap(self.P.detach(), self.size, self.channels)
+
+
+class ConsistencyLoss2d(nn.Module):
+    """forward(student, teacher, valid=None): ops.consistency_loss of two dense logit tensors, or ops.upsample_consistency_loss of two
+    ScoreMaps of one size and class count (their pitch and low resolution may differ).  kind 'kl' (T^2 KL(teacher || student), the
+    teacher a constant), 'js' (T^2 times the Jensen-Shannon divergence, a gradient to every view that requires one) or 'hard' (cross
+    entropy against the teacher's arg-max where its confidence reaches `threshold`, over the kept pixels or, normalize='valid', over
+    the counted ones).  valid: an int64 [B,H,W] label map, a pixel counts iff 0 <= valid < C; None: every pixel.  Nothing counted or
+    kept: 0.  At most 64 classes.  Not an (inputs, targets) criterion: fused_ce_kwargs has no entry for it and a model refuses it."""
+
+    def __init__(self, kind="kl", temperature=1.0, threshold=0.0, normalize="kept"):
+        super().__init__()
+        ops._consist_options("ConsistencyLoss2d", kind, temperature, threshold, normalize)
+        self.kind, self.temperature, self.threshold, self.normalize = kind, float(temperature), float(threshold), normalize
+
+    def forward(self, student, teacher, valid=None, want_counts=False):
+        if isinstance(teacher, torch.Tensor) and not teacher.is_floating_point():
+            raise TypeError("ConsistencyLoss2d compares the class scores of two forward passes: forward(student, teacher, valid=None); "
+                            "it is not an (inputs, targets) criterion (got an integer tensor as the teacher's scores)")
+        kw = dict(kind=self.kind, temperature=self.temperature, threshold=self.threshold, normalize=self.normalize,
+                  want_counts=want_counts)
+        fused = (isinstance(student, ScoreMap), isinstance(teacher, ScoreMap))
+        if fused[0] != fused[1]:
+            raise ops._lib.MrfpHipError("ConsistencyLoss2d: both views are dense logits or both are ScoreMaps (mixed forms are not built)")
+        if not fused[0]:
+            return ops.consistency_loss(student, teacher, valid, **kw)
+        if student.size != teacher.size or student.channels != teacher.channels:
+            raise ops._lib.MrfpHipError("ConsistencyLoss2d: the two ScoreMaps have one output size and one class count (got %s x %d and "
+                                        "%s x %d)" % (student.size, student.channels, teacher.size, teacher.channels))
+        return ops.upsample_consistency_loss(student.P, teacher.P, student.size, student.channels, valid, **kw)
+
+
+def refuse_two_view_criterion(name, criterion):
+    """A model's `criterion` / `criterion_aux` is called as criterion(inputs, targets): ConsistencyLoss2d is not such a module."""
+    if isinstance(criterion, ConsistencyLoss2d):
+        raise TypeError("%s: ConsistencyLoss2d compares two forward passes, forward(student, teacher, valid=None), and is not an "
+                        "(inputs, targets) criterion: keep the model's supervised criterion and hand the Trainer a "
+                        "harness.ConsistencyStep as loss_fn" % name)
+
+
 def fused_ce_kwargs(criterion):
     """The keyword arguments with which ops.cross_entropy / ops.upsample_cross_entropy compute `criterion`, or None for a criterion
     they cannot (reduction='none', a foreign module): that one keeps the stock call on the full-resolution fp32 logits.  `weight` is
@@ -253,6 +309,8 @@ def fused_ce_kwargs(criterion):
     OhemCrossEntropy2d chooses its pixels first: dict(ohem=<its own fused call>), called the same way; so are FocalLoss2d (dict(focal=),
     None with reduction='none'), RegionLoss2d (dict(region=)), LovaszSoftmax2d (dict(lovasz=)) and SumLoss (dict(sum=), None if a part has none)."""
     c = criterion
+    if isinstance(c, ConsistencyLoss2d):          # two forward passes, no label map: not an (inputs, targets) criterion at all
+        return None
     if isinstance(c, FocalLoss2d):
         return dict(focal=c.fused) if c.reduction in ("mean", "sum") else None
     if isinstance(c, RegionLoss2d):

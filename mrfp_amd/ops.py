@@ -998,13 +998,18 @@ class _Scores:
             env.update(ld=self.ld, Hi=self.Hi, Wi=self.Wi)
         return env
 
-    def grad(self, entry, env):
+    def grad(self, entry, env, tag=""):
         """d(loss)/d(scores) by the backward `entry`.  Dense: the entry writes it.  Fused: the entry writes d(loss)/d(logits) at full
-        resolution once, channel-padded to Cd, and the gather-form bilinear backward takes it to dP."""
+        resolution once, channel-padded to Cd, and the gather-form bilinear backward takes it to dP.
+        tag: a two-view entry (mrfp_[upsample_]consist_bwd) names this view's rows dlogits<tag>; it is launched once for both views,
+        by the caller: with entry None this only places the row buffer in env and returns finish() -> the gradient, to be called
+        after that launch."""
         x = self.x
         if not self.fused:
             d = torch.empty_like(x, memory_format=CL)
-            env["dlogits"] = ptr(d)
+            env["dlogits" + tag] = ptr(d)
+            if entry is None:
+                return lambda: d
             _call_named(entry, env)
             return d
         B, ld, Hi, Wi, H, W = self.B, self.ld, self.Hi, self.Wi, self.H, self.W
@@ -1012,12 +1017,24 @@ class _Scores:
         Cd = (self.C + epc - 1) // epc * epc
         dP = empty_cl(B, ld, Hi, Wi, x.dtype, x.device)
         dlog = empty_cl(B, Cd, H, W, x.dtype, x.device)
-        env.update(dlogits=ptr(dlog), Cd=Cd)
+        env.update({"dlogits" + tag: ptr(dlog), "Cd": Cd})
+
+        def down():
+            if ld != Cd:
+                dP.zero_()
+            call("mrfp_bilinear_bwd", ptr(dlog), ptr(dP), dt(x), B, Hi, Wi, H, W, Cd, ld, stream())
+            return dP
+        if entry is None:
+            return down
         _call_named(entry, env)
-        if ld != Cd:
-            dP.zero_()
-        call("mrfp_bilinear_bwd", ptr(dlog), ptr(dP), dt(x), B, Hi, Wi, H, W, Cd, ld, stream())
-        return dP
+        return down()
+
+    def view_env(self, tag):
+        """This view's own arguments of a two-view entry under the header's names: logits<tag> / P<tag> and, fused, ld / Hi / Wi<tag>."""
+        env = {"logits" + tag: ptr(self.x), "P" + tag: ptr(self.x)}
+        if self.fused:
+            env.update({"ld" + tag: self.ld, "Hi" + tag: self.Hi, "Wi" + tag: self.Wi})
+        return env
 
 
 class _PlainCe:
@@ -1595,6 +1612,149 @@ def lovasz_errors(logits, target, ignore_index=255, *, size=None, channels=None)
     call("mrfp_lovasz_errors", ptr(src.x), src.ld if fused else 0, ptr(target), dt(src.x), src.B, src.Hi if fused else 0,
          src.Wi if fused else 0, src.H, src.W, src.C, int(ignore_index), ptr(err), stream())
     return err
+
+
+# ---- two-view consistency losses (csrc/consist.hip; include/mrfp_hip.h and DESIGN.md section 8 hold the definitions).  The "target" of a
+# pixel is the class vector of a second forward pass, so this is no criterion record of _PixelLoss: one autograd function over TWO
+# _Scores, both dense or both fused, launched once forward and once backward for both views ----
+CONSIST_KINDS = {"kl": 0, "js": 1, "hard": 2}        # mrfp_consist_kind
+CONSIST_NORMALIZE = {"kept": 0, "valid": 1}          # mrfp_consist_normalize
+CONSIST_MAX_CLASSES = 64                             # mrfp_consist_max_classes(): the student's class vector lives in registers
+
+
+def _consist_options(who, kind, temperature, threshold, normalize):
+    """-> (kind id, T, threshold, normalize id), validated without touching the device or the library."""
+    if not isinstance(kind, str) or kind not in CONSIST_KINDS:
+        raise _lib.MrfpHipError("%s: kind must be 'kl', 'js' or 'hard' (got %r)" % (who, kind))
+    try:
+        T, thr = float(temperature), float(threshold)
+    except (TypeError, ValueError):
+        T = thr = float("nan")
+    if not 0.0 < T < float("inf"):              # also false for a NaN
+        raise _lib.MrfpHipError("%s: temperature must be a finite number > 0 (got %r)" % (who, temperature))
+    if not 0.0 <= thr <= 1.0:
+        raise _lib.MrfpHipError("%s: threshold must be in [0, 1] (got %r)" % (who, threshold))
+    if not isinstance(normalize, str) or normalize not in CONSIST_NORMALIZE:
+        raise _lib.MrfpHipError("%s: normalize must be 'kept' or 'valid' (got %r)" % (who, normalize))
+    return CONSIST_KINDS[kind], T, thr, CONSIST_NORMALIZE[normalize]
+
+
+def _consist_views(who, student, teacher, valid, size, channels):
+    """The two views and the validity map against each other, before the library is touched: types, dtypes, shapes, the class limit,
+    and last the devices.  -> (C, H, W)."""
+    for name, t in (("student", student), ("teacher", teacher)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise _lib.MrfpHipError("%s: %s must be a 4-D tensor, dense logits [B,C,H,W] or fused scores [B,ld,Hi,Wi] (got %s)" % (
+                who, name, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)))
+    if student.dtype != teacher.dtype or student.dtype not in _lib._DT:
+        raise _lib.MrfpHipError("%s: both views have one dtype, float32 / bfloat16 / float16 (got %s and %s)" % (
+            who, student.dtype, teacher.dtype))
+    if size is None:
+        if tuple(student.shape) != tuple(teacher.shape):
+            raise _lib.MrfpHipError("%s: dense views have one shape [B,C,H,W] (got %s and %s)" % (
+                who, tuple(student.shape), tuple(teacher.shape)))
+        C, H, W = student.shape[1:]
+    else:
+        H, W, C = int(size[0]), int(size[1]), int(channels)
+        epc = 16 // student.element_size()
+        if student.shape[0] != teacher.shape[0] or H < 1 or W < 1:
+            raise _lib.MrfpHipError("%s: the views have one batch size and one output size (got %s and %s -> %s)" % (
+                who, tuple(student.shape), tuple(teacher.shape), (H, W)))
+        for name, t in (("student", student), ("teacher", teacher)):
+            if t.shape[1] % epc or t.shape[1] < C or C < 1:
+                raise _lib.MrfpHipError("%s: the %s's scores must be channel-padded to 16-byte chunks and hold %d classes (ld=%d)" % (
+                    who, name, C, t.shape[1]))
+    if not 1 <= int(C) <= CONSIST_MAX_CLASSES:
+        raise _lib.MrfpHipError("%s: 1 <= C <= %d: the student's class vector lives in registers (C=%d)" % (who, CONSIST_MAX_CLASSES, C))
+    if valid is not None and (not isinstance(valid, torch.Tensor) or valid.dtype != torch.int64
+                              or tuple(valid.shape) != (student.shape[0], H, W)):
+        raise _lib.MrfpHipError("%s: valid must be None or an int64 [B,H,W] label map (got %s)" % (
+            who, (valid.dtype, tuple(valid.shape)) if isinstance(valid, torch.Tensor) else type(valid)))
+    for name, t in (("student", student), ("teacher", teacher), ("valid", valid)):
+        if t is not None and (not t.is_cuda or t.device != student.device):
+            raise _lib.MrfpHipError("%s: %s must live on the student's GPU (got %s): the HIP path has no CPU fallback" % (who, name, t.device))
+    return int(C), int(H), int(W)
+
+
+def _consist_env(ss, st, valid, out, opts):
+    kind, T, thr, norm = opts
+    env = ss.env()
+    env.update(ss.view_env("_s"))
+    env.update(st.view_env("_t"))
+    env.update(valid=ptr(valid), loss=ptr(out), kind=kind, temperature=T, threshold=thr, normalize=norm)
+    return env
+
+
+class _Consistency(torch.autograd.Function):
+    """(loss, counts) = the consistency criterion of two views at full resolution: two launches forward (pixel loop, finalize;
+    neither waits for the host), one backward for both views plus the bilinear backward of each fused view that takes a gradient.
+    counts: int64 [2] on the device, (N_counted, N_kept)."""
+
+    @staticmethod
+    def forward(ctx, xs, xt, valid, size, channels, opts):
+        ss = _Scores(_chk(xs, "student"), size, channels)
+        st = _Scores(_chk(xt, "teacher"), size, channels)
+        valid = None if valid is None else valid.contiguous()
+        L, dev = _lib.lib(), ss.x.device
+        nloss = int(L.mrfp_consist_loss_floats())
+        nws = int(L.mrfp_consist_ws_floats(ss.B, ss.H * ss.W))
+        # (one zero-filled buffer, not torch.empty: tests/test_poison_gpu.py holds the table of the functions that obtain uninitialised
+        #  memory; 8 + 4 * workgroups floats.  The loss words come first: 8-byte aligned)
+        buf = torch.zeros(8 + nws, dtype=torch.float32, device=dev)
+        out, ws = buf[:nloss], buf[8:]
+        env = _consist_env(ss, st, valid, out, opts)
+        env["ws"] = ptr(ws)
+        _call_named(ss.prefix + "consist_fwd", env)
+        ctx.save_for_backward(ss.x, st.x, valid, buf)
+        ctx.size, ctx.channels, ctx.opts = size, channels, opts
+        counts = out[2:6].view(torch.int64).clone()
+        ctx.mark_non_differentiable(counts)
+        return out[0].clone(), counts
+
+    @staticmethod
+    def backward(ctx, g, _gcounts):
+        xs, xt, valid, buf = ctx.saved_tensors
+        ss, st = _Scores(xs, ctx.size, ctx.channels), _Scores(xt, ctx.size, ctx.channels)
+        gs = g.detach().float().reshape(1).contiguous()
+        env = _consist_env(ss, st, valid, buf, ctx.opts)
+        env.update(gscale=ptr(gs), dlogits_s=None, dlogits_t=None, Cd=0)
+        js = ctx.opts[0] == CONSIST_KINDS["js"]
+        fin_s = ss.grad(None, env, "_s") if ctx.needs_input_grad[0] else None
+        fin_t = st.grad(None, env, "_t") if js and ctx.needs_input_grad[1] else None
+        _call_named(ss.prefix + "consist_bwd", env)
+        return (None if fin_s is None else fin_s()), (None if fin_t is None else fin_t()), None, None, None, None
+
+
+def _consistency(who, student, teacher, valid, size, channels, kind, temperature, threshold, normalize, want_counts):
+    opts = _consist_options(who, kind, temperature, threshold, normalize)
+    _consist_views(who, student, teacher, valid, size, channels)
+    if kind != "js":
+        teacher = teacher.detach()           # the teacher is a constant of kl and hard
+    loss, counts = _Consistency.apply(student, teacher, valid, size, channels, opts)
+    return (loss, counts) if want_counts else loss
+
+
+def consistency_loss(student, teacher, valid=None, *, kind="kl", temperature=1.0, threshold=0.0, normalize="kept", want_counts=False):
+    """The consistency of two views' class scores, dense logits [B,C,H,W] of one shape and dtype, C <= 64.  With p = softmax(student / T),
+    q = softmax(teacher / T), m = (p + q) / 2, over the counted pixels (valid: an int64 [B,H,W] label map, counted iff 0 <= valid < C --
+    the ground truth as it is -- or None: every pixel):
+      kind 'kl':   T^2 KL(q || p), the mean over the counted pixels; the teacher is a constant.
+      kind 'js':   T^2 (KL(p || m) + KL(q || m)) / 2, the same mean; the gradient goes to every view that requires one.
+      kind 'hard': the cross entropy of the student against the teacher's arg-max (the first maximum) over the pixels whose teacher
+                   confidence softmax(teacher)_k (at T = 1: temperature does not enter this kind) reaches `threshold`; divided by the
+                   kept pixels (normalize 'kept') or by the counted ones ('valid': weighted by the confident share).  The teacher is a
+                   constant.
+    An empty denominator gives 0 and a zero gradient.  -> fp32 scalar; with want_counts (loss, int64 [2] on the device: N_counted, N_kept)."""
+    return _consistency("consistency_loss", student, teacher, valid, None, None, kind, temperature, threshold, normalize, want_counts)
+
+
+def upsample_consistency_loss(Ps, Pt, size, channels, valid=None, *, kind="kl", temperature=1.0, threshold=0.0, normalize="kept",
+                              want_counts=False):
+    """consistency_loss of Upsample(Ps[:, :channels], size) and Upsample(Pt[:, :channels], size) without materialising either at full
+    resolution.  Ps, Pt: channel-padded low-resolution class scores [B,ld,Hi,Wi] (ld a multiple of the 16-byte chunk), which may
+    differ in ld, Hi and Wi -- a teacher with another output stride."""
+    return _consistency("upsample_consistency_loss", Ps, Pt, valid, (int(size[0]), int(size[1])), int(channels), kind, temperature,
+                        threshold, normalize, want_counts)
 
 
 def _chk_u32(who, name, t, n=None):
